@@ -2,6 +2,7 @@
 """bench.py — the contract benchmark of the HQQ forward hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|decode|decode70b|prefill] [--nbits 4|2|3] [--bs M]
+                    [--full] [--dump-outputs DIR]
 
 Headline (N = 1; BASELINE.json configs[1], the configuration the metric is quoted on):
   one *step* = one token (bs=1) through every quantised linear of a Llama-2-7B decoder stack —
@@ -11,18 +12,20 @@ Headline (N = 1; BASELINE.json configs[1], the configuration the metric is quote
   every step is HBM traffic).  Weights are synthetic N(0, 0.02^2) fp16 tensors quantised on the GPU by the
   HIP half-quadratic solver before timing.  Arithmetic: exact weights (round16(round16(q - z) * s), the
   reference's), in the three-op form wherever hqq_hip_meta_check allows it.
-  `legs` adds the other shapes the metric names (bs=32; one 4096x4096 layer at bs=1 / bs=32), the int3 / int2 stacks, bs=128 and the
-  prefill block; `quantize` times the other hot path; `end_to_end` the fused decode loop; `cpu_baseline` times the reference's per-call arithmetic
-  (unpack -> (W_r - zero) * scale -> matmul, hqq/core/bitpack.py:31-38, quantize.py:183-199, :880-882) restated
-  in torch eager on the host cores of this box.
+  A plain run times the headline only.  With --full, `legs` adds the other shapes the metric names (bs=32; one 4096x4096 layer at bs=1 / bs=32),
+  the int3 / int2 stacks, bs=128 and the prefill block; `quantize` times the other hot path; `end_to_end` the fused decode loop; `cpu_baseline`
+  times the reference's per-call arithmetic (unpack -> (W_r - zero) * scale -> matmul, hqq/core/bitpack.py:31-38, quantize.py:183-199, :880-882)
+  restated in torch eager on the host's cores.
+  --dump-outputs DIR writes the last timed step's outputs (what a caller of the step receives) as DIR/<layer>.npy, float32; the inputs are
+  seeded, so two builds run with the same arguments can be compared output for output.
   `--workload prefill` runs configs[2]: M tokens (default 8192 = 4 x 2048) through one block's seven linears.
 
 Multi-GPU (launched by torch.distributed.run, one rank per GPU, RCCL).  Default for N > 1 (`auto`) is BASELINE
 configs[4]: the Llama-2-70B linear shapes (q,o 8192x8192; k,v 1024x8192; gate,up 28672x8192; down 8192x28672),
 nbits=4, every layer's output columns sharded over the N ranks (packed-row blocks of the reference layout,
 hqq_amd/shard.py) — STRONG scaling of fixed layers: x is replicated, every exchange point (after q|k|v, o,
-gate|up, down) completes the outputs in the reference's column order inside the timed region, and the exchange is
-also timed on its own.  At one activation row the exchange is per-slab RCCL all-gathers in one coalesced launch (straight into
+gate|up, down) completes the outputs in the reference's column order inside the timed region, and with --full the
+exchange is also timed on its own.  At one activation row the exchange is per-slab RCCL all-gathers in one coalesced launch (straight into
 the reference's column order) or, where the backend cannot coalesce, the shard-wide all-gather + un-permute; HQQ_BENCH_EXCHANGE=peer
 opts into one small kernel storing the rank's slices into every rank's full rows over peer memory (csrc/exchange.hip; fine-grained
 arenas mapped through IPC handles, validated against the collective at start-up; a wait that gives up fails the run) — opt-in until
@@ -101,7 +104,16 @@ def parse():
     ap.add_argument("--gemv-mode", default="exact", choices=["exact", "exact4", "factored"],
                     help="exact: reference-identical weights, three-op rebuild where the meta allows it (default); exact4: always the "
                          "general four-op rebuild; factored: fp32 affine map factored out of the dot product (not the reference's weights)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the benchmark measures: the extra legs, the CPU baseline and, for N > 1, the "
+                         "exchange timed on its own and the unsharded stack on one GPU (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step, one float32 DIR/<layer>.npy per layer of a block (q, k, v, o, gate, up, down); "
+                         "above 64 MB in all, a fixed seeded sample of the rows")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 class Layer:
@@ -568,6 +580,19 @@ def main():
     if xmode.get("peer") is not None:   # a wait that gave up inside the timed region: the rows of that exchange were undefined — not a measurement
         st_ = xmode["peer"].status()
         assert st_ == 0, f"rank {rank}: the peer-memory exchange reported a wait that gave up (status {st_}) inside the timed region"
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed step receives: every block writes the same output buffers, so they hold the last block's outputs of the last step
+        # (N > 1: the exchanged full rows in the reference's column order; --streams S: the branch that wrote each group last)
+        res = {}
+        for gi, grp in enumerate(EXCHANGE_GROUPS):
+            if S > 1:
+                ts = out_local_s[((nblocks - 1) * len(EXCHANGE_GROUPS) + gi) % S][grp]
+            elif world > 1 and not whole[grp[0]]:
+                ts = out_full[grp]
+            else:
+                ts = out_local[grp]
+            res.update(zip(grp, ts))
+        _dump_outputs(a.dump_outputs, res)
 
     # ---- accounting ----
     launches_per_step = nblocks * (len(EXCHANGE_GROUPS) if grouped else len(BLOCK))
@@ -616,7 +641,7 @@ def main():
                            "bytes_per_launch": bytes_per_step_rank // unit_launches,
                            "note": "avg launch = HIP-event time of the timed region / dependent stages (includes inter-kernel gaps"
                                    + ("; and the all-gathers" if world > 1 else "") + ")"}
-        if world > 1:   # the exchange alone (same graph structure without the GEMV launches)
+        if world > 1 and a.full:   # the exchange alone (same graph structure without the GEMV launches)
             xrun, _ = _graphed(lambda: step(only_exchange=True), use_graph, rank)
             xs_, _ = _timed(xrun, max(5, a.steps // 2), 3, dist, dev)
             rows1 = bool(M == 1 and xmode.get("rows1"))
@@ -689,7 +714,7 @@ def main():
                            "traffic": None, "kernel": route_kernel, "mfma_busy": _pmc_dense_busy()}
 
     # ---- the other shapes the metric names, same resident weights (N = 1, default decode only) ----
-    if decode and world == 1 and not a.no_legs and not big and M == 1 and a.dtype == "f16" and S == 1 and nbits in (4, 2, 8):
+    if a.full and decode and world == 1 and not a.no_legs and not big and M == 1 and a.dtype == "f16" and S == 1 and nbits in (4, 2, 8):
         legs = []
 
         def leg(name, fn, nbytes, rows, launches, kernel):
@@ -1152,11 +1177,29 @@ def main():
         out["legs"] = legs
 
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nbits)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(path, outs):
+    """outs: {layer name: [M, N] device tensor} -> path/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, the same seeded
+    sample of rows is kept from every layer, so two builds run with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    M = next(iter(outs.values())).shape[0]
+    rows_fit = max(1, DUMP_LIMIT_BYTES // (4 * sum(t.shape[1] for t in outs.values())))
+    keep = None
+    if M > rows_fit:
+        keep = torch.from_numpy(np.sort(np.random.default_rng(0).choice(M, size=rows_fit, replace=False)))
+    for name, t in outs.items():
+        t = t.detach() if keep is None else t.detach()[keep.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def _decode_kernel_name(nbits, M, dtype, mode):

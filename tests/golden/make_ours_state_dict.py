@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Run ON THE GPU BOX: quantise the BASELINE configs[0] layer (nn.Linear(1024,1024,bias=True), seed 0, 4-bit gs=64) with the HIP
 solver and write hqq_amd.HQQLinear.state_dict() — the wire format of hqq/core/quantize.py:617-680 as THIS build emits it — to an
-.npz.  tests/test_wire_format_cpu.py loads that file into the REFERENCE's HQQLinear (where /root/reference is mounted) and checks
-the reference's own forward on it.
+.npz.  tests/golden/make_refload_golden.py loads that file into the REFERENCE's HQQLinear and records what the reference computes
+from it; tests/test_wire_format_cpu.py checks both files.
 
     gpurun -- 'python tests/golden/make_ours_state_dict.py gpurun_out/ours_sd_cfg1_4b.npz'   # then copy into tests/golden/
 """

@@ -30,7 +30,7 @@ def _run(mode, bs, plan="sharded"):
     else:
         env["HQQ_BENCH_EXCHANGE"] = mode
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bs", str(bs), "--blocks", "2", "--steps", "3", "--warmup", "1", "--random-codes", "--no-single-gpu-reference", "--plan", plan]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bs", str(bs), "--blocks", "2", "--steps", "3", "--warmup", "1", "--random-codes", "--no-single-gpu-reference", "--plan", plan, "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
