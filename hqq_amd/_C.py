@@ -57,10 +57,16 @@ SYMBOLS = {
     "hqq_hip_quantize_axis0": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                       _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "hqq_hip_optimize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # ABI 9: the solver's precision per call (solver_dtype F32 / F16 after lp_norm; scale_out / zero_out fp16 with F16)
+    "hqq_hip_quantize_solver": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32,
+                                       _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hqq_hip_quantize_axis0_solver": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32,
+                                             _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hqq_hip_optimize_solver": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "hqq_hip_quantize_tensor": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 _lib = None
 
 

@@ -50,7 +50,12 @@ class Quantizer:
     @classmethod
     def quantize(cls, tensor: Tensor, nbits: float = 4, channel_wise: bool = True, group_size: int = 64, optimize: bool = True,
                  round_zero: bool = False, axis: int = 0, bitpack: bool = True, compute_dtype: Union[torch.dtype, None] = None,
-                 view_as_float: bool = False, device: str = "cuda") -> tuple:
+                 view_as_float: bool = False, device: str = "cuda", solver_dtype: torch.dtype = torch.float32) -> tuple:
+        """solver_dtype: torch.float32 (default) is the reference's solver as it runs on the CPU; torch.float16 is the same solver in the
+        reference's GPU precision (optimize.py:231), and meta["scale"] / meta["zero"] are then fp16, as the reference returns them.
+        Neither changes the channel_wise=False / optimize=False results (no solver runs there)."""
+        if solver_dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"hqq_amd: solver_dtype must be torch.float32 or torch.float16, got {solver_dtype}")
         assert nbits in Quantizer.SUPPORTED_BITS, "nbits=" + str(nbits) + " not supported."
         assert axis in [0, 1], "axis should be either 0 or 1"
         if group_size is not None:
@@ -75,7 +80,8 @@ class Quantizer:
         # group_size None: one group per row (axis 1) / per column (axis 0) — HQQLinear.initialize resolves it the same way (quantize.py:434-439)
         gs = (tensor.shape[-1] if axis == 1 else tensor.shape[0]) if group_size is None else group_size
         W = tensor.to(device)
-        W_q, scale, zero = ops.quantize(W, nbits=nbits, group_size=gs, round_zero=round_zero, optimize=optimize, axis=axis)
+        W_q, scale, zero = ops.quantize(W, nbits=nbits, group_size=gs, round_zero=round_zero, optimize=optimize, axis=axis,
+                                        solver_dtype=solver_dtype if optimize else torch.float32)
         meta = {"nbits": nbits, "group_size": group_size, "shape": shape, "scale": scale, "zero": zero, "axis": axis,
                 "packing": Quantizer.bit_to_packing[nbits]}
         if not bitpack:   # the levels themselves, in the input dtype (quantize.py:169): unpack what the fused solver packed
@@ -225,7 +231,9 @@ class HQQLinear(nn.Module):
     backend = HQQBackend.HIP   # class-wide default (the reference's is PYTORCH, quantize.py:389)
 
     def __init__(self, linear_layer: Union[nn.Module, None], quant_config: Union[dict, None], del_orig: bool = True,
-                 compute_dtype: torch.dtype = float16, device: str = "cuda", initialize: bool = True):
+                 compute_dtype: torch.dtype = float16, device: str = "cuda", initialize: bool = True, solver_dtype: torch.dtype = torch.float32):
+        """solver_dtype: the precision of the quantiser's solver (torch.float16: the reference's GPU result).  It is not part of the
+        quant_config nor of the state_dict: the stored bytes say nothing about how they were solved."""
         super().__init__()
         self.ready = False
         self.in_gpu = False
@@ -234,6 +242,7 @@ class HQQLinear(nn.Module):
         self.channel_wise = None
         self.device = device
         self.compute_dtype = compute_dtype
+        self.solver_dtype = solver_dtype
         self.quant_config = copy.deepcopy(quant_config)
         self.del_orig = del_orig
         self.offload_meta = self.quant_config.pop("offload_meta") if (self.quant_config is not None) else None
@@ -257,7 +266,7 @@ class HQQLinear(nn.Module):
         wq = self.quant_config["weight_quant_params"]
         if wq["group_size"] is None:
             wq["group_size"] = self.linear_layer.in_features if (wq["axis"] == 1) else self.linear_layer.out_features
-        self.quantize(self.linear_layer.weight.data, **self.quant_config)
+        self.quantize(self.linear_layer.weight.data, **self.quant_config, solver_dtype=self.solver_dtype)
         self.bias = None if (self.linear_layer.bias is None) else self.linear_layer.bias.clone().to(device=self.device, dtype=self.compute_dtype)
         if self.del_orig:
             for name, _ in list(self.linear_layer.named_parameters()):
@@ -444,9 +453,9 @@ class HQQLinear(nn.Module):
 
     # ---- quantise / dequantise ----
     def quantize(self, W: Tensor, weight_quant_params: dict, scale_quant_params: Union[dict, None] = None,
-                 zero_quant_params: Union[dict, None] = None) -> None:
+                 zero_quant_params: Union[dict, None] = None, solver_dtype: torch.dtype = torch.float32) -> None:
         self.in_features, self.out_features = W.t().shape
-        W_q, meta = Quantizer.quantize(W, device=self.device, compute_dtype=self.compute_dtype, **weight_quant_params)
+        W_q, meta = Quantizer.quantize(W, device=self.device, compute_dtype=self.compute_dtype, solver_dtype=solver_dtype, **weight_quant_params)
         meta.update({"quant_scale": False, "quant_zero": False})
         self.W_q, self.meta = W_q, meta
         self.axis = weight_quant_params.get("axis")

@@ -629,12 +629,23 @@ def forward(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None, fused=
     return _compose(x, W, bias, out, N, K, library_gemm)
 
 
+def _solver_dt(solver_dtype) -> int:
+    """the solver precisions the kernels have: float32 (the reference's CPU solver, the default) and float16 (its GPU solver)"""
+    if solver_dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"hqq_amd: solver_dtype must be torch.float32 or torch.float16, got {solver_dtype}")
+    return _DT[solver_dtype]
+
+
 def quantize(W: Tensor, nbits=4, group_size: int = 64, round_zero: bool = False, optimize: bool = True,
-             iters: int = 20, beta: float = 10.0, lp_norm: float = 0.7, return_info: bool = False, axis: int = 1):
+             iters: int = 20, beta: float = 10.0, lp_norm: float = 0.7, return_info: bool = False, axis: int = 1,
+             solver_dtype: torch.dtype = torch.float32):
     """Quantizer.quantize(channel_wise=True, bitpack=True) with optimize_weights_proximal_legacy, fused with packing.
     axis=1: groups are runs of `group_size` consecutive elements — returns (W_q packed [packed_rows(R), gs], scale [R,1] f32 (already
     inverted), zero [R,1] f32), R = numel / gs.  axis=0: W is viewed as [gs, C], C = numel / gs, every column a group — returns
-    (W_q packed [packed_rows(gs), C], scale [1,C], zero [1,C]).  [+ info int32[2] on device with return_info]"""
+    (W_q packed [packed_rows(gs), C], scale [1,C], zero [1,C]).  [+ info int32[2] on device with return_info]
+    solver_dtype=torch.float16 runs the reference's GPU solver (fp16 arithmetic, optimize.py:231) instead of its CPU float32 one;
+    scale and zero are then fp16, as the reference returns them."""
+    sdt = _solver_dt(solver_dtype)
     _dev(W)
     if axis not in (0, 1):
         raise ValueError("axis should be either 0 or 1")
@@ -652,13 +663,13 @@ def quantize(W: Tensor, nbits=4, group_size: int = 64, round_zero: bool = False,
     if axis == 1:
         prow = packed_rows(pack_bits, R)
         W_q = torch.empty((prow, group_size), dtype=torch.int32 if pack_bits == 3 else torch.uint8, device=dev)
-        scale = torch.empty((R, 1), dtype=torch.float32, device=dev)
-        zero = torch.empty((R, 1), dtype=torch.float32, device=dev)
+        scale = torch.empty((R, 1), dtype=solver_dtype, device=dev)
+        zero = torch.empty((R, 1), dtype=solver_dtype, device=dev)
     else:
         prow = packed_rows(pack_bits, group_size)
         W_q = torch.empty((prow, R), dtype=torch.int32 if pack_bits == 3 else torch.uint8, device=dev)
-        scale = torch.empty((1, R), dtype=torch.float32, device=dev)
-        zero = torch.empty((1, R), dtype=torch.float32, device=dev)
+        scale = torch.empty((1, R), dtype=solver_dtype, device=dev)
+        zero = torch.empty((1, R), dtype=solver_dtype, device=dev)
     info = torch.zeros((2,), dtype=torch.int32, device=dev)
     L = _C.lib()
     it = iters if optimize else 0
@@ -666,19 +677,22 @@ def quantize(W: Tensor, nbits=4, group_size: int = 64, round_zero: bool = False,
     if ws_bytes == 0:
         raise ValueError(f"hqq_amd: bad quantize arguments (numel={numel}, group_size={group_size}, iters={it})")
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    fn = L.hqq_hip_quantize if axis == 1 else L.hqq_hip_quantize_axis0
+    fn = L.hqq_hip_quantize_solver if axis == 1 else L.hqq_hip_quantize_axis0_solver
     with torch.cuda.device(dev):
         rc = fn(_p(W), _dt(W.dtype), numel, group_size, max_v, pack_bits, int(bool(round_zero)), int(bool(optimize)),
-                it, float(beta), float(lp_norm), _p(W_q), _p(scale), _p(zero), _p(info), _p(ws), ws_bytes, _stream())
+                it, float(beta), float(lp_norm), sdt, _p(W_q), _p(scale), _p(zero), _p(info), _p(ws), ws_bytes, _stream())
     _C.check(rc, "hqq_hip_quantize" if axis == 1 else "hqq_hip_quantize_axis0")
     if return_info:
         return W_q, scale, zero, info
     return W_q, scale, zero
 
 
-def optimize(W: Tensor, scale: Tensor, zero: Tensor, max_v: int, axis: int = 1, iters: int = 20, beta: float = 10.0, lp_norm: float = 0.7):
+def optimize(W: Tensor, scale: Tensor, zero: Tensor, max_v: int, axis: int = 1, iters: int = 20, beta: float = 10.0, lp_norm: float = 0.7,
+             return_info: bool = False, solver_dtype: torch.dtype = torch.float32):
     """optimize_weights_proximal_legacy on its own (optimize.py:208-255): W is the grouped 2-D view ([groups, gs] for axis=1, [gs, groups] for
-    axis=0), scale / zero float32 with one value per group.  Returns (levels uint8 in W's shape, zero float32 in zero's shape)."""
+    axis=0), scale / zero float32 with one value per group.  Returns (levels uint8 in W's shape, zero float32 in zero's shape)
+    [+ info int32[2] on device with return_info].  solver_dtype=torch.float16: the reference's GPU solver; zero is then fp16."""
+    sdt = _solver_dt(solver_dtype)
     _dev(W, scale, zero)
     if W.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         W = W.float()
@@ -690,15 +704,17 @@ def optimize(W: Tensor, scale: Tensor, zero: Tensor, max_v: int, axis: int = 1, 
         raise ValueError(f"hqq_amd: scale / zero must hold one value per group ({R}), got {sc.numel()} / {ze.numel()}")
     dev = W.device
     levels = torch.empty(W.shape, dtype=torch.uint8, device=dev)
-    zero_out = torch.empty(zero.shape, dtype=torch.float32, device=dev)
+    zero_out = torch.empty(zero.shape, dtype=solver_dtype, device=dev)
     info = torch.zeros((2,), dtype=torch.int32, device=dev)
     L = _C.lib()
     ws_bytes = int(L.hqq_hip_quantize_workspace_bytes(W.numel(), gs, int(iters))) + 4 * R
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = L.hqq_hip_optimize(_p(W), _dt(W.dtype), W.numel(), gs, int(axis), int(max_v), _p(sc), _p(ze), int(iters), float(beta), float(lp_norm),
-                                _p(levels), _p(zero_out), _p(info), _p(ws), ws_bytes, _stream())
+        rc = L.hqq_hip_optimize_solver(_p(W), _dt(W.dtype), W.numel(), gs, int(axis), int(max_v), _p(sc), _p(ze), int(iters), float(beta),
+                                       float(lp_norm), sdt, _p(levels), _p(zero_out), _p(info), _p(ws), ws_bytes, _stream())
     _C.check(rc, "hqq_hip_optimize")
+    if return_info:
+        return levels, zero_out, info
     return levels, zero_out
 
 

@@ -25,9 +25,11 @@ def _block_index(name: str) -> int:
 
 
 def quantize_model(model: nn.Module, quant_config: Union[dict, Dict[str, Optional[dict]]], compute_dtype: torch.dtype = torch.float16,
-                   device: Union[str, Sequence[str]] = "cuda", linear_tags: Iterable[str] = LLAMA_LINEAR_TAGS, verbose: bool = False) -> nn.Module:
+                   device: Union[str, Sequence[str]] = "cuda", linear_tags: Iterable[str] = LLAMA_LINEAR_TAGS, verbose: bool = False,
+                   solver_dtype: torch.dtype = torch.float32) -> nn.Module:
     """quant_config: one BaseQuantizeConfig dict for every tag, or {tag: config-or-None} (None = leave that linear alone).
-    device: one device, or a list — decoder block i goes to devices[i % len(devices)]."""
+    device: one device, or a list — decoder block i goes to devices[i % len(devices)].  solver_dtype: HQQLinear's (torch.float16: the
+    reference's GPU solver)."""
     tags = list(linear_tags)
     per_tag = quant_config if (isinstance(quant_config, dict) and "weight_quant_params" not in quant_config) else {t: quant_config for t in tags}
     devices = [device] if isinstance(device, (str, torch.device)) else list(device)
@@ -42,7 +44,7 @@ def quantize_model(model: nn.Module, quant_config: Union[dict, Dict[str, Optiona
         parent = model.get_submodule(parent_name) if parent_name else model
         lin = getattr(parent, child)
         dev = devices[_block_index(name) % len(devices)]
-        q = HQQLinear(lin, per_tag[tag], compute_dtype=compute_dtype, device=dev, del_orig=True)
+        q = HQQLinear(lin, per_tag[tag], compute_dtype=compute_dtype, device=dev, del_orig=True, solver_dtype=solver_dtype)
         q.name = name
         setattr(parent, child, q)
         if verbose:

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HQQ_HIP_ABI_VERSION 8
+#define HQQ_HIP_ABI_VERSION 9
 
 /* element types of activations / meta / outputs ("compute_dtype" in the reference) */
 enum { HQQ_F32 = 0, HQQ_F16 = 1, HQQ_BF16 = 2, HQQ_U8 = 3 };
@@ -294,13 +294,27 @@ int hqq_hip_forward(int nbits, const void* x, const void* Wq, const void* scale,
  *   scale_out  [N*K/gs] float32 = 1/scale (quantize.py:154) ; zero_out [N*K/gs] float32
  *   info_out   int32[2] on the device: {iterations run, stop iteration index}  (may be NULL)
  * The solver runs in float32 — the reference's CPU precision (optimize.py:231); packed levels, zero and scale equal the
- * reference's CPU path bit for bit (the reference's GPU path solves in fp16 and differs from its own CPU result).
+ * reference's CPU path bit for bit.  The reference's GPU path solves in fp16 and differs from its own CPU
+ * result: hqq_hip_quantize_solver (ABI 9) below computes either.
  * ------------------------------------------------------------------------------------------- */
 size_t hqq_hip_quantize_workspace_bytes(int64_t numel, int64_t group_size, int iters);
 int hqq_hip_quantize(const void* W, int w_dtype, int64_t numel, int64_t group_size, int max_v, int pack_bits,
                      int round_zero, int optimize, int iters, float beta, float lp_norm,
                      void* Wq_out, float* scale_out, float* zero_out, int32_t* info_out,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* hqq_hip_quantize with the solver's precision chosen per call (ABI 9): solver_dtype HQQ_F32 is hqq_hip_quantize itself, bit for bit;
+ * HQQ_F16 is the reference's GPU solver (optimize.py:231: fp16 when the device is "cuda"): after the float32 min/max initialisation W,
+ * scale and zero are cast to fp16 and every op of the loop rounds once to fp16, the error means are compared as fp16, the final
+ * levels use the float32 W with the fp16 scale / zero (optimize.py:254), and scale_out / zero_out are fp16 (quantize.py:154 computes
+ * 1/scale in fp16).  Equal to the reference's fp16 solver as PyTorch's CPU kernels run it (their float32 summation order for the means);
+ * torch-ROCm's own reduction order is not restated.  A group whose W * scale overflows fp16 gets a NaN zero, and its NaN error stops
+ * the whole layer after one iteration, as in the reference; its levels are then not defined (the reference's cast of NaN to uint8
+ * is platform-defined).  Any other solver_dtype: HQQ_ERR_DTYPE (checked before anything touches the device).  Same workspace size. */
+int hqq_hip_quantize_solver(const void* W, int w_dtype, int64_t numel, int64_t group_size, int max_v, int pack_bits,
+                            int round_zero, int optimize, int iters, float beta, float lp_norm, int solver_dtype,
+                            void* Wq_out, void* scale_out, void* zero_out, int32_t* info_out,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same with axis=0 (quantize.py:104-116): W is viewed as [group_size, numel/group_size] and every COLUMN is a group (min/max,
  * scale, zero and the solver's mean run down the rows).  Wq_out: the packed [packed_rows(group_size), numel/group_size] tensor
@@ -310,6 +324,11 @@ int hqq_hip_quantize_axis0(const void* W, int w_dtype, int64_t numel, int64_t gr
                            int round_zero, int optimize, int iters, float beta, float lp_norm,
                            void* Wq_out, float* scale_out, float* zero_out, int32_t* info_out,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* hqq_hip_quantize_axis0 with solver_dtype HQQ_F32 / HQQ_F16, as hqq_hip_quantize_solver (ABI 9) */
+int hqq_hip_quantize_axis0_solver(const void* W, int w_dtype, int64_t numel, int64_t group_size, int max_v, int pack_bits,
+                                  int round_zero, int optimize, int iters, float beta, float lp_norm, int solver_dtype,
+                                  void* Wq_out, void* scale_out, void* zero_out, int32_t* info_out,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* optimize_weights_proximal_legacy called on its own (optimize.py:208-255; `Quantizer.optimize_weights`): the same solver, started from the
  * CALLER's scale and zero instead of the group's min / max.  W viewed as [numel / group_size, group_size] (axis 1: a group per row) or
@@ -321,6 +340,11 @@ int hqq_hip_quantize_axis0(const void* W, int w_dtype, int64_t numel, int64_t gr
 int hqq_hip_optimize(const void* W, int w_dtype, int64_t numel, int64_t group_size, int axis, int max_v, const float* scale_in, const float* zero_in,
                      int iters, float beta, float lp_norm, void* levels_out, float* zero_out, int32_t* info_out,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* hqq_hip_optimize with solver_dtype HQQ_F32 / HQQ_F16, as hqq_hip_quantize_solver (ABI 9): scale_in / zero_in stay float32 (cast to fp16
+ * inside, as optimize.py:232-234 casts them), zero_out is fp16 with HQQ_F16.  Same workspace size as hqq_hip_optimize. */
+int hqq_hip_optimize_solver(const void* W, int w_dtype, int64_t numel, int64_t group_size, int axis, int max_v, const float* scale_in,
+                            const float* zero_in, int iters, float beta, float lp_norm, int solver_dtype, void* levels_out, void* zero_out,
+                            int32_t* info_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* channel_wise=False (quantize.py:114-116, 146): one scale and one zero for the WHOLE [rows, cols] tensor from its min and max, no
  * solver; the levels are packed in the tensor's own shape — Wq_out [packed_rows(rows), cols].  scale_out / zero_out: one float32 each
