@@ -28,15 +28,16 @@ class HQQLinearHIP(nn.Module):
         m = hqq_layer.meta
         self.out_features, self.in_features = (int(v) for v in m["shape"])
         self.nbits = Quantizer._packing_bits[m["packing"]]
-        self.group_size = int(m["group_size"])
-        self.axis = 1
+        self.axis = int(m["axis"])
+        # (axis 0: group_size None is one group per column of W, i.e. out_features weights per (scale, zero))
+        self.group_size = int(m["group_size"]) if m["group_size"] else self.out_features
         self.compute_dtype = hqq_layer.compute_dtype
         self.device = hqq_layer.device
         self.name = getattr(hqq_layer, "name", None)
         W_q = hqq_layer.W_q.data
         if m["view_as_float"]:
             W_q = W_q.view(m["unpack_view_dtype"])
-        self.w3s = bool(self.nbits == 3 and ops.w3s_covers(self.out_features, self.in_features, self.group_size) and W_q.is_cuda)
+        self.w3s = bool(self.axis == 1 and self.nbits == 3 and ops.w3s_covers(self.out_features, self.in_features, self.group_size) and W_q.is_cuda)
         if self.w3s:
             W_q = ops.w3s_pack(W_q.contiguous(), self.out_features, self.in_features)
         self.W_q = nn.Parameter(W_q.contiguous(), requires_grad=False)
@@ -47,7 +48,11 @@ class HQQLinearHIP(nn.Module):
 
     def refresh_opts(self) -> None:
         """May the exact weight rebuild use its three-op form on this layer's (zero, scale)?  (include/hqq_hip.h, hqq_hip_meta_check.)
-        Checked when the layer is built and again whenever a state dict is loaded into it; call it after editing `scale` / `zero` in place."""
+        Checked when the layer is built and again whenever a state dict is loaded into it; call it after editing `scale` / `zero` in place.
+        (Axis-0 layers: no option applies — their kernel always rebuilds the exact weights in the four-op form.)"""
+        if self.axis == 0:
+            self.opts = 0
+            return
         if self.w3s:
             self.opts = ops.OPT_W3S | (ops.OPT_META_SCALABLE if (self.compute_dtype == torch.float16 and self.scale.is_cuda and
                                                                   ops.w3s_meta_scalable(self.scale, self.zero, self.out_features, self.in_features)) else 0)
@@ -77,6 +82,12 @@ class HQQLinearHIP(nn.Module):
         m = getattr(hqq_layer, "meta", None)
         if m is None or not m.get("packing"):
             return False
+        if m["axis"] == 0:   # the axis-0 decode kernel (hqq_hip_gemv_axis0) at one row: byte containers, channel-wise meta
+            N, K = (int(v) for v in m["shape"])
+            gs = int(m["group_size"]) if m["group_size"] else N
+            return (m["packing"] in ("8bit_u8", "4bit_u8", "2bit_u8", "1bit_u8") and gs > 0 and N % gs == 0 and m["scale"].numel() == N * K // gs
+                    and m["scale"].dtype == hqq_layer.compute_dtype and ops.decode_axis0_covers(hqq_layer.compute_dtype, 1, N, K, gs, Quantizer._packing_bits[m["packing"]])
+                    and not m.get("quant_scale") and not m.get("quant_zero") and hqq_layer.W_q.is_cuda)
         gs = m["group_size"]
         N, K = m["shape"]
         dt = hqq_layer.compute_dtype
@@ -91,7 +102,7 @@ class HQQLinearHIP(nn.Module):
 
     def dequantize(self) -> Tensor:
         W_q = ops.w3s_unpack(self.W_q.data, self.out_features, self.in_features) if self.w3s else self.W_q
-        return ops.dequantize(W_q, self.scale, self.zero, self.out_features, self.in_features, self.group_size, self.nbits, 1)
+        return ops.dequantize(W_q, self.scale, self.zero, self.out_features, self.in_features, self.group_size, self.nbits, self.axis)
 
     @torch.compiler.disable   # (a tracing compiler has nothing to see in a ctypes call into libhqq_hip.so: HF's static-cache generate() auto-compiles the model's forward)
     def forward(self, x: Tensor) -> Tensor:
@@ -99,9 +110,10 @@ class HQQLinearHIP(nn.Module):
             x = x.to(self.compute_dtype)
         rows = x.numel() // x.shape[-1]
         # every number of rows through ops.forward: decode kernels, skinny GEMM, pipelined GEMM, and beyond them (long prompts, shapes the fused
-        # kernels do not cover) the dequantise kernel + the in-tree dense GEMM; a 3-bit layer in the stream layout says so in its option bits
+        # kernels do not cover) the dequantise kernel + the in-tree dense GEMM; a 3-bit layer in the stream layout says so in its option bits.
+        # Axis-0 layers: the axis-0 decode kernel up to 16 rows, beyond it the route HQQLinear takes (dequantise kernel + torch.matmul)
         return ops.forward(x, self.W_q, self.scale, self.zero, self.bias, self.out_features, self.in_features, self.group_size, self.nbits,
-                           opts=ops.layer_opts(self.opts))
+                           opts=ops.layer_opts(self.opts), axis=self.axis)
 
 
 def patch_hqq_to_hip(layer, patch_params=None):
@@ -173,6 +185,8 @@ def group_projections(parent: nn.Module, names) -> bool:
     launch per distinct input.  Returns False (and changes nothing) when the layers cannot be grouped."""
     layers = [getattr(parent, n, None) for n in names]
     if not all(isinstance(L, HQQLinearHIP) for L in layers) or not 2 <= len(layers) <= ops.GEMV_MAX_GROUP:
+        return False
+    if any(L.axis != 1 for L in layers):   # the grouped kernels read axis-1 meta (one constant pair per group of a row)
         return False
     L0 = layers[0]
     if any((L.in_features, L.nbits, L.group_size, L.compute_dtype, L.w3s) != (L0.in_features, L0.nbits, L0.group_size, torch.float16, L0.w3s) for L in layers):

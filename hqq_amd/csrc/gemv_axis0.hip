@@ -1,0 +1,315 @@
+// gemv_axis0.hip — the decode kernel for layers quantised along axis 0 (hqq_hip_gemv_axis0): fused unpack -> dequantize -> GEMV, gfx950.
+//
+// Replaces, for axis=0 layers, the chain HQQLinear.forward runs for them (hqq/core/quantize.py:183-199, :880-898): the dequantise kernel writes
+// the whole fp16 weight, torch.matmul reads it back.  One pass over the packed bytes and the meta instead.
+//
+// Layout.  axis 0 views the level matrix as [gs, C], C = N K / gs, one (scale, zero) per COLUMN.  For the byte containers the packed bytes
+// of that view are the axis-1 packed bytes of the same [N, K] matrix: byte (p, k), p < N / per, holds W[p + s N / per, k] in slab s.  With
+// gs | N and S = N / gs, weight W[n, k] uses meta column (n mod S) K + k: the meta is an [S, K] matrix, output rows n = r (mod S) share meta
+// row r — the "class" r — and so do the `per` rows of one packed byte (N / per is a multiple of S).
+//
+// Work.  A wave owns (class r, a block of up to 16 * NBITS packed rows of the class = 128 output rows, a K-split of whole 64-k units).  Per
+// unit a lane fetches 16 k of its (scale, zero) row and of x ONCE and rebuilds the weights of every packed row of its block against them:
+// each meta element leaves HBM once per call (the blocks of one class are neighbouring waves when the class has more than 128 rows).
+// Contraction: mfma_f32_16x16x32_{f16,bf16} with A = 16 packed rows of the class (lane l: row l & 15, k octet l >> 4) and B = x (column
+// m = l & 15, up to 16 activation rows, zero padded), one MFMA pair per unit and slab.  A lane group's 16 k are its own 16 consecutive
+// bytes of the row (one 16-byte load), kept in the byte-pair order of biased_levels (decode_common.h) in A, B and the meta alike.
+// Weights: round(round(q - z) * s) in the compute dtype, the two roundings of Quantizer.dequantize — bit-identical to hqq_hip_dequantize.
+// Split-K: every wave parks its fp32 partial sums in the caller's workspace (past the counter head, which stays untouched); a second
+// launch sums the splits in split order, rounds once and adds the bias (one more rounding): deterministic, shape-only split rule.
+#include "decode_common.h"
+
+namespace hqq {
+
+constexpr int A0_WAVES = 4;             // waves per workgroup (independent work items, no LDS)
+constexpr int A0_KU = 64;               // k per unit: 16 per lane group
+constexpr int A0_TARGET_WAVES = 2048;   // ~8 waves per CU before K is split further
+constexpr int A0_MAX_SPLITS = 64;
+
+struct A0Plan {
+  int S, P, nblocks, splits, upc, units;
+  int64_t items;
+};
+
+static A0Plan a0_plan(int nbits, int64_t N, int64_t K, int64_t gs) {
+  A0Plan p;
+  const int per = 8 / nbits;
+  p.S = static_cast<int>(N / gs);
+  p.P = static_cast<int>(gs / per);
+  const int rows_per_block = 16 * nbits;   // NBITS tiles of 16 packed rows: 128 output rows whatever the width
+  p.nblocks = (p.P + rows_per_block - 1) / rows_per_block;
+  p.units = static_cast<int>(K / A0_KU);
+  const int64_t base = static_cast<int64_t>(p.S) * p.nblocks;
+  int64_t sp = (A0_TARGET_WAVES + base - 1) / base;
+  if (sp > A0_MAX_SPLITS) sp = A0_MAX_SPLITS;
+  if (sp > p.units) sp = p.units;
+  if (sp < 1) sp = 1;
+  p.upc = static_cast<int>((p.units + sp - 1) / sp);
+  p.splits = (p.units + p.upc - 1) / p.upc;
+  p.items = base * p.splits;
+  return p;
+}
+
+static __device__ __forceinline__ u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p); }
+static __device__ __forceinline__ u32x4 ld16_nt(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
+
+// fp16: the 16 weights of slab SL of one packed 16-byte vector, (q - z) then * s per element, as two MFMA A operands
+template <int NBITS, int SL>
+__device__ __forceinline__ void rebuild_f16(const u32x4& w, const half2_t (&zz)[8], const half2_t (&ss)[8], h8_t& a0, h8_t& a1, uint32_t magic) {
+  constexpr int sh = NBITS * (8 / NBITS - 1 - SL);
+  constexpr float inv = 1.0f / static_cast<float>(1 << sh);
+  const half2_t k1 = {static_cast<half_t>(inv), static_cast<half_t>(inv)};
+  const half2_t k2 = {static_cast<half_t>(-1024.0f * inv), static_cast<half_t>(-1024.0f * inv)};
+  half2_t q[8];
+  uint32_t o[8];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    q[2 * d] = biased_levels<NBITS, SL>(w[d], magic);            // bytes (4d+0, 4d+2)
+    q[2 * d + 1] = biased_levels<NBITS, SL>(w[d] >> 8, magic);   // bytes (4d+1, 4d+3)
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) q[i] = __builtin_elementwise_fma(q[i], k1, k2);   // exact integer level
+#pragma unroll
+  for (int i = 0; i < 8; ++i) q[i] = q[i] - zz[i];                               // rounding 1
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o[i] = __builtin_bit_cast(uint32_t, q[i] * ss[i]);   // rounding 2
+  a0 = __builtin_bit_cast(h8_t, u32x4{o[0], o[1], o[2], o[3]});
+  a1 = __builtin_bit_cast(h8_t, u32x4{o[4], o[5], o[6], o[7]});
+}
+
+// bf16: the same through fp32 (gfx950 has no packed bf16 arithmetic): q - z in fp32, rounded to bf16, times s (exact in fp32), rounded again
+template <int NBITS, int SL>
+__device__ __forceinline__ void rebuild_bf16(const u32x4& w, const uint32_t (&zz)[8], const uint32_t (&ss)[8], bf16x8_t& a0, bf16x8_t& a1) {
+  constexpr int sh = NBITS * (8 / NBITS - 1 - SL);
+  constexpr uint32_t mask = (NBITS == 8) ? 0xFFu : ((1u << NBITS) - 1u);
+  uint32_t o[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int d = i >> 1, b0 = i & 1;                  // bytes (4d + b0, 4d + b0 + 2)
+    const float q0 = static_cast<float>((w[d] >> (8 * b0 + sh)) & mask);
+    const float q1 = static_cast<float>((w[d] >> (8 * b0 + 16 + sh)) & mask);
+    const f32x2_t dq = {q0 - __uint_as_float(zz[i] << 16), q1 - __uint_as_float(zz[i] & 0xFFFF0000u)};
+    const bf16x2_t dr = __builtin_convertvector(dq, bf16x2_t);                                           // rounding 1
+    const uint32_t du = __builtin_bit_cast(uint32_t, dr);
+    const f32x2_t pw = {__uint_as_float(du << 16) * __uint_as_float(ss[i] << 16),
+                        __uint_as_float(du & 0xFFFF0000u) * __uint_as_float(ss[i] & 0xFFFF0000u)};   // exact: two 8-bit significands
+    o[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pw, bf16x2_t));                          // rounding 2
+  }
+  a0 = __builtin_bit_cast(bf16x8_t, u32x4{o[0], o[1], o[2], o[3]});
+  a1 = __builtin_bit_cast(bf16x8_t, u32x4{o[4], o[5], o[6], o[7]});
+}
+
+// every slab of one packed 16-byte vector against the same meta and x: rebuild, then one MFMA pair per slab
+template <int NBITS, int SL>
+struct A0Slabs {
+  static constexpr int PER = 8 / NBITS;
+  static __device__ __forceinline__ void f16(const u32x4& w, const half2_t (&zz)[8], const half2_t (&ss)[8], const h8_t& b0, const h8_t& b1,
+                                             f32x4 (&acc)[PER], uint32_t magic) {
+    h8_t a0, a1;
+    rebuild_f16<NBITS, SL>(w, zz, ss, a0, a1, magic);
+    acc[SL] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b0, acc[SL], 0, 0, 0);
+    acc[SL] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b1, acc[SL], 0, 0, 0);
+    if constexpr (SL + 1 < PER) A0Slabs<NBITS, SL + 1>::f16(w, zz, ss, b0, b1, acc, magic);
+  }
+  static __device__ __forceinline__ void bf16(const u32x4& w, const uint32_t (&zz)[8], const uint32_t (&ss)[8], const bf16x8_t& b0, const bf16x8_t& b1,
+                                              f32x4 (&acc)[PER]) {
+    bf16x8_t a0, a1;
+    rebuild_bf16<NBITS, SL>(w, zz, ss, a0, a1);
+    acc[SL] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[SL], 0, 0, 0);
+    acc[SL] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[SL], 0, 0, 0);
+    if constexpr (SL + 1 < PER) A0Slabs<NBITS, SL + 1>::bf16(w, zz, ss, b0, b1, acc);
+  }
+};
+
+template <int NBITS, bool BF16>
+__global__ __launch_bounds__(A0_WAVES * 64) void gemv_axis0_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ Wq,
+                                                                  const uint16_t* __restrict__ scale, const uint16_t* __restrict__ zero,
+                                                                  float* __restrict__ part, int M, int N, int K, int S, int P, int nblocks,
+                                                                  int upc, int units, int64_t items) {
+  constexpr int PER = 8 / NBITS;
+  constexpr int TB = NBITS;   // tiles of 16 packed rows per wave: TB * 16 * PER = 128 output rows
+  const int lane = threadIdx.x & 63;
+  const int64_t item = static_cast<int64_t>(blockIdx.x) * A0_WAVES + (threadIdx.x >> 6);
+  if (item >= items) return;
+  const int b = static_cast<int>(item % nblocks);
+  const int64_t rest = item / nblocks;
+  const int r = static_cast<int>(rest % S);
+  const int split = static_cast<int>(rest / S);
+  const int col = lane & 15, g = lane >> 4;
+  const int t0 = b * 16 * TB;
+  const int ntiles = (P - t0 + 15) / 16 < TB ? (P - t0 + 15) / 16 : TB;
+  const uint8_t* wrow[TB];
+#pragma unroll
+  for (int tl = 0; tl < TB; ++tl) {
+    int t = t0 + 16 * tl + col;
+    t = t < P ? t : P - 1;   // rows past the class (P not a multiple of 16): a valid address, results never stored
+    wrow[tl] = Wq + static_cast<int64_t>(r + static_cast<int64_t>(t) * S) * K + 16 * g;
+  }
+  const uint16_t* srow = scale + static_cast<int64_t>(r) * K + 16 * g;
+  const uint16_t* zrow = zero + static_cast<int64_t>(r) * K + 16 * g;
+  const bool mv = col < M;
+  const uint16_t* xrow = x + static_cast<int64_t>(mv ? col : 0) * K + 16 * g;
+  const uint32_t magic = 0x64006400u;
+  f32x4 acc[TB][PER];
+#pragma unroll
+  for (int tl = 0; tl < TB; ++tl)
+#pragma unroll
+    for (int j = 0; j < PER; ++j) acc[tl][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int u0 = split * upc;
+  const int u1 = u0 + upc < units ? u0 + upc : units;
+  for (int u = u0; u < u1; ++u) {
+    const int k = u * A0_KU;
+    u32x4 w[TB];
+#pragma unroll
+    for (int tl = 0; tl < TB; ++tl) w[tl] = tl < ntiles ? ld16_nt(wrow[tl] + k) : u32x4{0u, 0u, 0u, 0u};
+    const u32x4 s0 = permute_x8(ld16(srow + k)), s1 = permute_x8(ld16(srow + k + 8));
+    const u32x4 z0 = permute_x8(ld16(zrow + k)), z1 = permute_x8(ld16(zrow + k + 8));
+    u32x4 x0 = ld16(xrow + k), x1 = ld16(xrow + k + 8);
+    if (!mv) { x0 = u32x4{0u, 0u, 0u, 0u}; x1 = x0; }
+    x0 = permute_x8(x0);
+    x1 = permute_x8(x1);
+    if constexpr (!BF16) {
+      half2_t zz[8], ss[8];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { zz[i] = as_h2(z0[i]); zz[4 + i] = as_h2(z1[i]); ss[i] = as_h2(s0[i]); ss[4 + i] = as_h2(s1[i]); }
+      const h8_t b0 = __builtin_bit_cast(h8_t, x0), b1 = __builtin_bit_cast(h8_t, x1);
+#pragma unroll
+      for (int tl = 0; tl < TB; ++tl)
+        if (tl < ntiles) A0Slabs<NBITS, 0>::f16(w[tl], zz, ss, b0, b1, acc[tl], magic);
+    } else {
+      uint32_t zz[8], ss[8];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { zz[i] = z0[i]; zz[4 + i] = z1[i]; ss[i] = s0[i]; ss[4 + i] = s1[i]; }
+      const bf16x8_t b0 = __builtin_bit_cast(bf16x8_t, x0), b1 = __builtin_bit_cast(bf16x8_t, x1);
+#pragma unroll
+      for (int tl = 0; tl < TB; ++tl)
+        if (tl < ntiles) A0Slabs<NBITS, 0>::bf16(w[tl], zz, ss, b0, b1, acc[tl]);
+    }
+  }
+  // D[i][m]: lane l holds m = l & 15 and packed rows t0 + 16 tl + 4 (l >> 4) + reg; output row n = r + (t + slab P) S
+  if (!mv) return;
+  float* out = part + (static_cast<int64_t>(split) * M + col) * N;
+#pragma unroll
+  for (int tl = 0; tl < TB; ++tl) {
+    if (tl >= ntiles) break;
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) {
+      const int t = t0 + 16 * tl + 4 * g + rg;
+      if (t < P) {
+#pragma unroll
+        for (int j = 0; j < PER; ++j) out[r + static_cast<int64_t>(t + j * P) * S] = acc[tl][j][rg];
+      }
+    }
+  }
+}
+
+// y[m, n] = round(sum over splits, in split order) (+ bias: `out += bias` on the rounded result, quantize.py:896-897)
+template <bool BF16>
+__global__ __launch_bounds__(256) void gemv_axis0_reduce_kernel(const float* __restrict__ part, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
+                                                                int M, int N, int splits) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t MN = static_cast<int64_t>(M) * N;
+  if (i >= MN) return;
+  // the loads of eight splits are issued together (independent), then added in split order: a thread is one chain of dependent adds, not of
+  // dependent round trips to memory
+  float s = 0.f;
+  int c = 0;
+  for (; c + 8 <= splits; c += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = part[(c + j) * MN + i];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += v[j];
+  }
+  for (; c < splits; ++c) s += part[c * MN + i];
+  const int n = static_cast<int>(i % N);
+  if constexpr (BF16) {
+    uint16_t o = f32_to_bf16(s);
+    if (bias) o = f32_to_bf16(bf16_to_f32(o) + bf16_to_f32(bias[n]));
+    y[i] = o;
+  } else {
+    half_t o = static_cast<half_t>(s);
+    if (bias) o = o + __builtin_bit_cast(half_t, bias[n]);
+    y[i] = __builtin_bit_cast(uint16_t, o);
+  }
+}
+
+// what the kernel covers, checked before anything is launched: 0, or an HQQ_ERR_* with the message set
+static int a0_validate(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
+  if (opts & ~HQQ_OPT_ALL) { set_error("hqq_hip_gemv_axis0: unknown option bits 0x%x", opts & ~HQQ_OPT_ALL); return HQQ_ERR_SHAPE; }
+  if (nbits != 8 && nbits != 4 && nbits != 3 && nbits != 2 && nbits != 1) { set_error("hqq_hip_gemv_axis0: nbits=%d", nbits); return HQQ_ERR_NBITS; }
+  if (nbits == 3) { set_error("hqq_hip_gemv_axis0: 3-bit containers are not covered"); return HQQ_ERR_UNSUPPORTED; }
+  if (dtype == HQQ_F32) { set_error("hqq_hip_gemv_axis0: fp32 is not covered (fp16 / bf16)"); return HQQ_ERR_UNSUPPORTED; }
+  if (dtype != HQQ_F16 && dtype != HQQ_BF16) { set_error("hqq_hip_gemv_axis0: dtype %d", dtype); return HQQ_ERR_DTYPE; }
+  if (dtype == HQQ_BF16 && nbits != 4 && nbits != 2) { set_error("hqq_hip_gemv_axis0: bf16 with nbits=%d is not covered (4 / 2)", nbits); return HQQ_ERR_UNSUPPORTED; }
+  if (M < 1 || N < 1 || K < 1 || group_size < 1) { set_error("hqq_hip_gemv_axis0: bad M/N/K/group_size"); return HQQ_ERR_SHAPE; }
+  if (M > HQQ_GEMV_MAX_M) { set_error("hqq_hip_gemv_axis0: M=%lld is not covered (at most %d rows)", (long long)M, HQQ_GEMV_MAX_M); return HQQ_ERR_UNSUPPORTED; }
+  if (group_size % 16 || N % group_size || K % A0_KU) {
+    set_error("hqq_hip_gemv_axis0: not covered: needs group_size %% 16 == 0, N %% group_size == 0, K %% %d == 0 (N=%lld K=%lld gs=%lld)", A0_KU,
+              (long long)N, (long long)K, (long long)group_size);
+    return HQQ_ERR_UNSUPPORTED;
+  }
+  // (N / per) * K packed bytes and N K / gs meta elements per layer, M N fp32 partial sums per split: 32-bit offsets stay in range
+  if (N > INT32_MAX || K > INT32_MAX || (N / (8 / nbits)) * K > static_cast<int64_t>(UINT32_MAX) || (N / group_size) * K > INT32_MAX ||
+      M * N * A0_MAX_SPLITS > INT32_MAX) {
+    set_error("hqq_hip_gemv_axis0: size overflow");
+    return HQQ_ERR_SHAPE;
+  }
+  return 0;
+}
+
+}  // namespace hqq
+
+using namespace hqq;
+
+extern "C" size_t hqq_hip_gemv_axis0_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype) {
+  if (a0_validate(nbits, M, N, K, group_size, dtype, 0)) return 0;
+  const A0Plan p = a0_plan(nbits, N, K, group_size);
+  return WS_COUNTER_BYTES + ((static_cast<size_t>(p.splits) * M * N * sizeof(float) + 15) & ~static_cast<size_t>(15));
+}
+
+extern "C" int hqq_hip_gemv_axis0(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias, void* y,
+                                  int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  clear_stale_error();
+  if (const int rc = a0_validate(nbits, M, N, K, group_size, dtype, opts)) return rc;
+  if (!x || !Wq || !scale || !zero || !y) { set_error("hqq_hip_gemv_axis0: null argument"); return HQQ_ERR_SHAPE; }
+  if (!aligned16(x) || !aligned16(Wq) || !aligned16(scale) || !aligned16(zero)) { set_error("hqq_hip_gemv_axis0: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
+  const size_t need = hqq_hip_gemv_axis0_workspace_bytes(nbits, M, N, K, group_size, dtype);
+  if (!workspace || workspace_bytes < need || !aligned16(workspace)) {
+    set_error("hqq_hip_gemv_axis0: needs %zu bytes of 16-byte aligned workspace (got %zu)", need, workspace_bytes);
+    return HQQ_ERR_WORKSPACE;
+  }
+  const A0Plan p = a0_plan(nbits, N, K, group_size);
+  float* part = reinterpret_cast<float*>(static_cast<uint8_t*>(workspace) + WS_COUNTER_BYTES);
+  hipStream_t st = as_stream(stream);
+  const int grid = static_cast<int>((p.items + A0_WAVES - 1) / A0_WAVES);
+  const auto* xs = static_cast<const uint16_t*>(x);
+  const auto* ws = static_cast<const uint8_t*>(Wq);
+  const auto* ss = static_cast<const uint16_t*>(scale);
+  const auto* zs = static_cast<const uint16_t*>(zero);
+  const int Mi = static_cast<int>(M), Ni = static_cast<int>(N), Ki = static_cast<int>(K);
+#define HQQ_A0_LAUNCH(NB, BF)                                                                                                            \
+  hipLaunchKernelGGL((gemv_axis0_kernel<NB, BF>), dim3(grid), dim3(A0_WAVES * 64), 0, st, xs, ws, ss, zs, part, Mi, Ni, Ki, p.S, p.P, \
+                     p.nblocks, p.upc, p.units, p.items)
+  if (dtype == HQQ_BF16) {
+    if (nbits == 4) HQQ_A0_LAUNCH(4, true); else HQQ_A0_LAUNCH(2, true);
+  } else {
+    switch (nbits) {
+      case 8: HQQ_A0_LAUNCH(8, false); break;
+      case 4: HQQ_A0_LAUNCH(4, false); break;
+      case 2: HQQ_A0_LAUNCH(2, false); break;
+      default: HQQ_A0_LAUNCH(1, false); break;
+    }
+  }
+#undef HQQ_A0_LAUNCH
+  if (const int rc = check_launch("hqq_hip_gemv_axis0")) return rc;
+  const int64_t MN = M * N;
+  const int rgrid = static_cast<int>((MN + 255) / 256);
+  if (dtype == HQQ_BF16)
+    hipLaunchKernelGGL(gemv_axis0_reduce_kernel<true>, dim3(rgrid), dim3(256), 0, st, part, static_cast<const uint16_t*>(bias), static_cast<uint16_t*>(y), Mi, Ni, p.splits);
+  else
+    hipLaunchKernelGGL(gemv_axis0_reduce_kernel<false>, dim3(rgrid), dim3(256), 0, st, part, static_cast<const uint16_t*>(bias), static_cast<uint16_t*>(y), Mi, Ni, p.splits);
+  return check_launch("hqq_hip_gemv_axis0");
+}

@@ -560,6 +560,61 @@ def decode_covers(dtype, M, N, K, group_size, nbits) -> bool:
     return dtype == torch.float16 and (M <= 4 or K % 64 == 0)
 
 
+def decode_axis0_covers(dtype, M, N, K, group_size, nbits) -> bool:
+    """what hqq_hip_gemv_axis0 serves: a layer quantised along axis 0 (group_size None: one group per column, i.e. group_size = N), fp16 at
+    8 / 4 / 2 / 1 bits or bf16 at 4 / 2 bits, group_size % 16 == 0 dividing N, K % 64 == 0, 1 <= M <= GEMV_MAX_M"""
+    gs = N if group_size is None else int(group_size)
+    if not (1 <= M <= GEMV_MAX_M) or N <= 0 or K <= 0 or gs <= 0 or gs % 16 or N % gs or K % 64:
+        return False
+    if dtype == torch.float16:
+        return nbits in (8, 4, 2, 1)
+    return dtype == torch.bfloat16 and nbits in (4, 2)
+
+
+def gemv_axis0(x: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, bias, N: int, K: int, group_size, nbits: int, out: Tensor | None = None,
+               opts=None) -> Tensor:
+    """y = x @ dequantize(W_q, axis=0)^T (+ bias) for x [*, K] of 1..GEMV_MAX_M rows (hqq_hip_gemv_axis0): W_q the reference's axis-0 container,
+    scale / zero its [1, N * K / group_size] meta (any shape, read flat); group_size None = N.  Raises NotImplementedError outside
+    decode_axis0_covers()."""
+    _dev(x, W_q, scale, zero, bias)
+    if x.dtype != scale.dtype or zero.dtype != scale.dtype or (bias is not None and bias.dtype != scale.dtype):
+        raise TypeError("hqq_amd: x / scale / zero / bias must share the compute dtype")
+    if x.shape[-1] != K:
+        raise ValueError(f"hqq_amd: x has {x.shape[-1]} features, layer expects {K}")
+    gs = N if group_size is None else int(group_size)
+    if scale.numel() != (N * K) // gs or zero.numel() != (N * K) // gs:
+        raise ValueError(f"hqq_amd: gemv_axis0 needs {(N * K) // gs} scale / zero values (N * K / group_size), got {scale.numel()} / {zero.numel()}")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    if M > 0:
+        L = _C.lib()
+        with torch.cuda.device(x.device):
+            need = int(L.hqq_hip_gemv_axis0_workspace_bytes(int(nbits), M, int(N), int(K), gs, _dt(x.dtype)))
+            ws = reserve_workspace(x.device, need) if need else None
+            rc = L.hqq_hip_gemv_axis0(int(nbits), _p(x2), _p(W_q.contiguous()), _p(scale.contiguous()), _p(zero.contiguous()), _p(bias), _p(out),
+                                      M, int(N), int(K), gs, _dt(x.dtype), _opts(opts), _p(ws), 0 if ws is None else ws.numel(), _stream())
+        _C.check(rc, "hqq_hip_gemv_axis0")
+    return out.reshape(*x.shape[:-1], N)
+
+
+def _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts) -> Tensor:
+    """axis-0 layers: decode sizes through hqq_hip_gemv_axis0; everything else as HQQLinear has always run them — the HIP dequantise kernel
+    (axis 0) + torch.matmul, then `out += bias` (quantize.py:880-898)"""
+    M = x.numel() // K if K else 0
+    if x.is_cuda and decode_axis0_covers(x.dtype, M, N, K, group_size, nbits):
+        return gemv_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=out, opts=opts)
+    gs = N if group_size is None else int(group_size)
+    W = dequantize(W_q, scale.reshape(-1), zero.reshape(-1), N, K, gs, nbits, 0)
+    y = torch.matmul(x.reshape(-1, K), W.t(), out=None if out is None else out.reshape(-1, N))
+    if bias is not None:
+        y += bias
+    return y.reshape(*x.shape[:-1], N)
+
+
 def gemm_dense(x: Tensor, W: Tensor, bias=None, out: Tensor | None = None) -> Tensor:
     """HQQLinear.matmul on dequantised weights: x [*, K] @ W[N, K].T (+ bias) on the in-tree MFMA GEMM (csrc/gemm_dense.hip), fp16 / bf16"""
     _dev(x, W, bias)
@@ -601,15 +656,21 @@ def _compose(x, W, bias, out, N, K, library: bool) -> Tensor:
     return y.reshape(*x.shape[:-1], N)
 
 
-def forward(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None, fused=None, opts=None, library_gemm: bool = False) -> Tensor:
+def forward(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None, fused=None, opts=None, library_gemm: bool = False, axis: int = 1) -> Tensor:
     """y = x @ dequantize(W_q)^T (+ bias).  M <= 16 (<= 64 where the skinny-GEMM kernel applies): weight-streaming decode kernels;
     larger M: fused MFMA dequant-GEMM to 2560 rows, beyond — and for what the fused kernels do not cover, unless fused=True — the dequantise
     kernel + the in-tree dense MFMA GEMM (library_gemm=True: a library GEMM instead, the bench's comparison; also the residual route for
     K % 64 != 0 or N % 4 != 0).  Same dequantised weights either way.  fused=None also composes the few decode-sized cases the kernels do not cover (3-bit beyond 4 rows,
-    bf16 beyond 4 rows outside the skinny-GEMM kernel, 5..16 rows with K % 64 != 0); fused=True never composes: an uncovered configuration raises."""
+    bf16 beyond 4 rows outside the skinny-GEMM kernel, 5..16 rows with K % 64 != 0); fused=True never composes: an uncovered configuration raises.
+    axis=0: a layer quantised along axis 0 — decode_axis0_covers() shapes through hqq_hip_gemv_axis0, the rest through the dequantise kernel +
+    torch.matmul (`fused` and `library_gemm` do not apply)."""
     M = x.numel() // K if K else 0
     if x.dtype != scale.dtype or zero.dtype != scale.dtype or (bias is not None and bias.dtype != scale.dtype):
         raise TypeError("hqq_amd: x / scale / zero / bias must share the compute dtype")
+    if axis == 0:
+        return _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts)
+    if axis != 1:
+        raise ValueError(f"hqq_amd: axis must be 0 or 1, got {axis}")
     if nbits == 3 and (_opts(opts) & OPT_W3S):
         # the 3-bit stream layout: the 4-bit container's kernels (1..4 rows: row-per-wave GEMV; 5..64: the skinny GEMM); beyond, the reference
         # container is restored on the fly for the dequantise kernel + dense GEMM (long prompts of a patched 3-bit layer)

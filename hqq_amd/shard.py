@@ -27,8 +27,15 @@ def shard_rows(N: int, nbits: int, rank: int, world: int) -> Tensor:
     return torch.cat([base + slot * (N // per) for slot in range(per)])
 
 
-def shard_packed(W_q: Tensor, scale: Tensor, zero: Tensor, bias, N: int, K: int, group_size: int, nbits: int, rank: int, world: int):
-    """-> (W_q_local, scale_local, zero_local, bias_local, N_local): the rank's self-contained packed layer."""
+def _require_axis1(axis: int) -> None:
+    if axis != 1:
+        raise NotImplementedError(f"hqq_amd: column sharding covers layers quantised along axis 1 (got axis={axis}): an axis-0 layer's meta is shared by "
+                                  "output rows n = r (mod N / group_size), so a row block is not a self-contained layer — run it unsharded")
+
+
+def shard_packed(W_q: Tensor, scale: Tensor, zero: Tensor, bias, N: int, K: int, group_size: int, nbits: int, rank: int, world: int, axis: int = 1):
+    """-> (W_q_local, scale_local, zero_local, bias_local, N_local): the rank's self-contained packed layer (axis-1 layers only)."""
+    _require_axis1(axis)
     G = K // group_size
     rows = shard_rows(N, nbits, rank, world).to(scale.device)
     n_loc = N // world
@@ -112,11 +119,12 @@ class ShardedHQQForward:
     """One rank's share of a column-sharded layer.  forward(x) = local fused forward + one all-gather over the process
     group (RCCL on GPUs; any torch.distributed backend works, the CPU tests use gloo with a stand-in local op)."""
 
-    def __init__(self, W_q, scale, zero, bias, N, K, group_size, nbits, group=None, local_forward=None, peer=None, replicate: bool = False):
+    def __init__(self, W_q, scale, zero, bias, N, K, group_size, nbits, group=None, local_forward=None, peer=None, replicate: bool = False, axis: int = 1):
         """peer: (PeerExchange, point) — at one activation row the outputs are then exchanged by that object's kernel (peer-memory stores,
         csrc/exchange.hip) instead of a collective; the returned row is the exchange's buffer, valid until the point is used again.
         replicate: the plan (plan_exchange_groups) found this layer's exchange group too small to shard: the rank keeps the WHOLE layer and
         forward() is the local forward — no slice, no collective, the same result on every rank."""
+        _require_axis1(axis)   # (also for replicate=True: the local forward below reads axis-1 meta)
         import torch.distributed as dist
         self.dist, self.group = dist, group
         self.peer = peer

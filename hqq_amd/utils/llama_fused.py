@@ -55,7 +55,8 @@ def arch_supported(model) -> bool:
 
 def supports(model) -> bool:
     """a LlamaForCausalLM-shaped model of an allow-listed architecture (arch_supported) — model.model.layers[*].self_attn.{q,k,v,o}_proj,
-    .mlp.{gate,up,down}_proj, RMSNorm without bias —, fp16 or bf16, every decoder linear an HQQLinearHIP without bias whose group can share one launch"""
+    .mlp.{gate,up,down}_proj, RMSNorm without bias —, fp16 or bf16, every decoder linear an HQQLinearHIP without bias, quantised along axis 1 (the folded
+    block kernels read axis-1 meta), whose group can share one launch"""
     if not arch_supported(model):
         return False
     try:
@@ -69,7 +70,7 @@ def supports(model) -> bool:
         for blk in layers:
             at, mlp = blk.self_attn, blk.mlp
             lin = [_hip(getattr(at, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
-            if not all(isinstance(L, HQQLinearHIP) and L.bias is None and L.compute_dtype == dt and L.W_q.is_cuda for L in lin):
+            if not all(isinstance(L, HQQLinearHIP) and L.bias is None and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == 1 for L in lin):
                 return False
             if len({(L.nbits, L.group_size, L.w3s) for L in lin[:3]}) != 1 or len({(L.nbits, L.group_size, L.w3s) for L in lin[4:6]}) != 1:
                 return False

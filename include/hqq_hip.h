@@ -286,6 +286,23 @@ int hqq_hip_forward(int nbits, const void* x, const void* Wq, const void* scale,
                     void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * HQQLinear.forward for layers quantised along AXIS 0 (quantize.py:104-116, :880-898), decode sizes: y[M,N] = x[M,K] . dequantize(Wq)^T (+ bias[N])
+ * in one pass over the packed bytes and the meta (csrc/gemv_axis0.hip).  Wq: the reference's axis-0 container of the byte widths — the [gs, N K / gs]
+ * level matrix packed — which holds the same bytes as the axis-1 container of [N, K]; scale / zero: the reference's [1, N K / gs] meta, flat
+ * (weight W[n, k] uses element (n mod (N / gs)) K + k).  Weights rebuilt bit-identically to hqq_hip_dequantize(axis = 0), fp32 accumulation, one
+ * rounding to dtype (+ one for the bias add).  Covered: nbits 8 / 4 / 2 / 1 in fp16, 4 / 2 in bf16; group_size % 16 == 0 with N % group_size == 0
+ * (group_size = N is the reference's group_size=None); K % 64 == 0; 1 <= M <= HQQ_GEMV_MAX_M.  Anything else: HQQ_ERR_UNSUPPORTED ("not covered").
+ * opts: bits outside HQQ_OPT_ALL are an argument error; none changes this kernel (its weights are always the exact ones).
+ * Workspace: hqq_hip_gemv_axis0_workspace_bytes(...) bytes, never 0 — fp32 partial sums of the K splits, parked past the counter head of the
+ * decode workspace (same contract as hqq_hip_gemv_workspace_bytes; this call leaves the counters untouched).  Two launches: the contraction and a
+ * reduce that sums the splits in a fixed order (deterministic; the split depends on the shape only).
+ * ------------------------------------------------------------------------------------------- */
+size_t hqq_hip_gemv_axis0_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype);
+int hqq_hip_gemv_axis0(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias, void* y,
+                       int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
