@@ -36,6 +36,12 @@ SYMBOLS = {
     "hqq_hip_attn_decode": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
     "hqq_hip_rope_attn_decode": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
     "hqq_hip_attn_decode_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    # one decode step of a batch of sequences (csrc/block.hip, the *_batched entry points)
+    "hqq_hip_rope_cache_batched": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
+    "hqq_hip_token_prologue_batched": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "hqq_hip_argmax_advance_batched": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "hqq_hip_attn_decode_batched": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
+    "hqq_hip_rope_attn_decode_batched": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
     "hqq_hip_gemv_workspace_bytes": (_sz, [_i32, _i32, _vp, _i64, _i64, _i64, _i32, _u32]),
     "hqq_hip_gemv": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _sz, _vp]),
     "hqq_hip_gemv_grouped": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _u32, _vp, _sz, _vp]),

@@ -112,7 +112,8 @@ __global__ __launch_bounds__(512) void add_rmsnorm_kernel(uint16_t* __restrict__
   }
 }
 
-// ---- rotary embedding of q and k, KV-cache write.  One thread per (head, i < hd / 2): elements i and i + hd / 2 of a head ----
+// ---- rotary embedding of q and k, KV-cache write.  One thread per (head, i < hd / 2): elements i and i + hd / 2 of a head.
+//      blockIdx.y: the sequence of a batch (hqq_hip_rope_cache_batched) — every tensor advances by one sequence's extent, the arithmetic is the same ----
 template <bool BF>
 __global__ __launch_bounds__(256) void rope_cache_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
                                                          const uint16_t* __restrict__ cosv, const uint16_t* __restrict__ sinv, const int64_t* __restrict__ pos,
@@ -122,6 +123,16 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(const uint16_t* __restr
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   const int total = (n_heads + n_kv) * half;
   if (id >= total) return;
+  const int64_t row = blockIdx.y;
+  q += row * n_heads * hd;
+  q_out += row * n_heads * hd;
+  k += row * n_kv * hd;
+  v += row * n_kv * hd;
+  cosv += row * hd;
+  sinv += row * hd;
+  pos += row;
+  k_cache += row * n_kv * cache_len * hd;
+  v_cache += row * n_kv * cache_len * hd;
   const int head = id / half, i = id - head * half;
   const bool is_k = head >= n_heads;
   const uint16_t* src = is_k ? k + static_cast<int64_t>(head - n_heads) * hd : q + static_cast<int64_t>(head) * hd;
@@ -168,7 +179,9 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const uint16_t* __restric
 //      Deterministic: no atomics, fixed orders.  Keys beyond pos are never read.
 //      ROPE = true (hqq_hip_rope_attn_decode): q, k, v are the RAW projections; the workgroup applies the rotary embedding to its query and to its
 //      KV head's new key itself (rope_cache_kernel's arithmetic, rounding for rounding), uses the new key / value from LDS for position pos — the
-//      cache is only read below pos, so no workgroup depends on another's write — and the first query head of each KV head writes them to the cache ----
+//      cache is only read below pos, so no workgroup depends on another's write — and the first query head of each KV head writes them to the cache.
+//      blockIdx.z: the sequence of a batch (the *_batched entry points) — its own q / k / v rows, cache [n_kv, L, HD], position and output row;
+//      its records are those of head b n_heads + h ----
 template <int HD, bool ROPE, bool BF>
 __global__ __launch_bounds__(512) void attn_decode_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc_in, const uint16_t* __restrict__ vc_in,
                                                           const int64_t* __restrict__ pos, uint16_t* __restrict__ out, int n_heads, int n_kv, int L, float scaling,
@@ -176,6 +189,23 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(const uint16_t* __rest
                                                           const uint16_t* __restrict__ sinv, uint16_t* __restrict__ kc_out, uint16_t* __restrict__ vc_out,
                                                           int S, float* __restrict__ ws) {
   using E = El<BF>;
+  {
+    const int64_t row = blockIdx.z;
+    q += row * n_heads * HD;
+    out += row * n_heads * HD;
+    kc_in += row * n_kv * L * HD;
+    vc_in += row * n_kv * L * HD;
+    pos += row;
+    if constexpr (ROPE) {
+      k_raw += row * n_kv * HD;
+      v_raw += row * n_kv * HD;
+      cosv += row * HD;
+      sinv += row * HD;
+      kc_out += row * n_kv * L * HD;
+      vc_out += row * n_kv * L * HD;
+    }
+    if (S > 1) ws += row * n_heads * S * (HD + 2);
+  }
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   float* red = reinterpret_cast<float*>(smem);                 // [16] reduction scratch
   uint16_t* qs = reinterpret_cast<uint16_t*>(smem + 64);        // [HD] the query; ROPE: + [HD] the new key, [HD] the new value
@@ -364,11 +394,20 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
 //      query in front; argmax, token hand-over and position increment behind), one launch each instead of nine small torch kernels.  Pure copies and compares:
 //      bit-identical to the torch ops they replace.
 //      token_prologue: h = embed[tok]; cos = cos_tab[pos]; sin = sin_tab[pos]; mask[i] = i <= pos ? 0 : -inf (mask == null: the caller's attention needs none).
-//      A token / position outside the tables reads the last row (the torch ops would trap; the host checks positions, utils/generation.py) ----
+//      A token / position outside the tables reads the last row (the torch ops would trap; the host checks positions, utils/generation.py).
+//      blockIdx.y: the sequence of a batch (hqq_hip_token_prologue_batched): tok / pos element, h [H], cos / sin [hd] and mask [L] row of its own ----
 __global__ __launch_bounds__(256) void token_prologue_kernel(const int64_t* __restrict__ tok, const int64_t* __restrict__ pos, const uint16_t* __restrict__ embed, int64_t vocab, int H,
                                                              const uint16_t* __restrict__ cos_tab, const uint16_t* __restrict__ sin_tab, int64_t L, int hd,
                                                              uint16_t* __restrict__ h, uint16_t* __restrict__ cos_o, uint16_t* __restrict__ sin_o, uint16_t* __restrict__ mask,
                                                              uint16_t zero_bits, uint16_t ninf_bits) {
+  {
+    const int64_t row = blockIdx.y;
+    tok += row;
+    pos += row;
+    h += row * H;
+    if (cos_tab) { cos_o += row * hd; sin_o += row * hd; }
+    if (mask) mask += row * L;
+  }
   int64_t t = tok[0], p = pos[0];
   t = t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
   const int64_t pr = p < 0 ? 0 : (p >= L ? L - 1 : p);
@@ -384,13 +423,21 @@ __global__ __launch_bounds__(256) void token_prologue_kernel(const int64_t* __re
 }
 
 // argmax_advance: next = the FIRST index of the largest logit (torch.argmax's tie rule; logits finite), written to next_tok and tok, pos += 1.  One workgroup:
-// 1024 threads keep (value, index) of their strided share in index order, then a fixed tree in LDS.
+// 1024 threads keep (value, index) of their strided share in index order, then a fixed tree in LDS.  blockIdx.x: the sequence of a batch
+// (hqq_hip_argmax_advance_batched): logits row, next_tok / tok / pos element of its own.
 template <bool BF>
 __global__ __launch_bounds__(1024) void argmax_advance_kernel(const uint16_t* __restrict__ logits, int n, int64_t* __restrict__ next_tok, int64_t* __restrict__ tok, int64_t* __restrict__ pos) {
   using E = El<BF>;
   __shared__ float bv[1024];
   __shared__ int bi[1024];
   const int tid = static_cast<int>(threadIdx.x);
+  {
+    const int64_t row = blockIdx.x;
+    logits += row * n;
+    next_tok += row;
+    if (tok) tok += row;
+    if (pos) pos += row;
+  }
   // torch.argmax's order: a NaN is the maximum (the FIRST NaN wins), otherwise the greatest value, the earliest index on a tie
   auto better = [](float v, int i, float bvv, int bii) {
     if (bii == 0x7fffffff) return true;
@@ -457,21 +504,44 @@ int hqq_hip_add_rmsnorm(void* h, const void* delta, const void* weight, float ep
   return check_launch("hqq_hip_add_rmsnorm");
 }
 
-int hqq_hip_rope_cache(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, void* q_out, void* k_cache,
-                       void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
+}  // extern "C"
+
+// the batch count of a *_batched call: one grid dimension (y / z) of up to 65535 sequences
+static inline bool batch_ok(int64_t batch, const char* who) {
+  if (batch >= 1 && batch <= 65535) return true;
+  set_error("%s: batch %lld outside [1, 65535]", who, (long long)batch);
+  return false;
+}
+
+static int rope_cache_run(const char* who, const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out,
+                          void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
   clear_stale_error();
-  if (!block_dtype_ok(dtype, "hqq_hip_rope_cache")) return HQQ_ERR_UNSUPPORTED;
+  if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
+  if (!batch_ok(batch, who)) return HQQ_ERR_SHAPE;
   if (!q || !k || !v || !cos || !sin || !pos_dev || !q_out || !k_cache || !v_cache || n_heads < 1 || n_kv_heads < 1 || head_dim < 2 || head_dim % 2 || cache_len < 1 ||
-      (n_heads + n_kv_heads) * head_dim > INT32_MAX || cache_len > INT32_MAX) { set_error("hqq_hip_rope_cache: bad arguments"); return HQQ_ERR_SHAPE; }
+      (n_heads + n_kv_heads) * head_dim > INT32_MAX || cache_len > INT32_MAX) { set_error("%s: bad arguments", who); return HQQ_ERR_SHAPE; }
   const int64_t total = (n_heads + n_kv_heads) * (head_dim / 2);
 #define HQQ_ROPE_GO(BFV)                                                                                                                          \
-  hipLaunchKernelGGL(rope_cache_kernel<BFV>, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, as_stream(stream), static_cast<cu16>(q), static_cast<cu16>(k), \
+  hipLaunchKernelGGL(rope_cache_kernel<BFV>, dim3(static_cast<unsigned>((total + 255) / 256), static_cast<unsigned>(batch)), dim3(256), 0, as_stream(stream), \
+                     static_cast<cu16>(q), static_cast<cu16>(k),                                                                                  \
                      static_cast<cu16>(v), static_cast<cu16>(cos), static_cast<cu16>(sin), pos_dev, static_cast<u16>(q_out), static_cast<u16>(k_cache),  \
                      static_cast<u16>(v_cache), static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(head_dim), static_cast<int>(cache_len))
   if (dtype == HQQ_BF16) HQQ_ROPE_GO(true);
   else HQQ_ROPE_GO(false);
 #undef HQQ_ROPE_GO
-  return check_launch("hqq_hip_rope_cache");
+  return check_launch(who);
+}
+
+extern "C" {
+
+int hqq_hip_rope_cache(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, void* q_out, void* k_cache,
+                       void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
+  return rope_cache_run("hqq_hip_rope_cache", q, k, v, cos, sin, pos_dev, 1, q_out, k_cache, v_cache, n_heads, n_kv_heads, head_dim, cache_len, dtype, stream);
+}
+
+int hqq_hip_rope_cache_batched(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out,
+                               void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
+  return rope_cache_run("hqq_hip_rope_cache_batched", q, k, v, cos, sin, pos_dev, batch, q_out, k_cache, v_cache, n_heads, n_kv_heads, head_dim, cache_len, dtype, stream);
 }
 
 int hqq_hip_silu_mul(const void* gate, const void* up, void* out, int64_t n, int dtype, void* stream) {
@@ -486,12 +556,13 @@ int hqq_hip_silu_mul(const void* gate, const void* up, void* out, int64_t n, int
 }
 
 static int attn_decode_run(const char* who, bool rope, const void* q, const void* k_raw, const void* v_raw, const void* cosv, const void* sinv, const int64_t* pos_dev,
-                           void* k_cache, void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype,
-                           int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
+                           int64_t batch, void* k_cache, void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling,
+                           int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
   clear_stale_error();
   if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
+  if (!batch_ok(batch, who)) return HQQ_ERR_SHAPE;
   if (!q || !k_cache || !v_cache || !pos_dev || !out || (rope && (!k_raw || !v_raw || !cosv || !sinv)) || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads ||
-      cache_len < 1 || cache_len > 30000 || n_heads > INT32_MAX) {
+      cache_len < 1 || cache_len > 30000 || n_heads > INT32_MAX || batch * n_heads > INT32_MAX) {
     set_error("%s: bad arguments (cache_len <= 30000, n_heads a multiple of n_kv_heads)", who);
     return HQQ_ERR_SHAPE;
   }
@@ -503,13 +574,14 @@ static int attn_decode_run(const char* who, bool rope, const void* q, const void
   const int HD = static_cast<int>(head_dim);
   if (splits < 1 || splits > 64) { set_error("%s: splits must be 1..64 (got %lld)", who, (long long)splits); return HQQ_ERR_SHAPE; }
   const int S = static_cast<int>(splits);
-  if (S > 1 && (!workspace || workspace_bytes < static_cast<size_t>(n_heads) * S * (HD + 2) * sizeof(float))) {
+  // (a batch's records: those of batch * n_heads heads, hqq_hip_attn_decode_workspace_bytes(batch * n_heads, ...))
+  if (S > 1 && (!workspace || workspace_bytes < static_cast<size_t>(batch * n_heads) * S * (HD + 2) * sizeof(float))) {
     set_error("%s: %lld splits need a workspace of hqq_hip_attn_decode_workspace_bytes(...) bytes", who, (long long)splits);
     return HQQ_ERR_SHAPE;
   }
   float* wsf = static_cast<float*>(workspace);
   const int lds = 64 + HD * 6 + 8 * HD * 4 + static_cast<int>((cache_len + S - 1) / S + 8) * 4;
-  const dim3 grid(static_cast<unsigned>(n_heads), static_cast<unsigned>(S)), block(512);
+  const dim3 grid(static_cast<unsigned>(n_heads), static_cast<unsigned>(S), static_cast<unsigned>(batch)), block(512);
   static LdsRaised raised[12];
   constexpr int LDS_MAX = 64 + 256 * 6 + 8 * 256 * 4 + 30000 * 4;
 #define HQQ_ATTN_GO(HDV, RP, BFV, IDX)                                                                                                     \
@@ -534,9 +606,10 @@ static int attn_decode_run(const char* who, bool rope, const void* q, const void
   else HQQ_ATTN_HD(false, false, 9);
 #undef HQQ_ATTN_HD
 #undef HQQ_ATTN_GO
-  if (S > 1) {
-    if (bf) hipLaunchKernelGGL(attn_combine_kernel<true>, dim3(static_cast<unsigned>(n_heads)), dim3(256), 0, as_stream(stream), wsf, static_cast<u16>(out), S, HD);
-    else hipLaunchKernelGGL(attn_combine_kernel<false>, dim3(static_cast<unsigned>(n_heads)), dim3(256), 0, as_stream(stream), wsf, static_cast<u16>(out), S, HD);
+  if (S > 1) {   // (record of head b n_heads + h and output row b, head h: the same offset for a dense [batch, n_heads, HD] output)
+    const dim3 cgrid(static_cast<unsigned>(batch * n_heads));
+    if (bf) hipLaunchKernelGGL(attn_combine_kernel<true>, cgrid, dim3(256), 0, as_stream(stream), wsf, static_cast<u16>(out), S, HD);
+    else hipLaunchKernelGGL(attn_combine_kernel<false>, cgrid, dim3(256), 0, as_stream(stream), wsf, static_cast<u16>(out), S, HD);
   }
   return check_launch(who);
 }
@@ -547,41 +620,81 @@ size_t hqq_hip_attn_decode_workspace_bytes(int64_t n_heads, int64_t head_dim, in
 
 int hqq_hip_attn_decode(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, void* out, int64_t n_heads, int64_t n_kv_heads,
                         int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
-  return attn_decode_run("hqq_hip_attn_decode", false, q, nullptr, nullptr, nullptr, nullptr, pos_dev, const_cast<void*>(k_cache), const_cast<void*>(v_cache), out,
+  return attn_decode_run("hqq_hip_attn_decode", false, q, nullptr, nullptr, nullptr, nullptr, pos_dev, 1, const_cast<void*>(k_cache), const_cast<void*>(v_cache), out,
                          n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype, splits, workspace, workspace_bytes, stream);
 }
 
 int hqq_hip_rope_attn_decode(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, void* k_cache, void* v_cache, void* out,
                              int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  return attn_decode_run("hqq_hip_rope_attn_decode", true, q, k, v, cos, sin, pos_dev, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype,
+  return attn_decode_run("hqq_hip_rope_attn_decode", true, q, k, v, cos, sin, pos_dev, 1, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype,
                          splits, workspace, workspace_bytes, stream);
 }
 
-int hqq_hip_token_prologue(const int64_t* tok_dev, const int64_t* pos_dev, const void* embed, int64_t vocab, int64_t H, const void* cos_tab, const void* sin_tab, int64_t L,
-                           int64_t head_dim, void* h, void* cos, void* sin, void* mask, int dtype, void* stream) {
+int hqq_hip_attn_decode_batched(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, int64_t batch, void* out, int64_t n_heads,
+                                int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  return attn_decode_run("hqq_hip_attn_decode_batched", false, q, nullptr, nullptr, nullptr, nullptr, pos_dev, batch, const_cast<void*>(k_cache),
+                         const_cast<void*>(v_cache), out, n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype, splits, workspace, workspace_bytes, stream);
+}
+
+int hqq_hip_rope_attn_decode_batched(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* k_cache,
+                                     void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype,
+                                     int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return attn_decode_run("hqq_hip_rope_attn_decode_batched", true, q, k, v, cos, sin, pos_dev, batch, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, cache_len,
+                         scaling, dtype, splits, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+static int token_prologue_run(const char* who, const int64_t* tok_dev, const int64_t* pos_dev, int64_t batch, const void* embed, int64_t vocab, int64_t H, const void* cos_tab,
+                              const void* sin_tab, int64_t L, int64_t head_dim, void* h, void* cos, void* sin, void* mask, int dtype, void* stream) {
   clear_stale_error();
-  if (!block_dtype_ok(dtype, "hqq_hip_token_prologue")) return HQQ_ERR_UNSUPPORTED;
+  if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
+  if (!batch_ok(batch, who)) return HQQ_ERR_SHAPE;
   if (!tok_dev || !pos_dev || !embed || !h || vocab < 1 || H < 8 || H % 8 || H > INT32_MAX || L < 1 || (cos_tab && (!sin_tab || !cos || !sin || head_dim < 1 || head_dim > INT32_MAX))) {
-    set_error("hqq_hip_token_prologue: bad arguments (H a multiple of 8; cos / sin tables and outputs come together)");
+    set_error("%s: bad arguments (H a multiple of 8; cos / sin tables and outputs come together)", who);
     return HQQ_ERR_SHAPE;
   }
-  if (!aligned16(embed) || !aligned16(h)) { set_error("hqq_hip_token_prologue: embed / h must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
+  if (!aligned16(embed) || !aligned16(h)) { set_error("%s: embed / h must be 16-byte aligned", who); return HQQ_ERR_ALIGN; }
   const uint16_t ninf = dtype == HQQ_BF16 ? 0xFF80u : 0xFC00u;
   const int64_t work = (mask ? L : 0) > H / 8 ? (mask ? L : 0) : H / 8;
   const unsigned blocks = static_cast<unsigned>(work / 256 < 1 ? 1 : (work / 256 > 64 ? 64 : work / 256));
-  hipLaunchKernelGGL(token_prologue_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tok_dev, pos_dev, static_cast<cu16>(embed), vocab, static_cast<int>(H), static_cast<cu16>(cos_tab),
-                     static_cast<cu16>(sin_tab), L, static_cast<int>(head_dim), static_cast<u16>(h), static_cast<u16>(cos), static_cast<u16>(sin), static_cast<u16>(mask), static_cast<uint16_t>(0), ninf);
-  return check_launch("hqq_hip_token_prologue");
+  hipLaunchKernelGGL(token_prologue_kernel, dim3(blocks, static_cast<unsigned>(batch)), dim3(256), 0, as_stream(stream), tok_dev, pos_dev, static_cast<cu16>(embed), vocab,
+                     static_cast<int>(H), static_cast<cu16>(cos_tab), static_cast<cu16>(sin_tab), L, static_cast<int>(head_dim), static_cast<u16>(h), static_cast<u16>(cos),
+                     static_cast<u16>(sin), static_cast<u16>(mask), static_cast<uint16_t>(0), ninf);
+  return check_launch(who);
+}
+
+static int argmax_advance_run(const char* who, const void* logits, int64_t batch, int64_t n, int dtype, int64_t* next_tok_dev, int64_t* tok_dev, int64_t* pos_dev, void* stream) {
+  clear_stale_error();
+  if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
+  if (!batch_ok(batch, who)) return HQQ_ERR_SHAPE;
+  if (!logits || !next_tok_dev || n < 1 || n > INT32_MAX - 1) { set_error("%s: bad arguments", who); return HQQ_ERR_SHAPE; }
+  const dim3 grid(static_cast<unsigned>(batch));
+  if (dtype == HQQ_BF16) hipLaunchKernelGGL(argmax_advance_kernel<true>, grid, dim3(1024), 0, as_stream(stream), static_cast<cu16>(logits), static_cast<int>(n), next_tok_dev, tok_dev, pos_dev);
+  else hipLaunchKernelGGL(argmax_advance_kernel<false>, grid, dim3(1024), 0, as_stream(stream), static_cast<cu16>(logits), static_cast<int>(n), next_tok_dev, tok_dev, pos_dev);
+  return check_launch(who);
+}
+
+extern "C" {
+
+int hqq_hip_token_prologue(const int64_t* tok_dev, const int64_t* pos_dev, const void* embed, int64_t vocab, int64_t H, const void* cos_tab, const void* sin_tab, int64_t L,
+                           int64_t head_dim, void* h, void* cos, void* sin, void* mask, int dtype, void* stream) {
+  return token_prologue_run("hqq_hip_token_prologue", tok_dev, pos_dev, 1, embed, vocab, H, cos_tab, sin_tab, L, head_dim, h, cos, sin, mask, dtype, stream);
+}
+
+int hqq_hip_token_prologue_batched(const int64_t* tok_dev, const int64_t* pos_dev, int64_t batch, const void* embed, int64_t vocab, int64_t H, const void* cos_tab,
+                                   const void* sin_tab, int64_t L, int64_t head_dim, void* h, void* cos, void* sin, void* mask, int dtype, void* stream) {
+  return token_prologue_run("hqq_hip_token_prologue_batched", tok_dev, pos_dev, batch, embed, vocab, H, cos_tab, sin_tab, L, head_dim, h, cos, sin, mask, dtype, stream);
 }
 
 int hqq_hip_argmax_advance(const void* logits, int64_t n, int dtype, int64_t* next_tok_dev, int64_t* tok_dev, int64_t* pos_dev, void* stream) {
-  clear_stale_error();
-  if (!block_dtype_ok(dtype, "hqq_hip_argmax_advance")) return HQQ_ERR_UNSUPPORTED;
-  if (!logits || !next_tok_dev || n < 1 || n > INT32_MAX - 1) { set_error("hqq_hip_argmax_advance: bad arguments"); return HQQ_ERR_SHAPE; }
-  if (dtype == HQQ_BF16) hipLaunchKernelGGL(argmax_advance_kernel<true>, dim3(1), dim3(1024), 0, as_stream(stream), static_cast<cu16>(logits), static_cast<int>(n), next_tok_dev, tok_dev, pos_dev);
-  else hipLaunchKernelGGL(argmax_advance_kernel<false>, dim3(1), dim3(1024), 0, as_stream(stream), static_cast<cu16>(logits), static_cast<int>(n), next_tok_dev, tok_dev, pos_dev);
-  return check_launch("hqq_hip_argmax_advance");
+  return argmax_advance_run("hqq_hip_argmax_advance", logits, 1, n, dtype, next_tok_dev, tok_dev, pos_dev, stream);
+}
+
+int hqq_hip_argmax_advance_batched(const void* logits, int64_t batch, int64_t n, int dtype, int64_t* next_tok_dev, int64_t* tok_dev, int64_t* pos_dev, void* stream) {
+  return argmax_advance_run("hqq_hip_argmax_advance_batched", logits, batch, n, dtype, next_tok_dev, tok_dev, pos_dev, stream);
 }
 
 }  // extern "C"

@@ -906,6 +906,120 @@ def argmax_advance(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, 
     _C.check(rc, "hqq_hip_argmax_advance")
 
 
+# ---- the same for a batch of B independent sequences, one decode step each (the *_batched entry points: row b gives the bits the batch-1 call gives
+#      for sequence b alone).  tok / pos: int64 [B] on the device; every other tensor is dense, one row (or cache) per sequence ----------------------
+def _batch_of(pos: Tensor, who: str) -> int:
+    if pos.dtype != torch.int64 or not pos.is_contiguous() or pos.numel() < 1:
+        raise ValueError(f"hqq_amd: {who} takes a dense int64 position tensor of B >= 1 elements")
+    return pos.numel()
+
+
+def token_prologue_batched(tok: Tensor, pos: Tensor, embed: Tensor, h: Tensor, cos_tab=None, sin_tab=None, cos=None, sin=None, mask=None) -> None:
+    """token_prologue for B sequences in one launch (hqq_hip_token_prologue_batched): h [B, H] = embed[tok[b]]; cos / sin [B, head_dim] = row pos[b] of the
+    rotary tables [L, head_dim] (skipped when the tables are None); mask [B, L] = 0 up to pos[b], -inf beyond (skipped when None).  tok [B] or [B, 1] / pos [B]
+    int64 on the device: graph-replay safe.  Copies and compares only: per row the same bits as embed_tokens, index_select and torch.where."""
+    _dev(tok, pos, embed, h)
+    B = _batch_of(pos, "token_prologue_batched")
+    if tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous() or embed.dim() != 2 or not embed.is_contiguous() or \
+            h.numel() != B * embed.shape[1] or not h.is_contiguous() or h.dtype != embed.dtype:
+        raise ValueError("hqq_amd: token_prologue_batched takes int64 tok / pos of B elements, a dense [vocab, H] embedding and a dense h [B, H] of its dtype")
+    L, hd = 1, 0
+    if cos_tab is not None:
+        _dev(cos_tab, sin_tab, cos, sin)
+        if cos_tab.shape != sin_tab.shape or cos_tab.dim() != 2 or not (cos_tab.is_contiguous() and sin_tab.is_contiguous()) or cos.numel() != B * cos_tab.shape[1] or \
+                sin.numel() != B * cos_tab.shape[1] or not (cos.is_contiguous() and sin.is_contiguous()) or any(t.dtype != embed.dtype for t in (cos_tab, sin_tab, cos, sin)):
+            raise ValueError("hqq_amd: token_prologue_batched takes dense [L, head_dim] rotary tables and dense [B, head_dim] outputs of the compute dtype")
+        L, hd = int(cos_tab.shape[0]), int(cos_tab.shape[1])
+    if mask is not None:
+        _dev(mask)
+        if mask.dtype != embed.dtype or not mask.is_contiguous() or mask.numel() % B or (cos_tab is not None and mask.numel() != B * L):
+            raise ValueError("hqq_amd: token_prologue_batched's mask is a dense [B, L] tensor of the compute dtype, L the rotary tables' rows")
+        L = int(mask.numel() // B)
+    with torch.cuda.device(h.device):
+        rc = _C.lib().hqq_hip_token_prologue_batched(_p(tok), _p(pos), B, _p(embed), int(embed.shape[0]), int(embed.shape[1]), _p(cos_tab), _p(sin_tab), L, hd, _p(h),
+                                                     _p(cos), _p(sin), _p(mask), _dt(embed.dtype), _stream())
+    _C.check(rc, "hqq_hip_token_prologue_batched")
+
+
+def rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
+    """rope_cache for B sequences in one launch: q_out [B, n_heads * hd] = rotary(q [B, n_heads * hd]) with cos / sin [B, hd]; rotary(k) and v ([B, n_kv * hd])
+    go into row b of the caches [B, n_kv_heads, cache_len, head_dim] (HF's StaticCache tensors of batch B) at position pos[b]; a position outside the cache writes nothing"""
+    _dev(q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
+    B = _batch_of(pos, "rope_cache_batched")
+    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError("hqq_amd: rope_cache_batched takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
+    hd = k_cache.shape[-1]
+    if cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
+            k.numel() != B * k_cache.shape[1] * hd or v.numel() != k.numel() or q_out.numel() != q.numel():
+        raise ValueError("hqq_amd: rope_cache_batched takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd]")
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_rope_cache_batched(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), B, _p(q_out), _p(k_cache), _p(v_cache), q.numel() // (B * hd),
+                                                 k_cache.shape[1], hd, k_cache.shape[2], _dt(q.dtype), _stream())
+    _C.check(rc, "hqq_hip_rope_cache_batched")
+    return q_out
+
+
+def _attn_batched_args(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, who: str):
+    B = _batch_of(pos, who)
+    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
+    _, n_kv, L, hd = k_cache.shape
+    if q.numel() % (B * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes dense q / out [B, n_heads * head_dim]")
+    return B, q.numel() // (B * hd), n_kv, L, hd
+
+
+def attn_workspace_batched(device, batch: int, n_heads: int, head_dim: int, splits: int):
+    """the record buffer of a split batched launch (hqq_hip_attn_decode_workspace_bytes(batch * n_heads, ...)), or None"""
+    return attn_workspace(device, int(batch) * int(n_heads), head_dim, splits)
+
+
+def attn_decode_batched(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode for B sequences in one launch: q / out [B, n_heads * hd], caches [B, n_kv, cache_len, hd], pos int64 [B]; sequence b attends over its own first
+    pos[b] + 1 keys.  splits is one for the whole launch (pick it from the largest position, attn_splits): a sequence with fewer visible keys than splits
+    leaves the surplus shares empty, and the merging launch ignores them"""
+    _dev(q, k_cache, v_cache, pos, out)
+    B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "attn_decode_batched")
+    if splits > 1 and workspace is None:
+        workspace = attn_workspace_batched(q.device, B, n_heads, hd, splits)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_attn_decode_batched(_p(q), _p(k_cache), _p(v_cache), _p(pos), B, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
+                                                  int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
+    _C.check(rc, "hqq_hip_attn_decode_batched")
+    return out
+
+
+def rope_attn_decode_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, out: Tensor, scaling: float,
+                             splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """rope_attn_decode for B sequences in one launch: raw q [B, n_heads * hd], k / v [B, n_kv * hd], cos / sin [B, hd]; each sequence's new key / value go to its
+    own cache row at pos[b] (bit-identical to rope_cache_batched's); splits as in attn_decode_batched"""
+    _dev(q, k, v, cos, sin, pos, k_cache, v_cache, out)
+    B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "rope_attn_decode_batched")
+    if cos.numel() != B * hd or sin.numel() != B * hd or k.numel() != B * n_kv * hd or v.numel() != k.numel() or \
+            not all(t.is_contiguous() for t in (k, v, cos, sin)):
+        raise ValueError("hqq_amd: rope_attn_decode_batched takes dense k / v [B, n_kv_heads * head_dim] and cos / sin [B, head_dim]")
+    if splits > 1 and workspace is None:
+        workspace = attn_workspace_batched(q.device, B, n_heads, hd, splits)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_rope_attn_decode_batched(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), B, _p(k_cache), _p(v_cache), _p(out), n_heads, n_kv, hd, L,
+                                                       float(scaling), _dt(q.dtype), int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
+    _C.check(rc, "hqq_hip_rope_attn_decode_batched")
+    return out
+
+
+def argmax_advance_batched(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, pos: Tensor | None = None) -> None:
+    """argmax_advance for B sequences in one launch, one workgroup per row (hqq_hip_argmax_advance_batched): next_tok[b] = logits[b].argmax() (torch.argmax's
+    tie and NaN rule), tok[b] = the same, pos[b] += 1 (each skipped when None).  logits [B, vocab] dense; int64 tensors of B elements on the device."""
+    _dev(logits, next_tok)
+    B = next_tok.numel()
+    if logits.dim() != 2 or logits.shape[0] != B or not logits.is_contiguous() or next_tok.dtype != torch.int64 or not next_tok.is_contiguous() or \
+            any(t is not None and (t.dtype != torch.int64 or t.numel() != B or not t.is_contiguous()) for t in (tok, pos)):
+        raise ValueError("hqq_amd: argmax_advance_batched takes dense logits [B, vocab] and dense int64 token / position tensors of B elements")
+    with torch.cuda.device(logits.device):
+        rc = _C.lib().hqq_hip_argmax_advance_batched(_p(logits), B, logits.shape[1], _dt(logits.dtype), _p(next_tok), _p(tok), _p(pos), _stream())
+    _C.check(rc, "hqq_hip_argmax_advance_batched")
+
+
 def silu_mul(gate: Tensor, up: Tensor, out: Tensor | None = None) -> Tensor:
     """LlamaMLP's act_fn(gate) * up in one kernel (fp16)"""
     _dev(gate, up)

@@ -12,6 +12,46 @@ from torch import Tensor
 from .. import ops
 
 
+def kv_bucket(p: int, attention: str, max_cache_len: int) -> int:
+    """the cache bucket a fused step at position p attends over (GraphedGreedyDecoder._kv_len's rule): "sdpa" 64, then multiples of 128 up to 1024,
+    then multiples of 512; "hip" (the kernel attention only changes its launch shape beyond 1024 visible keys) 1024, then powers of two; at most the cache"""
+    n = p + 1
+    if attention == "hip":
+        b = 1024
+        while b < n:
+            b *= 2
+    elif n <= 64:                 # SDPA over 64 / 128 / 256 / 512 keys: 6.4 / 9.0 / 14.4 / 24.8 us per block
+        b = 64
+    elif n <= 1024:
+        b = -(-n // 128) * 128
+    else:
+        b = -(-n // 512) * 512
+    return min(b, max_cache_len)
+
+
+def batch_kv_bucket(positions, attention: str, max_cache_len: int) -> int:
+    """the bucket of a batched step: that of the LARGEST row position (every row attends within it, each masked beyond its own position)"""
+    return kv_bucket(max(int(p) for p in positions), attention, max_cache_len)
+
+
+def check_batch_lengths(lengths, max_new_tokens: int, max_cache_len: int) -> None:
+    """every prompt of a batch must leave room for max_new_tokens in the cache: T_b + n <= max_cache_len (ValueError naming the first row that does not)"""
+    if max_new_tokens < 1:
+        raise ValueError("hqq_amd: max_new_tokens must be >= 1")
+    for b, T in enumerate(lengths):
+        if T < 1 or T + max_new_tokens > max_cache_len:
+            raise ValueError(f"hqq_amd: prompt {b} ({T} tokens) + {max_new_tokens} new tokens does not fit a cache of {max_cache_len} positions")
+
+
+def eos_lengths(rows, eos_token_id, n: int) -> list:
+    """per row of generated tokens (lists of ints), how many to keep: up to and including the row's first eos_token_id, else n (generate()'s rule, per row)"""
+    out = []
+    for r in rows:
+        r = list(r)[:n]
+        out.append(r.index(eos_token_id) + 1 if eos_token_id is not None and eos_token_id in r else len(r))
+    return out
+
+
 class GraphedGreedyDecoder:
     """fused=True (default): a Llama-shaped model whose decoder linears are HQQLinearHIP layers decodes through hqq_amd.utils.llama_fused —
     RMSNorm (+ the residual adds), rotary + KV-cache write and SiLU * up as one HIP kernel each around the grouped GEMVs, HF's own attention
@@ -39,6 +79,8 @@ class GraphedGreedyDecoder:
         self.graphs = {}       # attended cache length -> captured step
         self.cache = None      # HF StaticCache, kept between generate() calls (reset in place)
         self._state = None     # (tok, next_tok, pos): the device tensors the captured graphs read and write
+        self._batch = {}       # B -> the kept state of generate_batch (B-row cache, batch-1 prefill cache, batched step, tok / next_tok / pos)
+        self.batch_graphs = {} # (B, attended cache length) -> captured batched step
 
     def _kv_len(self, p: int) -> int:
         """how much of the static cache a step at position p attends over.  HF's attention function costs what it is given (the whole masked cache:
@@ -47,18 +89,7 @@ class GraphedGreedyDecoder:
         how many workgroups share a head's keys (one up to 1024 keys)"""
         if self.step is None or not self.bucket_cache:
             return self.max_cache_len
-        n = p + 1
-        if self.attention == "hip":   # (the kernel attention only changes its launch shape beyond 1024 visible keys: powers of two from there)
-            b = 1024
-            while b < n:
-                b *= 2
-        elif n <= 64:                 # SDPA over 64 / 128 / 256 / 512 keys: 6.4 / 9.0 / 14.4 / 24.8 us per block
-            b = 64
-        elif n <= 1024:
-            b = -(-n // 128) * 128
-        else:
-            b = -(-n // 512) * 512
-        return min(b, self.max_cache_len)
+        return kv_bucket(p, self.attention, self.max_cache_len)
 
     def _pick(self, logits: Tensor) -> Tensor:
         """logits [1, vocab] -> the next token [1, 1].  Greedy: argmax.  do_sample: temperature, then the top_k cut, then one draw from the softmax by the
@@ -102,13 +133,15 @@ class GraphedGreedyDecoder:
         return tuple(fp)
 
     def reset(self) -> None:
-        """drop what generate() keeps between calls (the static cache, the fused step with its re-laid-out layer copies, the captured graphs).  generate() calls it
+        """drop what generate() and generate_batch() keep between calls (the static caches, the fused steps with their re-laid-out layer copies, the captured graphs).  generate() calls it
         by itself when the model's quantised layers are no longer the ones the state was built from (_fingerprint)"""
         self.cache = None
         self.step = None
         self.graph = None
         self.graphs = {}
         self._state = None
+        self._batch = {}
+        self.batch_graphs = {}
 
     @torch.no_grad()
     def generate(self, input_ids: Tensor, max_new_tokens: int, use_graph: bool = True, eos_token_id: int | None = None, check_every: int = 16) -> Tensor:
@@ -219,6 +252,155 @@ class GraphedGreedyDecoder:
         return {"ms_per_token": ms, "tok_s": 1e3 / ms, "new_tokens": new_tokens, "prompt_tokens": T}
 
 
+    # ---- a batch of prompts through ONE fused step per token (llama_fused.FusedLlamaBatchStep) ----------------------------------------------------------------
+    @torch.no_grad()
+    def generate_batch(self, prompts, max_new_tokens: int, use_graph: bool = True, eos_token_id: int | None = None, check_every: int = 16) -> list:
+        """continuations of B prompts of any lengths (a list of 1-D or [1, T_b] int64 tensors), decoded together: each decode step runs the B sequences
+        through one fused step (every linear launch takes the B rows at once, so the weights are streamed once per step for all of them) and is
+        captured / replayed as generate()'s is, one graph per (B, cache bucket of the largest row position), kept across calls.  Returns one
+        [1, T_b + n_b] tensor per prompt: n_b = max_new_tokens, or fewer when row b produced eos_token_id (it then ends with it; the host looks every
+        `check_every` steps, and the loop ends once every row has ended).  Greedy unless the decoder was built with do_sample.
+        Prefill: each prompt alone through the model on a kept batch-1 StaticCache (exactly generate()'s prefill, no padding), whose first T_b positions
+        are copied into row b of a kept B-row StaticCache; row b's first token comes from its own prefill logits.  The B-row cache's cumulative_length
+        is not meaningful (its rows have different lengths): only the fused step reads that cache.
+        B == 1 is generate().  A model the batched step does not cover at B rows (llama_fused.supports_batch), or a cache / attention setting it refuses,
+        decodes the prompts one after another through generate() instead: the same tokens, only slower."""
+        ids = [torch.as_tensor(p).view(1, -1).to(device=self.device, dtype=torch.int64) for p in prompts]
+        B = len(ids)
+        if B == 0:
+            return []
+        lengths = [x.shape[1] for x in ids]
+        check_batch_lengths(lengths, max_new_tokens, self.max_cache_len)
+        if B == 1:
+            return [self.generate(ids[0], max_new_tokens, use_graph=use_graph, eos_token_id=eos_token_id, check_every=check_every)]
+        fp = self._fingerprint()
+        if getattr(self, "_fp", None) != fp:
+            self.reset()
+            self._fp = fp
+        st = self._batch.get(B)
+        kept = st is not None
+        if not kept:
+            st = self._batch_state(B)
+            if st is None:   # not covered: one prompt after another
+                return [self.generate(x, max_new_tokens, use_graph=use_graph, eos_token_id=eos_token_id, check_every=check_every) for x in ids]
+        bc, scratch = st["cache"], st["scratch"]
+        bc.reset()
+        firsts = []
+        for b, x in enumerate(ids):   # prefill: each prompt alone, then its first T_b key / value positions into row b
+            scratch.reset()
+            out = self.model(x, past_key_values=scratch, cache_position=torch.arange(lengths[b], device=self.device), use_cache=True)
+            firsts.append(self._pick(out.logits[:, -1]))
+            for dst, src in zip(bc.layers, scratch.layers):
+                dst.keys[b, :, :lengths[b]].copy_(src.keys[0, :, :lengths[b]])
+                dst.values[b, :, :lengths[b]].copy_(src.values[0, :, :lengths[b]])
+        st["tok"].copy_(torch.cat(firsts, dim=0))
+        st["pos"].copy_(torch.tensor(lengths, device=self.device))
+        toks = [st["tok"].clone()]
+        done = 0
+        n = max_new_tokens
+        for i in range(max_new_tokens - 1):
+            self._advance_batch(st, [T + i for T in lengths], use_graph and (kept or i >= 1))   # (a fresh state's step 0 runs eagerly, as in generate())
+            toks.append(st["tok"].clone())
+            if eos_token_id is not None and (len(toks) - done >= check_every or i == max_new_tokens - 2):
+                seen = torch.cat(toks, dim=1).tolist()   # one host read per check_every steps
+                if all(eos_token_id in r for r in seen):
+                    n = len(toks)
+                    break
+                done = len(toks)
+        rows = torch.cat(toks[:n], dim=1)
+        keep = eos_lengths(rows.tolist(), eos_token_id, n)
+        return [torch.cat([ids[b], rows[b:b + 1, :keep[b]]], dim=1) for b in range(B)]
+
+    def _batch_state(self, B: int):
+        """the kept state of generate_batch at B rows, or None when the batched step does not serve the model there"""
+        fm = self._fused_mod
+        if not (self.fused and fm.supports_batch(self.model, B)):
+            return None
+        cfg = self.model.config
+        n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
+        hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+        cache = self._StaticCache(config=cfg, max_cache_len=self.max_cache_len)
+        cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
+        try:
+            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention)
+        except ValueError:
+            return None
+        st = {"B": B, "cache": cache, "scratch": self._StaticCache(config=cfg, max_cache_len=self.max_cache_len), "step": step,
+              "tok": torch.zeros(B, 1, dtype=torch.int64, device=self.device), "next_tok": torch.zeros(B, 1, dtype=torch.int64, device=self.device),
+              "pos": torch.zeros(B, dtype=torch.int64, device=self.device)}
+        self._batch[B] = st
+        return st
+
+    @torch.no_grad()
+    def _decode_once_batch(self, st, kv_len) -> None:
+        """one transition of every row: logits at pos -> next_tok, tok = next_tok, pos += 1 (on the device)"""
+        logits = st["step"](st["tok"], st["pos"], kv_len)
+        if not self.do_sample and logits.dtype in (torch.float16, torch.bfloat16) and logits.is_contiguous():
+            ops.argmax_advance_batched(logits, st["next_tok"], st["tok"], st["pos"])   # per row: argmax + hand-over + position increment, one launch
+            return
+        st["next_tok"].copy_(self._pick(logits))
+        st["tok"].copy_(st["next_tok"])
+        st["pos"] += 1
+
+    def _batch_kv_len(self, positions) -> int:
+        """_kv_len for a batched step: the bucket of the largest row position"""
+        return batch_kv_bucket(positions, self.attention, self.max_cache_len) if self.bucket_cache else self.max_cache_len
+
+    @torch.no_grad()
+    def _advance_batch(self, st, positions, use_graph: bool) -> None:
+        """one batched step at the host's copy of the row positions: replay the graph of (B, the largest position's bucket), capturing it first if need be"""
+        kv = self._batch_kv_len(positions)
+        key = (st["B"], kv)
+        g = self.batch_graphs.get(key) if use_graph else None
+        if use_graph and g is None:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                snap = (st["tok"].clone(), st["pos"].clone())
+                self._decode_once_batch(st, kv)          # warm-up on the side stream (writes cache slots pos, re-written below)
+                st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
+            torch.cuda.current_stream().wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._decode_once_batch(st, kv)
+            self.batch_graphs[key] = g
+        if g is not None:
+            g.replay()
+        else:
+            self._decode_once_batch(st, kv)
+
+    @torch.no_grad()
+    def benchmark_batch(self, input_ids: Tensor, new_tokens: int = 64, warmup: int = 8) -> dict:
+        """benchmark() for a batch: prefill the B rows of input_ids [B, T], capture the batched step, time `new_tokens` replays of it (HIP events).
+        Returns the step time and the aggregate rate (B tokens per step).  Needs a model the batched step covers at B rows."""
+        B, T = input_ids.shape
+        assert T + warmup + new_tokens + 4 <= self.max_cache_len
+        if B == 1:
+            r = self.benchmark(input_ids, new_tokens, warmup)
+            return {"ms_per_step": r["ms_per_token"], "tok_s": r["tok_s"], "batch": 1, "new_tokens": new_tokens, "prompt_tokens": T}
+        self.generate_batch(list(input_ids), 3, use_graph=True)
+        st = self._batch.get(B)
+        assert st is not None, "hqq_amd: the batched step does not serve this model at this batch (llama_fused.supports_batch)"
+        p = T + 2
+        for _ in range(warmup):
+            self._advance_batch(st, [p] * B, True)
+            p += 1
+        for q in range(p, p + new_tokens):
+            if (B, self._batch_kv_len([q])) not in self.batch_graphs:
+                snap = (st["tok"].clone(), st["pos"].clone())
+                self._advance_batch(st, [q] * B, True)
+                st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(new_tokens):
+            self._advance_batch(st, [p] * B, True)
+            p += 1
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / new_tokens
+        return {"ms_per_step": ms, "tok_s": B * 1e3 / ms, "batch": B, "new_tokens": new_tokens, "prompt_tokens": T}
+
 
 # prompts of different lengths for HFGenerator.warmup(): what matters is that the first cache buckets get their graphs captured, not what is asked
 WARMUP_PROMPTS = ["Hello.", "Name three prime numbers and say why each one is prime.",
@@ -312,6 +494,31 @@ class HFGenerator:
         if print_tokens:
             print(output_text, flush=True)
         return {"output_text": output_text, "output_tokens": output_tokens, "input_tokens": ids[0].cpu()}
+
+    @torch.no_grad()
+    def generate_batch(self, prompts, use_chat_template: bool = True, verbose: bool = True, print_tokens: bool = False) -> list:
+        """generate() for several prompts decoded together (GraphedGreedyDecoder.generate_batch): one dict per prompt with generate()'s keys.  Every prompt gets
+        the same number of new tokens: max_new_tokens, or what the longest prompt leaves of the cache"""
+        ids = [self.tokenize_prompt(p, use_chat_template=use_chat_template)["input_ids"].to(torch.int64) for p in prompts]
+        if not ids:
+            return []
+        T = max(x.shape[1] for x in ids)
+        n = min(self.max_new_tokens, self.cache_size - T)
+        if n < 1:
+            raise ValueError(f"hqq_amd: the longest prompt ({T} tokens) leaves no room in a cache of {self.cache_size}")
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        outs = self.decoder.generate_batch(ids, n, use_graph=self.use_graph, eos_token_id=eos)
+        res = []
+        for x, out in zip(ids, outs):
+            new = out[0, x.shape[1]:]
+            if eos is not None and new.numel() and int(new[-1]) == eos:
+                new = new[:-1]
+            output_tokens = new.cpu()
+            output_text = self.tokenizer.decode(output_tokens)
+            if print_tokens:
+                print(output_text, flush=True)
+            res.append({"output_text": output_text, "output_tokens": output_tokens, "input_tokens": x[0].cpu()})
+        return res
 
     def generate_(self, prompt: str, use_chat_template: bool = True, verbose: bool = False, print_tokens: bool = False) -> dict:
         """HF's own generate with a static cache (generation_hf.py:515-527): the loop this class replaces, for comparison"""

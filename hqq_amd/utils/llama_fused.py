@@ -283,3 +283,159 @@ class FusedLlamaStep:
         """StaticLayer.update's bookkeeping for the n tokens the fused steps appended (kept out of the captured step: one add per layer)"""
         for b in self.blocks:
             b["len"].add_(n)
+
+
+# ---- a decode step of B independent sequences ------------------------------------------------------------------------------------------------
+def batch_covers(dtype, B: int, layers, opts: int = 0) -> bool:
+    """whether the fused decode kernels serve every layer of `layers` — (N, K, group_size, nbits, w3s) each — at M = B activation rows (a pure
+    function of the shapes: no device needed).  The grouped launch (hqq_hip_gemv_grouped) takes a group of layers at B rows where each of them is
+    served on its own, so the rule is per layer: the weight-streaming skinny kernel (ops.skinny_covers: 5..64 rows, group_size 64, K % 256 == 0,
+    K >= 512, fp16 / bf16, 3-bit in the stream layout) or else the decode kernels (ops.decode_covers: fp16 up to 16 rows, bf16 4 / 2-bit and
+    3-bit up to 4; with OPT_FACTORED in `opts` fp16 up to 8).  The 3-bit stream layout outside the skinny kernel: up to 4 rows."""
+    B = int(B)
+    if B < 1:
+        return False
+    factored = bool(int(opts) & ops.OPT_FACTORED) and dtype == torch.float16
+    for (N, K, gs, nbits, w3s) in layers:
+        if ops.skinny_covers(dtype, B, N, K, gs, nbits, w3s):
+            continue
+        if w3s:
+            ok = nbits == 3 and dtype in (torch.float16, torch.bfloat16) and B <= 4 and ops.w3s_covers(N, K, gs)
+        else:
+            ok = ops.decode_covers(dtype, B, N, K, gs, nbits) and not (factored and B > 8)
+        if not ok:
+            return False
+    return True
+
+
+def _decoder_linears(model):
+    """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers"""
+    return [[_hip(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
+            for b in model.model.layers]
+
+
+def supports_batch(model, B: int) -> bool:
+    """supports(model), and every decoder linear served by a fused decode kernel at B rows (batch_covers, with this module's default option bits)"""
+    if not supports(model):
+        return False
+    specs = [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lins in _decoder_linears(model) for L in lins]
+    return batch_covers(model.model.norm.weight.dtype, B, specs, ops._default_opts)
+
+
+class FusedLlamaBatchStep:
+    """decode step t of B independent sequences -> logits of their tokens t + 1, on the model's own weights and an HF StaticCache of batch B
+    (layer.keys / .values [B, n_kv, max_cache_len, hd], used in place).  Each sequence has its own position; the block is FusedLlamaStep's
+    glue="kernels" route with every launch taking the B rows at once:
+        add_rmsnorm -> q|k|v (one grouped GEMV, M = B) -> rope_cache_batched -> attention -> o -> add_rmsnorm -> gate|up (one grouped GEMV) -> silu_mul -> down
+    Attention "sdpa": HF's attention function on the B-row cache with the [B, 1, 1, kv_len] mask of token_prologue_batched; "hip":
+    rope_attn_decode_batched.  Row b of every glue kernel gives the bits of the batch-1 kernel for sequence b alone; the linears run at M = B
+    (supports_batch).  The folded launches (ops.gemv_block) are batch-1 only and never used here."""
+
+    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa"):
+        from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
+        from transformers.models.llama.modeling_llama import eager_attention_forward
+        self.model = model
+        inner = model.model
+        self.inner = inner
+        cfg = model.config
+        self.device = dev = inner.embed_tokens.weight.device
+        self.dt = dt = inner.norm.weight.dtype
+        self.B = B = int(batch)
+        self.n_heads = cfg.num_attention_heads
+        self.n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
+        self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+        self.H = cfg.hidden_size
+        self.L = max_cache_len
+        self.attn_fn = ALL_ATTENTION_FUNCTIONS.get_interface(cfg._attn_implementation, eager_attention_forward)
+        if attention not in ("sdpa", "hip"):
+            raise ValueError("attention: 'sdpa' or 'hip'")
+        if attention == "hip" and (self.hd not in (64, 128, 256) or getattr(cfg, "sliding_window", None) or getattr(cfg, "attn_logit_softcapping", None)
+                                   or max_cache_len > 30000):
+            raise ValueError("hqq_amd: the decode-attention kernel covers plain softmax attention with head_dim 64 / 128 / 256 and caches of <= 30000 positions")
+        self.attention = attention
+        if not supports_batch(model, B):
+            raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows (supports_batch)")
+        self.blocks = []
+        for li, (blk, (q, k, v, o, g, u, d)) in enumerate(zip(inner.layers, _decoder_linears(model))):
+            lay = cache.layers[li]
+            if not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (B, self.n_kv, max_cache_len, self.hd) or \
+                    not lay.keys.is_contiguous() or not lay.values.is_contiguous():
+                raise ValueError(f"hqq_amd: the batched decode step needs an initialised HF StaticCache of batch {B} and {max_cache_len} positions")
+            self.blocks.append({
+                "attn": blk.self_attn, "n1": blk.input_layernorm, "n2": blk.post_attention_layernorm,
+                "qkv": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (q, k, v)], "qkv_opts": FusedLlamaStep._gopts((q, k, v)), "qkv_nbits": q.nbits,
+                "qkv_gs": q.group_size, "o": o, "gu": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (g, u)], "gu_opts": FusedLlamaStep._gopts((g, u)),
+                "gu_nbits": g.nbits, "gu_gs": g.group_size, "d": d, "kc": lay.keys, "vc": lay.values,
+                # outputs of the launches (static addresses: the step is captured in a hipGraph)
+                "q": torch.empty(B, q.out_features, dtype=dt, device=dev), "k": torch.empty(B, k.out_features, dtype=dt, device=dev),
+                "v": torch.empty(B, v.out_features, dtype=dt, device=dev), "qr": torch.empty(B, self.n_heads, 1, self.hd, dtype=dt, device=dev),
+                "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
+                "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
+            })
+        self.h = torch.empty(B, self.H, dtype=dt, device=dev)
+        self.xn = torch.empty(B, self.H, dtype=dt, device=dev)
+        self.delta = torch.empty(B, self.H, dtype=dt, device=dev)
+        self.att = torch.empty(B, self.n_heads * self.hd, dtype=dt, device=dev)
+        self.attn_ws = {}
+        self.mask = torch.zeros(B, 1, 1, max_cache_len, dtype=dt, device=dev)   # one query per sequence, additive form
+        self.ar = torch.arange(max_cache_len, device=dev)
+        self.cos_tab = self.sin_tab = None   # (FusedLlamaStep's tables: rope types whose frequencies follow the sequence length keep the per-token call)
+        if getattr(inner.rotary_emb, "rope_type", "default") in ("default", "linear", "llama3", "yarn") and \
+                max_cache_len <= getattr(cfg, "max_position_embeddings", max_cache_len):
+            with torch.no_grad():
+                c, s_ = inner.rotary_emb(torch.empty(1, 1, self.H, dtype=dt, device=dev), self.ar.view(1, -1))
+            self.cos_tab, self.sin_tab = c[0].contiguous(), s_[0].contiguous()
+        self.zero = torch.zeros((), dtype=dt, device=dev)
+        self.ninf = torch.full((), float("-inf"), dtype=dt, device=dev)
+        emb = inner.embed_tokens
+        self.one_launch_front = bool(self.cos_tab is not None and type(emb) is torch.nn.Embedding and emb.max_norm is None and emb.weight.dtype == dt
+                                     and emb.weight.is_contiguous() and emb.weight.device == self.h.device and self.H % 8 == 0)
+        self.cos_v = torch.empty(B, self.hd, dtype=dt, device=dev)
+        self.sin_v = torch.empty(B, self.hd, dtype=dt, device=dev)
+
+    @torch.no_grad()
+    def __call__(self, tok: Tensor, pos: Tensor, kv_len: int | None = None) -> Tensor:
+        """tok [B, 1] int64, pos [B] int64 (each sequence's position; both on the device) -> logits [B, vocab].  kv_len (host integer > the LARGEST
+        position, default the whole cache): HF's attention function attends over that many cache positions (each row masked beyond its own
+        position); the kernel attention takes its split count from it"""
+        inner, B, h = self.inner, self.B, self.h
+        if self.one_launch_front:
+            ops.token_prologue_batched(tok, pos, inner.embed_tokens.weight, h, self.cos_tab, self.sin_tab, self.cos_v, self.sin_v,
+                                       None if self.attention == "hip" else self.mask.view(B, -1))
+            cos, sin = self.cos_v, self.sin_v
+        else:
+            h.copy_(inner.embed_tokens(tok).view(B, self.H))
+            if self.cos_tab is not None:
+                cos, sin = self.cos_tab.index_select(0, pos), self.sin_tab.index_select(0, pos)
+            else:
+                cos, sin = inner.rotary_emb(h.view(B, 1, self.H), pos.view(B, 1))   # [B, 1, hd] each, the model's own rotary module
+                cos, sin = cos.reshape(B, -1).contiguous(), sin.reshape(B, -1).contiguous()
+            if self.attention != "hip":
+                torch.where(self.ar.view(1, -1) <= pos.view(-1, 1), self.zero, self.ninf, out=self.mask.view(B, -1))
+        kvl = self.L if kv_len is None else min(int(kv_len), self.L)
+        mask = self.mask[..., :kvl]
+        splits = ops.attn_splits(kvl) if self.attention == "hip" else 1
+        if splits > 1 and splits not in self.attn_ws:
+            self.attn_ws[splits] = ops.attn_workspace_batched(self.device, B, self.n_heads, self.hd, splits)
+        delta = None
+        K = self.H
+        for b in self.blocks:
+            at = b["attn"]
+            ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
+            ops.gemv_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]], opts=b["qkv_opts"])
+            if self.attention == "hip":   # rotary + cache write + attention: one launch
+                att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
+                                                   workspace=self.attn_ws.get(splits))
+            else:
+                ops.rope_cache_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
+                att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :, :kvl], b["vc"][:, :, :kvl], mask, dropout=0.0, scaling=at.scaling)
+            o, d = b["o"], b["d"]
+            ops.gemv(att.reshape(B, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta,
+                     opts=ops.layer_opts(o.opts))
+            ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
+            ops.gemv_grouped(self.xn, b["gu"], K, b["gu_gs"], b["gu_nbits"], outs=[b["g"], b["u"]], opts=b["gu_opts"])
+            ops.silu_mul(b["g"], b["u"], out=b["a"])
+            ops.gemv(b["a"], d.W_q, d.scale, d.zero, None, d.out_features, d.in_features, d.group_size, d.nbits, out=self.delta, opts=ops.layer_opts(d.opts))
+            delta = self.delta
+        ops.add_rmsnorm(h, delta, inner.norm.weight, inner.norm.variance_epsilon, out=self.xn)
+        return self.model.lm_head(self.xn)

@@ -186,6 +186,11 @@ int hqq_hip_add_rmsnorm(void* h, const void* delta, const void* weight, float ep
 int hqq_hip_rope_cache(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, void* q_out, void* k_cache,
                        void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream);
 int hqq_hip_silu_mul(const void* gate, const void* up, void* out, int64_t n, int dtype, void* stream);
+/* hqq_hip_rope_cache for `batch` sequences (batch convention: hqq_hip_token_prologue_batched below): q / q_out [batch, n_heads, hd],
+ * k / v [batch, n_kv_heads, hd], cos / sin [batch, hd], caches [batch, n_kv_heads, cache_len, hd] (HF's StaticCache tensors of that batch), pos_dev
+ * int64[batch]; sequence b's key / value go to its own cache row at pos_dev[b]; a position outside [0, cache_len) writes nothing, as in the batch-1 call. */
+int hqq_hip_rope_cache_batched(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out,
+                               void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream);
 /* The per-token work either side of the decoder blocks (ABI 7; hqq/utils/generation_hf.py:405-540: embedding lookup, the rotary table's row, the causal mask of one query in
  * front; argmax, token hand-over, position increment behind) as ONE launch each — copies and compares only, bit-identical to the torch ops they replace:
  *   hqq_hip_token_prologue  h[H] = embed[*tok_dev]; cos / sin [head_dim] = cos_tab / sin_tab [L, head_dim] row *pos_dev (tables NULL: skipped);
@@ -194,6 +199,16 @@ int hqq_hip_silu_mul(const void* gate, const void* up, void* out, int64_t n, int
 int hqq_hip_token_prologue(const int64_t* tok_dev, const int64_t* pos_dev, const void* embed, int64_t vocab, int64_t H, const void* cos_tab, const void* sin_tab, int64_t L,
                            int64_t head_dim, void* h, void* cos, void* sin, void* mask, int dtype, void* stream);
 int hqq_hip_argmax_advance(const void* logits, int64_t n, int dtype, int64_t* next_tok_dev, int64_t* tok_dev, int64_t* pos_dev, void* stream);
+/* The same for a BATCH of `batch` independent sequences (1 <= batch <= 65535), one decode step of each — the glue of a batched decode step
+ * (hqq_amd.utils.llama_fused.FusedLlamaBatchStep).  tok_dev / pos_dev: int64[batch] on the device; every other tensor is dense and row-major per
+ * sequence.  Row b of each call gives exactly the bits the batch-1 call gives for sequence b alone (same kernel, same per-row arithmetic; the row is
+ * a grid index).  Argument checks as the batch-1 calls, plus batch; all of them before anything is launched.
+ *   hqq_hip_token_prologue_batched  hqq_hip_token_prologue per row: h [batch, H] = embed[tok[b]]; cos / sin [batch, head_dim] = the tables' row pos[b];
+ *                                   mask [batch, L] = i <= pos[b] ? 0 : -inf
+ *   hqq_hip_argmax_advance_batched  hqq_hip_argmax_advance per row, one workgroup each: logits [batch, n]; next_tok[b], tok[b] = the argmax of row b; pos[b] += 1 */
+int hqq_hip_token_prologue_batched(const int64_t* tok_dev, const int64_t* pos_dev, int64_t batch, const void* embed, int64_t vocab, int64_t H, const void* cos_tab,
+                                   const void* sin_tab, int64_t L, int64_t head_dim, void* h, void* cos, void* sin, void* mask, int dtype, void* stream);
+int hqq_hip_argmax_advance_batched(const void* logits, int64_t batch, int64_t n, int dtype, int64_t* next_tok_dev, int64_t* tok_dev, int64_t* pos_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The decoder block's launches with those steps FOLDED IN (ABI 6; csrc/gemv_block.hip): hqq_hip_gemv_grouped for ONE activation row whose
@@ -249,6 +264,17 @@ size_t hqq_hip_attn_decode_workspace_bytes(int64_t n_heads, int64_t head_dim, in
 int hqq_hip_rope_attn_decode(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, void* k_cache, void* v_cache,
                              void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* hqq_hip_attn_decode / hqq_hip_rope_attn_decode for `batch` sequences: q, k / v and out [batch, ...] of the batch-1 shapes, caches
+ * [batch, n_kv_heads, cache_len, head_dim], cos / sin [batch, head_dim], pos_dev int64[batch]; sequence b attends over its own first pos_dev[b] + 1
+ * keys.  `splits` holds for the whole launch (the caller picks it from the LARGEST position): a sequence with fewer visible keys than splits leaves
+ * the surplus shares empty (max -inf, sum 0), and the merging launch gives them weight 0 — as the batch-1 kernels already do (a share past the
+ * last key reads nothing).  workspace: hqq_hip_attn_decode_workspace_bytes(batch * n_heads, head_dim, splits) bytes. */
+int hqq_hip_attn_decode_batched(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, int64_t batch, void* out, int64_t n_heads,
+                                int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int hqq_hip_rope_attn_decode_batched(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* k_cache,
+                                     void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype,
+                                     int64_t splits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* workspace of hqq_hip_forward / hqq_hip_gemm for one layer at M rows (0 = none needed, workspace may be NULL): the decode kernels'
  * (hqq_hip_gemv_workspace_bytes) up to HQQ_GEMV_MAX_M_SKINNY rows, the split-K fused GEMM's fp32 partial tiles beyond.  Same contract. */
