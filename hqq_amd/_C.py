@@ -56,6 +56,7 @@ SYMBOLS = {
     "hqq_hip_gemm_workspace_bytes": (_sz, [_i32, _i64, _i64, _i64, _i64, _i32, _u32]),
     "hqq_hip_gemm_plan": (_i32, [_i32, _i64, _i64, _i64, _i64, _i32, _u32, _vp]),
     "hqq_hip_forward_prefers_fused": (_i32, [_i32, _i64, _i64, _i64, _i64, _i32]),
+    "hqq_hip_forward_route": (_i32, [_i32, _i32, _vp, _i64, _i64, _i64, _i32, _u32]),
     "hqq_hip_forward": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _sz, _vp]),
     # decode for layers quantised along axis 0 (csrc/gemv_axis0.hip)
     "hqq_hip_gemv_axis0_workspace_bytes": (_sz, [_i32, _i64, _i64, _i64, _i64, _i32]),

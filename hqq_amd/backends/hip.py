@@ -161,12 +161,14 @@ class _GroupedMember(nn.Module):
             return self.layer(x)
         layers = [m.layer for m in g.members]
         specs = [(L.W_q, L.scale, L.zero, L.bias, L.out_features) for L in layers]
-        if rows <= g.max_rows:
-            outs = ops.gemv_grouped(x, specs, self.in_features, layers[0].group_size, layers[0].nbits, opts=ops.layer_opts(g.opts))
-        elif g.gemm_rows and rows <= g.gemm_rows and ops.gemm_grouped_covers(x.dtype, [L.out_features for L in layers], rows, self.in_features, layers[0].group_size,
-                                                                             layers[0].nbits, ops.layer_opts(g.opts)):
-            # batched decode / speculative verification / short prompts: the group through ONE launch of the pipelined fused GEMM (round 6)
-            outs = ops.gemm_grouped(x, specs, self.in_features, layers[0].group_size, layers[0].nbits, opts=ops.layer_opts(g.opts))
+        K, gs, nbits, w3s = self.in_features, layers[0].group_size, layers[0].nbits, layers[0].w3s
+        if ops.route(x.dtype, rows, g.Ns, K, gs, nbits, g.opts & ops.OPT_W3S) in ops.DECODE_ROUTES:
+            outs = ops.gemv_grouped(x, specs, K, gs, nbits, opts=ops.layer_opts(g.opts))
+        elif ops.gemm_grouped_covers(x.dtype, g.Ns, rows, K, gs, nbits, ops.layer_opts(g.opts)) and \
+                all(ops.prefers_fused(x.dtype, rows, N, K, gs, nbits, w3s) for N in g.Ns):
+            # batched decode / speculative verification / short prompts: the group through ONE launch of the pipelined fused GEMM (round 6),
+            # up to the row count where ops.forward itself leaves the fused GEMM for dequantise + dense GEMM
+            outs = ops.gemm_grouped(x, specs, K, gs, nbits, opts=ops.layer_opts(g.opts))
         else:
             return self.layer(x)
         g.x, g.version, g.outs = x, ver, list(outs)
@@ -176,8 +178,7 @@ class _GroupedMember(nn.Module):
 
 class _GroupState:
     def __init__(self):
-        self.members, self.x, self.version, self.outs, self.max_rows, self.opts = [], None, -1, [], 4, 0
-        self.gemm_rows = 0   # > 0: batches up to this many rows take the grouped fused GEMM (hqq_hip_gemm_grouped); beyond, every layer its own route
+        self.members, self.x, self.version, self.outs, self.opts, self.Ns = [], None, -1, [], 0, ()
 
 
 def group_projections(parent: nn.Module, names) -> bool:
@@ -194,18 +195,10 @@ def group_projections(parent: nn.Module, names) -> bool:
     if L0.nbits == 3 and any(L.group_size != 64 for L in layers):
         return False
     state = _GroupState()
-    state.max_rows = 4 if (L0.nbits == 3 or L0.in_features % 64) else ops.GEMV_MAX_M   # (5..16 rows need K % 64 == 0)
-    if L0.nbits == 3 and not L0.w3s:   # long K: fewer rows of x fit the kernel's LDS staging (70B down_proj: 2)
-        while state.max_rows and not all(ops.decode_covers(torch.float16, state.max_rows, L.out_features, L.in_features, 64, 3) for L in layers):
-            state.max_rows -= 1
-        if not state.max_rows:
-            return False
-    if all(ops.skinny_covers(torch.float16, ops.SKINNY_MAX_M, L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for L in layers):
-        state.max_rows = ops.SKINNY_MAX_M   # decode with a batch: still one weight-streaming launch for the group
     state.opts = (ops.OPT_META_SCALABLE if all(L.opts & ops.OPT_META_SCALABLE for L in layers) else 0) | (ops.OPT_W3S if L0.w3s else 0)
-    # up to the row count where ops.forward itself leaves the fused GEMM for dequantise + dense GEMM (hqq_hip_forward_prefers_fused: 2560)
-    if ops.gemm_grouped_covers(torch.float16, [L.out_features for L in layers], 128, L0.in_features, L0.group_size, L0.nbits, state.opts):
-        state.gemm_rows = ops.FUSED_GEMM_MAX_M
+    state.Ns = tuple(L.out_features for L in layers)
+    if ops.route(torch.float16, 1, state.Ns, L0.in_features, L0.group_size, L0.nbits, state.opts & ops.OPT_W3S) not in ops.DECODE_ROUTES:
+        return False   # not even one row through the grouped decode launch
     for i, (n, L) in enumerate(zip(names, layers)):
         m = _GroupedMember(L, state, i)
         state.members.append(m)

@@ -422,29 +422,23 @@ static int launch_gemm_f16(const void* x, const void* Wq, const void* scale, con
 }
 
 // gemm_pipe.hip: the pipelined split-K kernel for the rows between decode and long prefill
-struct GpPlan;
-size_t gemm_pipe_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, uint32_t opts);
-bool gemm_pipe_covers(int nbits, int64_t M, int64_t N, int64_t K, int64_t gs, int dtype);
 bool gemm_pipe_wins(int nbits, int64_t M, int64_t N, int64_t K);
-bool skinny_covers(int nbits, int64_t M, int64_t K, int64_t group_size, const int64_t* N, int n_layers);   // skinny.hip
 void gemm_pipe_describe(int nbits, int64_t M, int64_t N, int64_t K, uint32_t opts, int out[8]);
 int gemm_pipe_run(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias, void* y,
                   int64_t M, int64_t N, int64_t K, int64_t gs, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes, hipStream_t st);
-size_t gemm_pipe_workspace_bytes_grouped(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, uint32_t opts);
 int gemm_pipe_run_grouped(int nbits, int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero, const void* const* bias,
                           void* const* y, const int64_t* N, int64_t M, int64_t K, int64_t gs, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes, hipStream_t st);
 
-// which fused GEMM serves a call: the pipelined kernel (gemm_pipe.hip) wherever it applies — it is ahead of the output-tile kernels
-// below at every M (0.8-1.14 PFLOP/s against 0.5-0.84 from 2048 rows on, 2-4x below 512) —, the output-tile kernels for the group sizes
-// and K it does not cover
-#ifndef GEMM_PIPE_MAX_M_VALUE
-#define GEMM_PIPE_MAX_M_VALUE (int64_t(1) << 40)
-#endif
-constexpr int64_t GEMM_PIPE_MAX_M = GEMM_PIPE_MAX_M_VALUE;
-static bool use_pipe(int nbits, int64_t M, int64_t N, int64_t K, int64_t gs, int dtype, uint32_t opts) {
-  if (opts & (HQQ_OPT_GEMM_REGTILE | HQQ_OPT_GEMM_CLASSIC)) return false;
-  if (nbits == 3 && !(opts & HQQ_OPT_W3S)) return false;   // (the reference's 3-bit container has no fused GEMM; the stream layout runs like a 4-bit layer)
-  return (M <= GEMM_PIPE_MAX_M || nbits == 8) && gemm_pipe_covers(nbits, M, N, K, gs, dtype);   // (8-bit: the only fused GEMM there is)
+// the shapes the output-tile kernels above cover (asked by the planner, gemv.hip): 0, or the refusal with its message set
+int gemm_tile_check(int nbits, int64_t N, int64_t K, int64_t group_size, int dtype) {
+  if (nbits != 4 && nbits != 2) { set_error("hqq_hip_gemm: nbits=%d not covered by the fused GEMM", nbits); return HQQ_ERR_UNSUPPORTED; }
+  const int per = 8 / nbits;
+  if (N % per || (N / per) % 4 || group_size % 16 || K % GB_K) {
+    set_error("hqq_hip_gemm: needs N %% %d == 0, K %% 64 == 0, group_size %% 16 == 0 (got N=%lld K=%lld gs=%lld)", 4 * per, (long long)N, (long long)K, (long long)group_size);
+    return HQQ_ERR_UNSUPPORTED;
+  }
+  if (dtype != HQQ_F16) { set_error("hqq_hip_gemm: dtype %d not covered (fp16 only for now)", dtype); return HQQ_ERR_UNSUPPORTED; }
+  return 0;
 }
 
 }  // namespace hqq
@@ -454,25 +448,19 @@ using namespace hqq;
 extern "C" {
 
 size_t hqq_hip_gemm_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
-  if (M < 1 || N <= 0 || K <= 0 || group_size <= 0) return 0;
-  return use_pipe(nbits, M, N, K, group_size, dtype, opts) ? gemm_pipe_workspace_bytes(nbits, M, N, K, opts) : 0;
+  const int route = plan_route(PLAN_GEMM, nbits, 1, &N, M, K, group_size, dtype, opts);
+  return route < 0 ? 0 : route_workspace_bytes(route, nbits, 1, &N, M, K, group_size, dtype, opts);
 }
 
 size_t hqq_hip_forward_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
-  if (M < 1 || N <= 0 || K <= 0 || group_size <= 0) return 0;
-  // (the same test as hqq_hip_forward's dispatch)
-  if (M <= (nbits == 3 ? 4 : HQQ_GEMV_MAX_M)) return hqq_hip_gemv_workspace_bytes(nbits, 1, &N, M, K, group_size, dtype, opts);
-  const bool w3s = nbits == 3 && (opts & HQQ_OPT_W3S);   // the 3-bit stream layout: two row slabs per packed row, served like a 4-bit layer
-  if (M <= HQQ_GEMV_MAX_M_SKINNY && (dtype == HQQ_F16 || dtype == HQQ_BF16) && (nbits == 8 || nbits == 4 || nbits == 2 || w3s) && group_size == 64 && K % 256 == 0 && K >= 512 &&
-      N % (w3s ? 2 : 8 / nbits) == 0)
-    return hqq_hip_gemv_workspace_bytes(nbits, 1, &N, M, K, group_size, dtype, opts);
-  return hqq_hip_gemm_workspace_bytes(nbits, M, N, K, group_size, dtype, opts);
+  const int route = plan_route(PLAN_FORWARD, nbits, 1, &N, M, K, group_size, dtype, opts);
+  return route < 0 ? 0 : route_workspace_bytes(route, nbits, 1, &N, M, K, group_size, dtype, opts);
 }
 
 int hqq_hip_gemm_plan(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, int* out8) {
   if (!out8) return HQQ_ERR_SHAPE;
   for (int i = 0; i < 8; ++i) out8[i] = 0;
-  if (M < 1 || N <= 0 || K <= 0 || group_size <= 0 || !use_pipe(nbits, M, N, K, group_size, dtype, opts)) return HQQ_ERR_UNSUPPORTED;
+  if (plan_route(PLAN_GEMM, nbits, 1, &N, M, K, group_size, dtype, opts) != HQQ_ROUTE_GEMM_PIPE) return HQQ_ERR_UNSUPPORTED;
   gemm_pipe_describe(nbits, M, N, K, opts, out8);
   return 0;
 }
@@ -480,28 +468,22 @@ int hqq_hip_gemm_plan(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_
 int hqq_hip_forward_prefers_fused(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype) {
   if (M < 1 || N <= 0 || K <= 0 || group_size <= 0) return 0;
   if (M <= HQQ_GEMV_MAX_M) return 1;          // decode: always the weight-streaming kernels (hqq_hip_gemv reports what it does not cover)
-  if (nbits == 3) return 0;   // the reference's 3-bit container has no fused kernel beyond the decode rows; a layer in the stream layout asks with nbits = 4 (same kernels, same plan)
-  if (M <= HQQ_GEMV_MAX_M_SKINNY && (dtype == HQQ_F16 || dtype == HQQ_BF16) && skinny_covers(nbits, M, K, group_size, &N, 1)) return 1;
-  return gemm_pipe_covers(nbits, M, N, K, group_size, dtype) && gemm_pipe_wins(nbits, M, N, K) ? 1 : 0;
+  // beyond: the skinny GEMM where it applies, the pipelined GEMM where it is measured ahead (the output-tile kernels never are)
+  const int route = plan_route(PLAN_FORWARD, nbits, 1, &N, M, K, group_size, dtype, 0);
+  return route == HQQ_ROUTE_SKINNY || (route == HQQ_ROUTE_GEMM_PIPE && gemm_pipe_wins(nbits, M, N, K)) ? 1 : 0;
 }
 
 int hqq_hip_gemm(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias,
                  void* y, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes,
                  void* stream) {
   clear_stale_error();
-  if (opts & ~HQQ_OPT_ALL) { set_error("hqq_hip_gemm: unknown option bits 0x%x", opts & ~HQQ_OPT_ALL); return HQQ_ERR_SHAPE; }
-  if (M < 1 || N <= 0 || K <= 0 || group_size <= 0 || K % group_size) { set_error("hqq_hip_gemm: bad M/N/K/group_size"); return HQQ_ERR_SHAPE; }
+  const int route = plan_route(PLAN_GEMM, nbits, 1, &N, M, K, group_size, dtype, opts);
+  if (route < 0) return route;
   if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || N * (K / group_size) > INT32_MAX) { set_error("hqq_hip_gemm: size overflow"); return HQQ_ERR_SHAPE; }
   if (!aligned16(x) || !aligned16(Wq) || !aligned16(y)) { set_error("hqq_hip_gemm: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
   hipStream_t st = as_stream(stream);
-  if (use_pipe(nbits, M, N, K, group_size, dtype, opts)) return gemm_pipe_run(nbits, x, Wq, scale, zero, bias, y, M, N, K, group_size, dtype, opts, workspace, workspace_bytes, st);
-  if (nbits != 4 && nbits != 2) { set_error("hqq_hip_gemm: nbits=%d not covered by the fused GEMM", nbits); return HQQ_ERR_UNSUPPORTED; }
+  if (route == HQQ_ROUTE_GEMM_PIPE) return gemm_pipe_run(nbits, x, Wq, scale, zero, bias, y, M, N, K, group_size, dtype, opts, workspace, workspace_bytes, st);
   const int per = 8 / nbits;
-  if (N % per || (N / per) % 4 || group_size % 16 || K % GB_K) {
-    set_error("hqq_hip_gemm: needs N %% %d == 0, K %% 64 == 0, group_size %% 16 == 0 (got N=%lld K=%lld gs=%lld)", 4 * per, (long long)N, (long long)K, (long long)group_size);
-    return HQQ_ERR_UNSUPPORTED;
-  }
-  if (dtype != HQQ_F16) { set_error("hqq_hip_gemm: dtype %d not covered (fp16 only for now)", dtype); return HQQ_ERR_UNSUPPORTED; }
   const int m = static_cast<int>(M), n = static_cast<int>(N), k = static_cast<int>(K), gs = static_cast<int>(group_size);
   // opt-in (HQQ_OPT_GEMM_REGTILE): register-tile kernel (weights never touch LDS).  Round-1 status: correct, 0.62-0.81 PFLOP/s — level
   // with the LDS-staged kernels below (0.65-0.83), not ahead; PMC: waves stall on issue 33 % and wait 45 % of their cycles.
@@ -514,51 +496,37 @@ int hqq_hip_gemm(int nbits, const void* x, const void* Wq, const void* scale, co
 }
 
 // A group of layers that read the same x (q | k | v, gate | up) through ONE launch of the pipelined fused GEMM (+ one split-K reduce): ABI 8
-static bool group_on_pipe(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
-  if (!N || n_layers < 1 || n_layers > HQQ_GEMV_MAX_GROUP || M < 1 || K <= 0 || group_size <= 0) return false;
-  for (int i = 0; i < n_layers; ++i)
-    if (N[i] <= 0 || !use_pipe(nbits, M, N[i], K, group_size, dtype, opts)) return false;
-  return true;
-}
 int hqq_hip_gemm_grouped_covers(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
-  return group_on_pipe(nbits, n_layers, N, M, K, group_size, dtype, opts) ? 1 : 0;
+  return plan_route(PLAN_GEMM_GROUPED, nbits, n_layers, N, M, K, group_size, dtype, opts) == HQQ_ROUTE_GEMM_PIPE ? 1 : 0;
 }
 size_t hqq_hip_gemm_grouped_workspace_bytes(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
-  return group_on_pipe(nbits, n_layers, N, M, K, group_size, dtype, opts) ? gemm_pipe_workspace_bytes_grouped(nbits, n_layers, N, M, K, opts) : 0;
+  const int route = plan_route(PLAN_GEMM_GROUPED, nbits, n_layers, N, M, K, group_size, dtype, opts);
+  return route < 0 ? 0 : route_workspace_bytes(route, nbits, n_layers, N, M, K, group_size, dtype, opts);
 }
 int hqq_hip_gemm_grouped(int nbits, int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero, const void* const* bias,
                          void* const* y, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes,
                          void* stream) {
   clear_stale_error();
-  if (opts & ~HQQ_OPT_ALL) { set_error("hqq_hip_gemm_grouped: unknown option bits 0x%x", opts & ~HQQ_OPT_ALL); return HQQ_ERR_SHAPE; }
-  if (n_layers < 1 || n_layers > HQQ_GEMV_MAX_GROUP) { set_error("hqq_hip_gemm_grouped: n_layers=%d outside [1,%d]", n_layers, HQQ_GEMV_MAX_GROUP); return HQQ_ERR_SHAPE; }
-  if (!x || !Wq || !scale || !zero || !y || !N) { set_error("hqq_hip_gemm_grouped: null argument"); return HQQ_ERR_SHAPE; }
-  if (M < 1 || K <= 0 || group_size <= 0 || K % group_size) { set_error("hqq_hip_gemm_grouped: bad M/K/group_size"); return HQQ_ERR_SHAPE; }
+  const int route = plan_route(PLAN_GEMM_GROUPED, nbits, n_layers, N, M, K, group_size, dtype, opts);
+  if (route < 0) return route;
+  if (!x || !Wq || !scale || !zero || !y) { set_error("hqq_hip_gemm_grouped: null argument"); return HQQ_ERR_SHAPE; }
   if (M > INT32_MAX || K > INT32_MAX) { set_error("hqq_hip_gemm_grouped: size overflow"); return HQQ_ERR_SHAPE; }
   int64_t ntot = 0;
   for (int i = 0; i < n_layers; ++i) {
-    if (N[i] <= 0 || N[i] > INT32_MAX || N[i] * (K / group_size) > INT32_MAX) { set_error("hqq_hip_gemm_grouped: bad N / size overflow"); return HQQ_ERR_SHAPE; }
+    if (N[i] > INT32_MAX || N[i] * (K / group_size) > INT32_MAX) { set_error("hqq_hip_gemm_grouped: bad N / size overflow"); return HQQ_ERR_SHAPE; }
     if (!Wq[i] || !scale[i] || !zero[i] || !y[i]) { set_error("hqq_hip_gemm_grouped: null layer pointer"); return HQQ_ERR_SHAPE; }
     if (!aligned16(Wq[i]) || !aligned16(y[i])) { set_error("hqq_hip_gemm_grouped: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
     ntot += N[i];
   }
   if (!aligned16(x)) { set_error("hqq_hip_gemm_grouped: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
   if (ntot > INT32_MAX) { set_error("hqq_hip_gemm_grouped: size overflow"); return HQQ_ERR_SHAPE; }
-  if (!group_on_pipe(nbits, n_layers, N, M, K, group_size, dtype, opts)) {
-    set_error("hqq_hip_gemm_grouped: every layer of the group must be served by the pipelined fused GEMM (fp16 / bf16, nbits 8 / 4 / 2 or the 3-bit stream layout, group_size 64, K %% 128 == 0)");
-    return HQQ_ERR_UNSUPPORTED;
-  }
   return gemm_pipe_run_grouped(nbits, n_layers, x, Wq, scale, zero, bias, y, N, M, K, group_size, dtype, opts, workspace, workspace_bytes, as_stream(stream));
 }
 
 int hqq_hip_forward(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias,
                     void* y, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes,
                     void* stream) {
-  if (M >= 1 && M <= (nbits == 3 ? 4 : HQQ_GEMV_MAX_M)) return hqq_hip_gemv(nbits, x, Wq, scale, zero, bias, y, M, N, K, group_size, dtype, opts, workspace, workspace_bytes, stream);
-  // a batch of 17..64 rows is still weight-streaming work: the skinny-GEMM kernel where it applies (same conditions as skinny_covers)
-  const bool w3s = nbits == 3 && (opts & HQQ_OPT_W3S);
-  if (M <= HQQ_GEMV_MAX_M_SKINNY && (dtype == HQQ_F16 || dtype == HQQ_BF16) && (nbits == 8 || nbits == 4 || nbits == 2 || w3s) && group_size == 64 && K % 256 == 0 && K >= 512 &&
-      N % (w3s ? 2 : 8 / nbits) == 0)
+  if (forward_on_decode(nbits, 1, &N, M, K, group_size, dtype, opts))
     return hqq_hip_gemv(nbits, x, Wq, scale, zero, bias, y, M, N, K, group_size, dtype, opts, workspace, workspace_bytes, stream);
   return hqq_hip_gemm(nbits, x, Wq, scale, zero, bias, y, M, N, K, group_size, dtype, opts, workspace, workspace_bytes, stream);
 }

@@ -660,8 +660,6 @@ size_t gemm_pipe_workspace_bytes_grouped(int nbits, int n_layers, const int64_t*
 // Against the other prefill route, hqq_hip_dequantize + hqq_hip_gemm_dense (rebuild the weights once, stream them as fp16): this kernel rebuilds
 // every weight once per 256-token tile and is ahead while that is a few times — to ~2000 tokens on the 7B shapes, level at 3072, behind from
 // 4096 (profiles/r04_prefill_routes_int4.txt; the dense kernel's 256 x 256 tiles also leave CUs idle below ~2000 tokens)
-size_t gemm_pipe_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, uint32_t opts) { return gemm_pipe_workspace_bytes_grouped(nbits, 1, &N, M, K, opts); }
-
 bool gemm_pipe_wins(int nbits, int64_t M, int64_t N, int64_t K) {
   (void)nbits; (void)N; (void)K;
   return M <= 2560;

@@ -231,12 +231,115 @@ size_t skinny_workspace_bytes(int nbits, int n_layers, const int64_t* N, int64_t
 int skinny_run(int nbits, int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero,
                const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int dtype, uint32_t opts, void* ws, size_t ws_bytes,
                hipStream_t st);
+int gemv_w3s_check(int n_layers, const int64_t* N, int64_t K, int64_t group_size);
 int gemv_w3s_run(int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero, const void* const* bias,
-                 void* const* y, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts, hipStream_t st);
-size_t gemv3_workspace_bytes(int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, uint32_t opts);
-int gemv3_run(int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero,
-              const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int64_t group_size, uint32_t opts,
-              void* ws, size_t ws_bytes, hipStream_t st);
+                 void* const* y, const int64_t* N, int64_t M, int64_t K, int dtype, uint32_t opts, hipStream_t st);
+int gemv3_route(int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, uint32_t opts);
+size_t gemv3s_workspace_bytes(int n_layers, const int64_t* N, int64_t M, int64_t K);
+int gemv3_run(bool slabs, int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero,
+              const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, uint32_t opts, void* ws, size_t ws_bytes,
+              hipStream_t st);
+bool gemm_pipe_covers(int nbits, int64_t M, int64_t N, int64_t K, int64_t gs, int dtype);
+size_t gemm_pipe_workspace_bytes_grouped(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, uint32_t opts);
+int gemm_tile_check(int nbits, int64_t N, int64_t K, int64_t group_size, int dtype);
+
+// ---- the planner: which kernel serves a call (include/hqq_hip.h, routes).  Each kernel's own shape test stays with the kernel; the choice
+// between them is made here and nowhere else.  The entry points add only their pointer and 32-bit offset checks.
+static bool fp16_or_bf16(int dtype) { return dtype == HQQ_F16 || dtype == HQQ_BF16; }
+
+// hqq_hip_gemv / hqq_hip_gemv_grouped
+static int plan_gemv(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
+  if (opts & ~HQQ_OPT_ALL) { set_error("hqq_hip_gemv: unknown option bits 0x%x", opts & ~HQQ_OPT_ALL); return HQQ_ERR_SHAPE; }
+  if (n_layers < 1 || n_layers > HQQ_GEMV_MAX_GROUP) { set_error("hqq_hip_gemv_grouped: n_layers=%d outside [1,%d]", n_layers, HQQ_GEMV_MAX_GROUP); return HQQ_ERR_SHAPE; }
+  if ((opts & HQQ_OPT_W3S) && nbits != 3) { set_error("hqq_hip_gemv: HQQ_OPT_W3S is a 3-bit layout (nbits=%d)", nbits); return HQQ_ERR_SHAPE; }
+  const bool w3s = nbits == 3 && (opts & HQQ_OPT_W3S);   // the 3-bit stream layout runs through the 4-bit container's kernels (w3s.h)
+  // 17..64 activation rows: only where the skinny-GEMM kernel (skinny.hip) applies
+  const bool skinny_ok = N && fp16_or_bf16(dtype) && skinny_covers(w3s ? 4 : nbits, M, K, group_size, N, n_layers);
+  if (M < 1 || M > (skinny_ok ? HQQ_GEMV_MAX_M_SKINNY : HQQ_GEMV_MAX_M)) {
+    set_error("hqq_hip_gemv: M=%lld outside [1,%d] (up to %d for fp16, 8-/4-/2-bit, group_size 64, K %% 256 == 0)", (long long)M, HQQ_GEMV_MAX_M, HQQ_GEMV_MAX_M_SKINNY);
+    return HQQ_ERR_SHAPE;
+  }
+  if (K <= 0 || group_size <= 0 || K % group_size) { set_error("hqq_hip_gemv: bad K/group_size"); return HQQ_ERR_SHAPE; }
+  if (!N) { set_error("hqq_hip_gemv: null argument"); return HQQ_ERR_SHAPE; }
+  if (w3s) {
+    if (!fp16_or_bf16(dtype)) { set_error("hqq_hip_gemv: dtype %d not covered (fp16 / bf16)", dtype); return HQQ_ERR_UNSUPPORTED; }
+    if (M <= GV_EXACT_ROWWISE_MAX_M) { const int rc = gemv_w3s_check(n_layers, N, K, group_size); return rc ? rc : HQQ_ROUTE_ROWWISE_W3S; }
+    if (!skinny_ok) { set_error("hqq_hip_gemv: 3-bit stream layout: M=%lld beyond %d rows needs group_size 64, K %% 256 == 0, K >= 512", (long long)M, GV_EXACT_ROWWISE_MAX_M); return HQQ_ERR_UNSUPPORTED; }
+    return HQQ_ROUTE_SKINNY;
+  }
+  if (nbits == 3) {   // int32 containers, ten slabs: its own kernels (gemv3.hip, gemv3s.hip), fp16, exact weights
+    if (dtype != HQQ_F16) { set_error("hqq_hip_gemv: the fused 3-bit kernel covers fp16 (got dtype %d)", dtype); return HQQ_ERR_UNSUPPORTED; }
+    return gemv3_route(n_layers, N, M, K, group_size, opts);
+  }
+  if (nbits != 4 && nbits != 2 && nbits != 8 && nbits != 1) { set_error("hqq_hip_gemv: nbits=%d not covered by the fused GEMV", nbits); return HQQ_ERR_UNSUPPORTED; }
+  if (!fp16_or_bf16(dtype)) { set_error("hqq_hip_gemv: dtype %d not covered (fp16 / bf16)", dtype); return HQQ_ERR_UNSUPPORTED; }
+  if (dtype == HQQ_BF16 && !skinny_ok && (M > GV_EXACT_ROWWISE_MAX_M || (nbits != 4 && nbits != 2))) {
+    set_error("hqq_hip_gemv: bf16 covers nbits 4/2 and M <= %d (got nbits=%d M=%lld)", GV_EXACT_ROWWISE_MAX_M, nbits, (long long)M);
+    return HQQ_ERR_UNSUPPORTED;
+  }
+  if (group_size % 16 || K % 16) { set_error("hqq_hip_gemv: needs group_size %% 16 == 0 (got gs=%lld)", (long long)group_size); return HQQ_ERR_UNSUPPORTED; }
+  const int per = 8 / nbits;
+  const bool exact = !(opts & HQQ_OPT_FACTORED) || dtype == HQQ_BF16;
+  // more activation rows than the row-per-wave kernel contracts cheaply (FACTORED: it serves M <= 8 per launch): the skinny kernel, else the
+  // 16-row-tile MFMA kernel (needs K % 64 == 0)
+  const bool tiled = exact ? M > GV_EXACT_ROWWISE_MAX_M : (M > 8 && skinny_ok);
+  if (tiled && K % 64) { set_error("hqq_hip_gemv: M=%lld > %d needs K %% 64 == 0 (got K=%lld)", (long long)M, GV_EXACT_ROWWISE_MAX_M, (long long)K); return HQQ_ERR_UNSUPPORTED; }
+  if (!tiled && max_m_per_launch(K) < 1) { set_error("hqq_hip_gemv: K=%lld too large to stage one row of x in LDS", (long long)K); return HQQ_ERR_UNSUPPORTED; }
+  for (int i = 0; i < n_layers; ++i)
+    if (N[i] <= 0 || N[i] % per) { set_error("hqq_hip_gemv: needs N %% %d == 0 (got N=%lld)", per, (long long)N[i]); return N[i] <= 0 ? HQQ_ERR_SHAPE : HQQ_ERR_UNSUPPORTED; }
+  return !tiled ? HQQ_ROUTE_ROWWISE : skinny_ok ? HQQ_ROUTE_SKINNY : HQQ_ROUTE_MFMA16;
+}
+
+// hqq_hip_gemm / hqq_hip_gemm_grouped: the pipelined kernel (gemm_pipe.hip) wherever it applies — it is ahead of the output-tile kernels
+// (gemm.hip) at every M (0.8-1.14 PFLOP/s against 0.5-0.84 from 2048 rows on, 2-4x below 512) —, the output-tile kernels for the group sizes
+// and K it does not cover; a group only on the pipelined kernel, in one launch
+static int plan_gemm(bool grouped, int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
+  const char* who = grouped ? "hqq_hip_gemm_grouped" : "hqq_hip_gemm";
+  if (opts & ~HQQ_OPT_ALL) { set_error("%s: unknown option bits 0x%x", who, opts & ~HQQ_OPT_ALL); return HQQ_ERR_SHAPE; }
+  if (grouped) {
+    if (n_layers < 1 || n_layers > HQQ_GEMV_MAX_GROUP) { set_error("%s: n_layers=%d outside [1,%d]", who, n_layers, HQQ_GEMV_MAX_GROUP); return HQQ_ERR_SHAPE; }
+    if (!N) { set_error("%s: null argument", who); return HQQ_ERR_SHAPE; }
+    if (M < 1 || K <= 0 || group_size <= 0 || K % group_size) { set_error("%s: bad M/K/group_size", who); return HQQ_ERR_SHAPE; }
+    for (int i = 0; i < n_layers; ++i)
+      if (N[i] <= 0) { set_error("%s: bad N / size overflow", who); return HQQ_ERR_SHAPE; }
+  } else if (M < 1 || N[0] <= 0 || K <= 0 || group_size <= 0 || K % group_size) {
+    set_error("%s: bad M/N/K/group_size", who);
+    return HQQ_ERR_SHAPE;
+  }
+  bool pipe = !(opts & (HQQ_OPT_GEMM_REGTILE | HQQ_OPT_GEMM_CLASSIC)) && (nbits != 3 || (opts & HQQ_OPT_W3S));   // (no fused GEMM for the 3-bit container)
+  for (int i = 0; i < n_layers; ++i) pipe = pipe && gemm_pipe_covers(nbits, M, N[i], K, group_size, dtype);
+  if (pipe) return HQQ_ROUTE_GEMM_PIPE;
+  if (grouped) {
+    set_error("%s: every layer of the group must be served by the pipelined fused GEMM (fp16 / bf16, nbits 8 / 4 / 2 or the 3-bit stream layout, group_size 64, K %% 128 == 0)", who);
+    return HQQ_ERR_UNSUPPORTED;
+  }
+  const int rc = gemm_tile_check(nbits, N[0], K, group_size, dtype);
+  return rc ? rc : HQQ_ROUTE_GEMM_TILE;
+}
+
+bool forward_on_decode(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
+  if (M >= 1 && M <= (nbits == 3 ? GV_EXACT_ROWWISE_MAX_M : HQQ_GEMV_MAX_M)) return true;
+  // a batch of 17..64 rows (3-bit: 5..64) is still weight-streaming work where the skinny-GEMM kernel applies
+  const bool w3s = nbits == 3 && (opts & HQQ_OPT_W3S);
+  return (nbits != 3 || w3s) && fp16_or_bf16(dtype) && skinny_covers(w3s ? 4 : nbits, M, K, group_size, N, n_layers);
+}
+
+int plan_route(PlanEntry entry, int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
+  if (entry == PLAN_FORWARD)
+    entry = !N || n_layers < 1 || n_layers > HQQ_GEMV_MAX_GROUP || forward_on_decode(nbits, n_layers, N, M, K, group_size, dtype, opts) ? PLAN_GEMV
+                                                                                                                                      : n_layers == 1 ? PLAN_GEMM : PLAN_GEMM_GROUPED;
+  if (entry == PLAN_GEMV) return plan_gemv(nbits, n_layers, N, M, K, group_size, dtype, opts);
+  return plan_gemm(entry == PLAN_GEMM_GROUPED, nbits, entry == PLAN_GEMM ? 1 : n_layers, N, M, K, group_size, dtype, opts);
+}
+
+size_t route_workspace_bytes(int route, int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
+  switch (route) {
+    case HQQ_ROUTE_SKINNY: return skinny_workspace_bytes(nbits, n_layers, N, M, K, opts);
+    case HQQ_ROUTE_GEMV3_SLABS: return gemv3s_workspace_bytes(n_layers, N, M, K);
+    case HQQ_ROUTE_GEMM_PIPE: return gemm_pipe_workspace_bytes_grouped(nbits, n_layers, N, M, K, opts);
+  }
+  return 0;
+}
 
 // hqq_hip_meta_check: groups whose (zero, scale) cannot take the three-op weight rebuild (decode_common.h, SlabExact<.., SUB>):
 // z 2^-J must be exact in fp16, s 2^J finite, |z| <= 2^15 (then q - z cannot overflow either), J = 9 - shift of the row's slab.
@@ -287,87 +390,33 @@ extern "C" int hqq_hip_gemv_grouped(int nbits, int n_layers, const void* x, cons
                                     int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes,
                                     void* stream) {
   clear_stale_error();
-  if (opts & ~HQQ_OPT_ALL) { set_error("hqq_hip_gemv: unknown option bits 0x%x", opts & ~HQQ_OPT_ALL); return HQQ_ERR_SHAPE; }
-  if (n_layers < 1 || n_layers > HQQ_GEMV_MAX_GROUP) { set_error("hqq_hip_gemv_grouped: n_layers=%d outside [1,%d]", n_layers, HQQ_GEMV_MAX_GROUP); return HQQ_ERR_SHAPE; }
-  // 17..64 activation rows: only where the skinny-GEMM kernel (skinny.hip) applies
-  if ((opts & HQQ_OPT_W3S) && nbits != 3) { set_error("hqq_hip_gemv: HQQ_OPT_W3S is a 3-bit layout (nbits=%d)", nbits); return HQQ_ERR_SHAPE; }
-  const bool w3s = nbits == 3 && (opts & HQQ_OPT_W3S);   // the 3-bit stream layout runs through the 4-bit container's kernels (w3s.h)
-  const bool skinny_ok = (N && (dtype == HQQ_F16 || dtype == HQQ_BF16) && skinny_covers(w3s ? 4 : nbits, M, K, group_size, N, n_layers));
-  if (M < 1 || M > (skinny_ok ? HQQ_GEMV_MAX_M_SKINNY : HQQ_GEMV_MAX_M)) {
-    set_error("hqq_hip_gemv: M=%lld outside [1,%d] (up to %d for fp16, 8-/4-/2-bit, group_size 64, K %% 256 == 0)", (long long)M, HQQ_GEMV_MAX_M, HQQ_GEMV_MAX_M_SKINNY);
-    return HQQ_ERR_SHAPE;
+  const int route = plan_gemv(nbits, n_layers, N, M, K, group_size, dtype, opts);
+  if (route < 0) return route;
+  if (!x || !Wq || !scale || !zero || !y) { set_error("hqq_hip_gemv: null argument"); return HQQ_ERR_SHAPE; }
+  if (!aligned16(x)) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
+  hipStream_t st = as_stream(stream);
+  switch (route) {
+    case HQQ_ROUTE_ROWWISE_W3S: return gemv_w3s_run(n_layers, x, Wq, scale, zero, bias, y, N, M, K, dtype, opts, st);
+    case HQQ_ROUTE_GEMV3_ROWS:
+    case HQQ_ROUTE_GEMV3_SLABS: return gemv3_run(route == HQQ_ROUTE_GEMV3_SLABS, n_layers, x, Wq, scale, zero, bias, y, N, M, K, opts, workspace, workspace_bytes, st);
   }
-  if (K <= 0 || group_size <= 0 || K % group_size) { set_error("hqq_hip_gemv: bad K/group_size"); return HQQ_ERR_SHAPE; }
-  if (w3s) {
-    if (dtype != HQQ_F16 && dtype != HQQ_BF16) { set_error("hqq_hip_gemv: dtype %d not covered (fp16 / bf16)", dtype); return HQQ_ERR_UNSUPPORTED; }
-    if (!x || !Wq || !scale || !zero || !y || !N) { set_error("hqq_hip_gemv: null argument"); return HQQ_ERR_SHAPE; }
-    if (!aligned16(x)) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
-    if (M <= GV_EXACT_ROWWISE_MAX_M) return gemv_w3s_run(n_layers, x, Wq, scale, zero, bias, y, N, M, K, group_size, dtype, opts, as_stream(stream));
-    if (!skinny_ok) { set_error("hqq_hip_gemv: 3-bit stream layout: M=%lld beyond %d rows needs group_size 64, K %% 256 == 0, K >= 512", (long long)M, GV_EXACT_ROWWISE_MAX_M); return HQQ_ERR_UNSUPPORTED; }
-    for (int i = 0; i < n_layers; ++i) {
-      if (N[i] <= 0 || N[i] % 2) { set_error("hqq_hip_gemv: needs N %% 2 == 0 (got N=%lld)", (long long)N[i]); return N[i] <= 0 ? HQQ_ERR_SHAPE : HQQ_ERR_UNSUPPORTED; }
-      if (N[i] * (K / group_size) > INT32_MAX) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
-      if (!Wq[i] || !scale[i] || !zero[i] || !y[i]) { set_error("hqq_hip_gemv: null layer pointer"); return HQQ_ERR_SHAPE; }
-      if (!aligned16(Wq[i])) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
-    }
-    return skinny_run(3, n_layers, x, Wq, scale, zero, bias, y, N, M, K, dtype, opts, workspace, workspace_bytes, as_stream(stream));
-  }
-  if (nbits == 3) {   // int32 containers, ten slabs: its own kernel (gemv3.hip), fp16, exact weights
-    if (dtype != HQQ_F16) { set_error("hqq_hip_gemv: the fused 3-bit kernel covers fp16 (got dtype %d)", dtype); return HQQ_ERR_UNSUPPORTED; }
-    if (!x || !Wq || !scale || !zero || !y || !N) { set_error("hqq_hip_gemv: null argument"); return HQQ_ERR_SHAPE; }
-    if (!aligned16(x)) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
-    return gemv3_run(n_layers, x, Wq, scale, zero, bias, y, N, M, K, group_size, opts, workspace, workspace_bytes, as_stream(stream));
-  }
-  if (nbits != 4 && nbits != 2 && nbits != 8 && nbits != 1) { set_error("hqq_hip_gemv: nbits=%d not covered by the fused GEMV", nbits); return HQQ_ERR_UNSUPPORTED; }
-  if (dtype != HQQ_F16 && dtype != HQQ_BF16) { set_error("hqq_hip_gemv: dtype %d not covered (fp16 / bf16)", dtype); return HQQ_ERR_UNSUPPORTED; }
-  if (dtype == HQQ_BF16 && !skinny_ok && (M > GV_EXACT_ROWWISE_MAX_M || (nbits != 4 && nbits != 2))) {
-    set_error("hqq_hip_gemv: bf16 covers nbits 4/2 and M <= %d (got nbits=%d M=%lld)", GV_EXACT_ROWWISE_MAX_M, nbits, (long long)M);
-    return HQQ_ERR_UNSUPPORTED;
-  }
-  if (!x || !Wq || !scale || !zero || !y || !N) { set_error("hqq_hip_gemv: null argument"); return HQQ_ERR_SHAPE; }
-  const int per = 8 / nbits;
-  if (group_size % 16 || K % 16) { set_error("hqq_hip_gemv: needs group_size %% 16 == 0 (got gs=%lld)", (long long)group_size); return HQQ_ERR_UNSUPPORTED; }
+  // the skinny, MFMA-16 and row-per-wave kernels address a layer with 32-bit offsets from its base pointers
+  const int per = nbits == 3 ? 2 : 8 / nbits;   // (packed rows: the stream layout holds two row slabs like the 4-bit container)
   if (K > INT32_MAX / 2) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
+  for (int i = 0; i < n_layers; ++i) {
+    if (N[i] * (K / group_size) > INT32_MAX || (route == HQQ_ROUTE_ROWWISE && (N[i] / per) * K > static_cast<int64_t>(UINT32_MAX))) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
+    if (!Wq[i] || !scale[i] || !zero[i] || !y[i]) { set_error("hqq_hip_gemv: null layer pointer"); return HQQ_ERR_SHAPE; }
+    if (!aligned16(Wq[i])) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
+  }
+  if (route == HQQ_ROUTE_SKINNY) return skinny_run(nbits, n_layers, x, Wq, scale, zero, bias, y, N, M, K, dtype, opts, workspace, workspace_bytes, st);
+  if (route == HQQ_ROUTE_MFMA16) return gemv_mfma_run(nbits, n_layers, x, Wq, scale, zero, bias, y, N, M, K, group_size, st);
+  // HQQ_ROUTE_ROWWISE
   const bool exact = !(opts & HQQ_OPT_FACTORED) || dtype == HQQ_BF16;
-  if (n_layers > 1 && !skinny_ok && (dtype == HQQ_F16 || dtype == HQQ_BF16) && (exact ? M > GV_EXACT_ROWWISE_MAX_M : M > 8)) {
-    // a group in which only some layers meet the skinny kernel's conditions: launch the layers one by one, so that a layer is
-    // served by the same kernel (same summation order, same bits) whether or not it was grouped
-    bool any = false;
-    for (int i = 0; i < n_layers; ++i) any = any || skinny_covers(nbits, M, K, group_size, N + i, 1);
-    if (any) {
-      for (int i = 0; i < n_layers; ++i) {
-        const void* b1 = bias ? bias[i] : nullptr;
-        const int rc = hqq_hip_gemv_grouped(nbits, 1, x, Wq + i, scale + i, zero + i, bias ? &b1 : nullptr, y + i, N + i, M, K, group_size, dtype, opts, workspace, workspace_bytes, stream);
-        if (rc) return rc;
-      }
-      return 0;
-    }
-  }
-  if (exact ? M > GV_EXACT_ROWWISE_MAX_M : (M > 8 && skinny_ok)) {   // (FACTORED: the row-per-wave kernel serves M <= 8 per launch)
-    // more activation rows than the row-per-wave kernel contracts cheaply: the 16-row-tile MFMA kernel (needs K % 64 == 0)
-    if (K % 64) { set_error("hqq_hip_gemv: M=%lld > %d needs K %% 64 == 0 (got K=%lld)", (long long)M, GV_EXACT_ROWWISE_MAX_M, (long long)K); return HQQ_ERR_UNSUPPORTED; }
-    for (int i = 0; i < n_layers; ++i) {
-      if (N[i] <= 0 || N[i] % per) { set_error("hqq_hip_gemv: needs N %% %d == 0 (got N=%lld)", per, (long long)N[i]); return N[i] <= 0 ? HQQ_ERR_SHAPE : HQQ_ERR_UNSUPPORTED; }
-      if (N[i] * (K / group_size) > INT32_MAX) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
-      if (!Wq[i] || !scale[i] || !zero[i] || !y[i]) { set_error("hqq_hip_gemv: null layer pointer"); return HQQ_ERR_SHAPE; }
-      if (!aligned16(Wq[i])) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
-    }
-    if (!aligned16(x)) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
-    if (skinny_ok) return skinny_run(nbits, n_layers, x, Wq, scale, zero, bias, y, N, M, K, dtype, opts, workspace, workspace_bytes, as_stream(stream));
-    return gemv_mfma_run(nbits, n_layers, x, Wq, scale, zero, bias, y, N, M, K, group_size, as_stream(stream));
-  }
   int m_max = max_m_per_launch(K);
   m_max = m_max > (exact ? GV_EXACT_ROWWISE_MAX_M : 8) ? (exact ? GV_EXACT_ROWWISE_MAX_M : 8) : m_max;
-  if (m_max < 1) { set_error("hqq_hip_gemv: K=%lld too large to stage one row of x in LDS", (long long)K); return HQQ_ERR_UNSUPPORTED; }
-  if (!aligned16(x)) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
   GvArgs a;
   int64_t total = 0;
   for (int i = 0; i < n_layers; ++i) {
-    if (N[i] <= 0 || N[i] % per) { set_error("hqq_hip_gemv: needs N %% %d == 0 (got N=%lld)", per, (long long)N[i]); return N[i] <= 0 ? HQQ_ERR_SHAPE : HQQ_ERR_UNSUPPORTED; }
-    // (the kernel addresses a layer with 32-bit byte offsets from its base pointers: packed weights and meta below 4 GiB per layer)
-    if (N[i] * (K / group_size) > INT32_MAX || (N[i] / per) * K > static_cast<int64_t>(UINT32_MAX)) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
-    if (!Wq[i] || !scale[i] || !zero[i] || !y[i]) { set_error("hqq_hip_gemv: null layer pointer"); return HQQ_ERR_SHAPE; }
-    if (!aligned16(Wq[i])) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
     total += N[i] / per;
     if (total > INT32_MAX) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
     a.Wq[i] = static_cast<const uint8_t*>(Wq[i]);
@@ -386,7 +435,6 @@ extern "C" int hqq_hip_gemv_grouped(int nbits, int n_layers, const void* x, cons
   a.gs = static_cast<int>(group_size);
   a.G = static_cast<int>(K / group_size);
   a.total_prow = static_cast<int>(total);
-  hipStream_t st = as_stream(stream);
   // x rows beyond the LDS budget of one launch are served by further launches over row blocks of x / y
   for (int64_t m0 = 0; m0 < M; m0 += m_max) {
     const int mm = static_cast<int>(M - m0 < m_max ? M - m0 : m_max);
@@ -407,20 +455,12 @@ extern "C" int hqq_hip_gemv(int nbits, const void* x, const void* Wq, const void
 }
 
 extern "C" size_t hqq_hip_gemv_workspace_bytes(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
-  if (!N || n_layers < 1 || n_layers > HQQ_GEMV_MAX_GROUP || M < 1 || K <= 0 || group_size <= 0) return 0;
-  if (nbits == 3 && (opts & HQQ_OPT_W3S)) {
-    if (M <= GV_EXACT_ROWWISE_MAX_M) return 0;
-    return ((dtype == HQQ_F16 || dtype == HQQ_BF16) && skinny_covers(4, M, K, group_size, N, n_layers)) ? skinny_workspace_bytes(3, n_layers, N, M, K, opts) : 0;
-  }
-  if (nbits == 3) return gemv3_workspace_bytes(n_layers, N, M, K, group_size, opts);
-  if ((dtype == HQQ_F16 || dtype == HQQ_BF16) && skinny_covers(nbits, M, K, group_size, N, n_layers)) return skinny_workspace_bytes(nbits, n_layers, N, M, K, opts);
-  if (n_layers > 1 && M > GV_EXACT_ROWWISE_MAX_M) {   // a partly covered group is launched layer by layer (hqq_hip_gemv_grouped)
-    size_t most = 0;
-    for (int i = 0; i < n_layers; ++i)
-      if (skinny_covers(nbits, M, K, group_size, N + i, 1)) { const size_t b = skinny_workspace_bytes(nbits, 1, N + i, M, K, opts); most = b > most ? b : most; }
-    return most;
-  }
-  return 0;
+  const int route = plan_gemv(nbits, n_layers, N, M, K, group_size, dtype, opts);
+  return route < 0 ? 0 : route_workspace_bytes(route, nbits, n_layers, N, M, K, group_size, dtype, opts);
+}
+
+extern "C" int hqq_hip_forward_route(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
+  return plan_route(PLAN_FORWARD, nbits, n_layers, N, M, K, group_size, dtype, opts);
 }
 
 extern "C" int hqq_hip_meta_check(int nbits, const void* scale, const void* zero, int64_t N, int64_t K, int64_t group_size, int dtype,

@@ -277,11 +277,12 @@ __global__ __launch_bounds__(G3_WAVES * 64) void gemv3_f16_kernel(const G3Args a
   }
 }
 
+// x (in 1024-k units) and the layer table, staged per workgroup
+static size_t g3_lds_bytes(int64_t M, int64_t K) { return static_cast<size_t>(M) * ((K / 64 + 15) >> 4) * 1024 * 2 + G3_MAXL * 12 * sizeof(int); }
+
 template <int M>
 static int g3_launch(const G3Args& a, hipStream_t st) {
-  const int nunits = (a.G + 15) >> 4;
-  const size_t lds = static_cast<size_t>(M) * nunits * 1024 * 2 + G3_MAXL * 12 * sizeof(int);
-  if (lds > 144 * 1024) { set_error("hqq_hip_gemv: x[M=%d, K=%d] does not fit the LDS staging budget", M, a.K); return HQQ_ERR_UNSUPPORTED; }
+  const size_t lds = g3_lds_bytes(M, a.K);
   int n_cus = 256, dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0) n_cus = 256;
   int per_cu = static_cast<int>(160 * 1024 / (lds + 256));
@@ -298,34 +299,36 @@ static int g3_launch(const G3Args& a, hipStream_t st) {
 }
 
 bool gemv3s_covers(int64_t M, int64_t K, int64_t group_size);   // gemv3s.hip: each packed word loaded once for all ten slabs
-size_t gemv3s_workspace_bytes(int n_layers, const int64_t* N, int64_t M, int64_t K);
 int gemv3s_run(int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero,
                const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, uint32_t opts, void* ws, size_t ws_bytes, hipStream_t st);
 
-// which of the two 3-bit kernels a launch takes: the slab-sharing one (gemv3s.hip) from 19 MB of packed weights on — 2.2 TB/s of
-// packed bytes at the margin against 1.2 here, but ~10 us of fixed cost (a task is a 4 us chain of instructions in one wave, plus
-// the finishing launch) against ~4 us; measured crossover on MI355X (tools/sweep_int3.py).  HQQ_OPT_GEMV3_ROWWISE / _SLABS force one.
-static bool gemv3_wants_slabs(int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, uint32_t opts) {
-  if (group_size != 64 || !gemv3s_covers(M, K, group_size)) return false;
-  int64_t packed = 0;
-  for (int i = 0; i < n_layers; ++i) packed += ((N[i] * (K / 64) + 9) / 10) * 256;
-  return (opts & HQQ_OPT_GEMV3_SLABS) || (packed >= (int64_t(19) << 20) && !(opts & HQQ_OPT_GEMV3_ROWWISE));
-}
-size_t gemv3_workspace_bytes(int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, uint32_t opts) {
-  return gemv3_wants_slabs(n_layers, N, M, K, group_size, opts) ? gemv3s_workspace_bytes(n_layers, N, M, K) : 0;
-}
-
-// called by hqq_hip_gemv_grouped (gemv.hip) for nbits == 3 after the common argument checks
-int gemv3_run(int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero,
-              const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int64_t group_size, uint32_t opts,
-              void* ws, size_t ws_bytes, hipStream_t st) {
+// the shapes the two 3-bit kernels cover and which of them takes a call (asked by the planner, gemv.hip): the slab-sharing one (gemv3s.hip)
+// from 19 MB of packed weights on — 2.2 TB/s of packed bytes at the margin against 1.2 here, but ~10 us of fixed cost (a task is a 4 us
+// chain of instructions in one wave, plus the finishing launch) against ~4 us; measured crossover on MI355X (tools/sweep_int3.py).
+// HQQ_OPT_GEMV3_ROWWISE / _SLABS force one.
+int gemv3_route(int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, uint32_t opts) {
   if (group_size != 64) { set_error("hqq_hip_gemv: the fused 3-bit kernel covers group_size 64 (got %lld)", (long long)group_size); return HQQ_ERR_UNSUPPORTED; }
   if (M > G3_MAX_M) { set_error("hqq_hip_gemv: the fused 3-bit kernel covers M <= %d (got %lld)", G3_MAX_M, (long long)M); return HQQ_ERR_UNSUPPORTED; }
+  const int64_t G = K / 64;
+  int64_t packed = 0;
+  for (int i = 0; i < n_layers; ++i) {
+    if (N[i] <= 0) { set_error("hqq_hip_gemv: bad N"); return HQQ_ERR_SHAPE; }
+    if (G > (N[i] * G + 9) / 10) { set_error("hqq_hip_gemv: 3-bit layer with fewer than 10 output rows per slab is not covered"); return HQQ_ERR_UNSUPPORTED; }
+    packed += ((N[i] * G + 9) / 10) * 256;
+  }
+  if (gemv3s_covers(M, K, group_size) && ((opts & HQQ_OPT_GEMV3_SLABS) || (packed >= (int64_t(19) << 20) && !(opts & HQQ_OPT_GEMV3_ROWWISE)))) return HQQ_ROUTE_GEMV3_SLABS;
+  if (g3_lds_bytes(M, K) > 144 * 1024) { set_error("hqq_hip_gemv: x[M=%d, K=%d] does not fit the LDS staging budget", static_cast<int>(M), static_cast<int>(K)); return HQQ_ERR_UNSUPPORTED; }
+  return HQQ_ROUTE_GEMV3_ROWS;
+}
+
+// called by hqq_hip_gemv_grouped (gemv.hip) for a call routed to either 3-bit kernel (gemv3_route)
+int gemv3_run(bool slabs, int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero,
+              const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, uint32_t opts, void* ws, size_t ws_bytes,
+              hipStream_t st) {
   G3Args a;
   const int64_t G = K / 64;
   int64_t ents = 0;
   for (int i = 0; i < n_layers; ++i) {
-    if (N[i] <= 0) { set_error("hqq_hip_gemv: bad N"); return HQQ_ERR_SHAPE; }
     if (!Wq[i] || !scale[i] || !zero[i] || !y[i]) { set_error("hqq_hip_gemv: null layer pointer"); return HQQ_ERR_SHAPE; }
     if (!aligned16(Wq[i])) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
     const int64_t R = N[i] * G;
@@ -350,9 +353,8 @@ int gemv3_run(int n_layers, const void* x, const void* const* Wq, const void* co
       if (ents > INT32_MAX / 2) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
     }
     a.e_end[i] = static_cast<int>(ents);
-    if (G > a.step[i]) { set_error("hqq_hip_gemv: 3-bit layer with fewer than 10 output rows per slab is not covered"); return HQQ_ERR_UNSUPPORTED; }
   }
-  if (gemv3_wants_slabs(n_layers, N, M, K, group_size, opts)) return gemv3s_run(n_layers, x, Wq, scale, zero, bias, y, N, M, K, opts, ws, ws_bytes, st);
+  if (slabs) return gemv3s_run(n_layers, x, Wq, scale, zero, bias, y, N, M, K, opts, ws, ws_bytes, st);
   for (int i = n_layers; i < G3_MAXL; ++i) {
     a.Wq[i] = a.Wq[n_layers - 1]; a.scale[i] = a.scale[n_layers - 1]; a.zero[i] = a.zero[n_layers - 1]; a.bias[i] = a.bias[n_layers - 1];
     a.y[i] = a.y[n_layers - 1]; a.N[i] = a.N[n_layers - 1]; a.step[i] = a.step[n_layers - 1]; a.e_end[i] = a.e_end[n_layers - 1];

@@ -117,17 +117,23 @@ static int w3s_max_m(int64_t K) {
   return static_cast<int>(m < 1 ? 0 : (m > 4 ? 4 : m));
 }
 
-// hqq_hip_gemv_grouped for nbits = 3 with HQQ_OPT_W3S, 1 <= M <= 4 (arguments validated by the caller up to what is checked here)
-int gemv_w3s_run(int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero, const void* const* bias,
-                 void* const* y, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts, hipStream_t st) {
+// the shapes this kernel covers (asked by the planner, gemv.hip): 0, or the refusal with its message set
+int gemv_w3s_check(int n_layers, const int64_t* N, int64_t K, int64_t group_size) {
   if (group_size != 64 || K % 64) { set_error("hqq_hip_gemv: the 3-bit stream layout covers group_size 64, K %% 64 == 0"); return HQQ_ERR_UNSUPPORTED; }
+  if (w3s_max_m(K) < 1) { set_error("hqq_hip_gemv: K=%lld too large to stage one row of x in LDS", (long long)K); return HQQ_ERR_UNSUPPORTED; }
+  for (int i = 0; i < n_layers; ++i)
+    if (N[i] <= 0 || N[i] % 2) { set_error("hqq_hip_gemv: the 3-bit stream layout needs N %% 2 == 0 (got N=%lld)", (long long)N[i]); return N[i] <= 0 ? HQQ_ERR_SHAPE : HQQ_ERR_UNSUPPORTED; }
+  return 0;
+}
+
+// hqq_hip_gemv_grouped for a call routed here (HQQ_ROUTE_ROWWISE_W3S: nbits = 3 with HQQ_OPT_W3S, 1 <= M <= 4, gemv_w3s_check passed)
+int gemv_w3s_run(int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero, const void* const* bias,
+                 void* const* y, const int64_t* N, int64_t M, int64_t K, int dtype, uint32_t opts, hipStream_t st) {
   if (K > INT32_MAX / 2) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
   const int m_max = w3s_max_m(K);
-  if (m_max < 1) { set_error("hqq_hip_gemv: K=%lld too large to stage one row of x in LDS", (long long)K); return HQQ_ERR_UNSUPPORTED; }
   GvArgs a;
   int64_t total = 0;
   for (int i = 0; i < n_layers; ++i) {
-    if (N[i] <= 0 || N[i] % 2) { set_error("hqq_hip_gemv: the 3-bit stream layout needs N %% 2 == 0 (got N=%lld)", (long long)N[i]); return N[i] <= 0 ? HQQ_ERR_SHAPE : HQQ_ERR_UNSUPPORTED; }
     if (N[i] * (K / 64) > INT32_MAX || (N[i] / 2) * (K / 4) * 3 > static_cast<int64_t>(UINT32_MAX)) { set_error("hqq_hip_gemv: size overflow"); return HQQ_ERR_SHAPE; }
     if (!Wq[i] || !scale[i] || !zero[i] || !y[i]) { set_error("hqq_hip_gemv: null layer pointer"); return HQQ_ERR_SHAPE; }
     if (!aligned16(Wq[i])) { set_error("hqq_hip_gemv: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }

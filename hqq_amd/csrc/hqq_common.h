@@ -39,6 +39,13 @@ static inline int raise_lds_limit(LdsRaised& st, const void* kern, int bytes, co
   return 0;
 }
 
+// ---- routing (host): plan_route (gemv.hip) decides which kernel serves a call (include/hqq_hip.h, routes); pure host arithmetic.
+// A refusal returns its HQQ_ERR_* code with the message of the entry point `entry` names.
+enum PlanEntry { PLAN_GEMV, PLAN_GEMM, PLAN_GEMM_GROUPED, PLAN_FORWARD };
+int plan_route(PlanEntry entry, int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts);
+bool forward_on_decode(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts);   // hqq_hip_forward -> hqq_hip_gemv
+size_t route_workspace_bytes(int route, int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts);
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static inline int per_of(int nbits) {

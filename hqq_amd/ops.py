@@ -7,6 +7,9 @@ eager PyTorch.
 """
 from __future__ import annotations
 
+import ctypes
+import functools
+
 import torch
 from torch import Tensor
 
@@ -17,8 +20,8 @@ _DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16, torch.uint8
 PER = {8: 1, 4: 2, 2: 4, 1: 8, 3: 10}
 # Quantizer.bit_to_packing (hqq/core/quantize.py:40-49): container width per nbits
 PACK_BITS = {8: 8, 6: 8, 5: 8, 4: 4, 3: 3, 2: 2, 1.58: 2, 1: 1}
-GEMV_MAX_M = 16
-SKINNY_MAX_M = 64   # HQQ_GEMV_MAX_M_SKINNY: fp16 / bf16, 8-/4-/2-bit, group_size 64, K % 256 == 0, K >= 512
+GEMV_MAX_M = 16     # HQQ_GEMV_MAX_M
+SKINNY_MAX_M = 64   # HQQ_GEMV_MAX_M_SKINNY
 GEMV_EXACT, GEMV_FACTORED = 0, 1
 GEMV_MAX_GROUP = 4
 # per-call option bits of the C ABI (include/hqq_hip.h HQQ_OPT_*)
@@ -29,6 +32,25 @@ OPT_BATCH_SPLITK = 2048   # LAB builds only (tools/lab_kwave/build.sh): force th
 
 def OPT_SKINNY_KS(n: int) -> int:
     return int(n) << 24
+
+
+# the kernel a call runs (include/hqq_hip.h HQQ_ROUTE_*, the table of routes); the first six are hqq_hip_gemv's
+ROUTE_ROWWISE, ROUTE_ROWWISE_W3S, ROUTE_GEMV3_ROWS, ROUTE_GEMV3_SLABS, ROUTE_MFMA16, ROUTE_SKINNY, ROUTE_GEMM_PIPE, ROUTE_GEMM_TILE = range(1, 9)
+DECODE_ROUTES = frozenset(range(ROUTE_ROWWISE, ROUTE_SKINNY + 1))
+
+
+@functools.lru_cache(maxsize=4096)
+def route(dtype, M: int, Ns: tuple, K: int, group_size, nbits: int, opts: int = 0) -> int:
+    """hqq_hip_forward_route: the ROUTE_* for x [M, K] through layers of Ns (a tuple) output rows, or the negative HQQ_ERR_* of the refusal"""
+    n = len(Ns)
+    return int(_C.lib().hqq_hip_forward_route(int(nbits), n, (ctypes.c_int64 * n)(*Ns), int(M), int(K), int(group_size or 0), _DT.get(dtype, -1), int(opts)))
+
+
+@functools.lru_cache(maxsize=4096)
+def prefers_fused(dtype, M: int, N: int, K: int, group_size, nbits: int, w3s: bool = False) -> bool:
+    """hqq_hip_forward_prefers_fused: the fused kernels are measured ahead of dequantise + GEMM for this shape (a speed hint).  A layer in the 3-bit
+    stream layout runs the 4-bit layer's GEMM plan and is asked as one (the query takes no option bits)."""
+    return dtype in _DT and bool(_C.lib().hqq_hip_forward_prefers_fused(4 if w3s else int(nbits), int(M), int(N), int(K), int(group_size or 0), _DT[dtype]))
 
 
 # Default arithmetic of the decode wrappers below when a call passes no `opts` — a convenience of THIS module (tools, tests,
@@ -145,7 +167,6 @@ def reserve_workspace(device, nbytes: int) -> Tensor:
 
 
 def _workspace(x: Tensor, nbits, Ns, M, K, group_size, opts):
-    import ctypes
     n = len(Ns)
     need = int(_C.lib().hqq_hip_gemv_workspace_bytes(int(nbits), n, (ctypes.c_int64 * n)(*[int(v) for v in Ns]), int(M), int(K), int(group_size),
                                                      _dt(x.dtype), int(opts)))
@@ -290,14 +311,13 @@ def _fwd(fn_name: str, x: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, bias
 
 
 def gemv(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None, opts=None) -> Tensor:
-    """fused unpack->dequant->GEMV for decode-sized batches: 1 <= M <= 16 (3-bit, and bf16 outside the skinny-GEMM kernel: <= 4; FACTORED mode: <= 8); up to SKINNY_MAX_M where skinny_covers()."""
+    """fused unpack->dequant->GEMV for decode-sized batches: the routes of hqq_hip_gemv (route() in DECODE_ROUTES; include/hqq_hip.h)."""
     return _fwd("hqq_hip_gemv", x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts)
 
 
 def gemv_grouped(x: Tensor, layers, K: int, group_size: int, nbits: int, outs=None, opts=None):
     """Horizontal fusion: one launch for up to GEMV_MAX_GROUP layers that consume the same x (q/k/v, gate/up, ...).
     layers: sequence of (W_q, scale, zero, bias_or_None, N).  Returns the list of outputs [*, N_i]."""
-    import ctypes
     n = len(layers)
     if not 1 <= n <= GEMV_MAX_GROUP:
         raise ValueError(f"hqq_amd: a GEMV group holds 1..{GEMV_MAX_GROUP} layers, got {n}")
@@ -327,12 +347,8 @@ def gemv_grouped(x: Tensor, layers, K: int, group_size: int, nbits: int, outs=No
     return [o.reshape(*x.shape[:-1], L[4]) for o, L in zip(outs, layers)]
 
 
-FUSED_GEMM_MAX_M = 2560   # gemm_pipe_wins (csrc/gemm_pipe.hip): beyond, dequantise + the dense GEMM is the faster route
-
-
 def gemm_grouped_covers(dtype, layers_N, M: int, K: int, group_size, nbits: int, opts=None) -> bool:
-    """True when hqq_hip_gemm_grouped serves this group: every layer on the pipelined fused GEMM (fp16 / bf16, 8 / 4 / 2 bit or the 3-bit stream layout, group_size 64, K % 128 == 0)"""
-    import ctypes
+    """True when hqq_hip_gemm_grouped serves this group: every layer on the pipelined fused GEMM (ROUTE_GEMM_PIPE)"""
     n = len(layers_N)
     if dtype not in _DT or not 1 <= n <= GEMV_MAX_GROUP or M < 1 or not group_size:
         return False
@@ -343,7 +359,6 @@ def gemm_grouped(x: Tensor, layers, K: int, group_size: int, nbits: int, outs=No
     """Horizontal fusion beyond the decode rows: ONE launch of the pipelined fused GEMM (+ one split-K reduce) for up to GEMV_MAX_GROUP layers that consume
     the same x (q / k / v, gate / up) — a decoder block at 65..2560 rows is 4 launches instead of 7.  layers: sequence of (W_q, scale, zero, bias_or_None, N).
     Returns the list of outputs [*, N_i].  The K split is chosen for the group's total width: a row can differ in the last bit from the layer launched alone."""
-    import ctypes
     n = len(layers)
     if not 1 <= n <= GEMV_MAX_GROUP:
         raise ValueError(f"hqq_amd: a GEMM group holds 1..{GEMV_MAX_GROUP} layers, got {n}")
@@ -396,7 +411,6 @@ def gemv_block(x: Tensor, norm_weight, eps: float, layers, K: int, group_size: i
       BLOCK_RESID              ONE layer; outs[0] is the residual stream, updated in place: h += layer(x)
       BLOCK_NORM | BLOCK_ROPE  q | k | v with q and k from rotary_pair_layout(): outs = [q_out [n_heads, hd], k_cache, v_cache [n_kv, L, hd]];
                                rope = (cos [hd], sin [hd], pos [1] int64 on the device, head_dim, cache_len): rope_cache() in the launch's epilogue"""
-    import ctypes
     n = len(layers)
     rp = None
     if flags & BLOCK_ROPE:
@@ -496,7 +510,6 @@ def exchange(y_loc, N_loc, nbits: int, world: int, rank: int, full_ptrs, flag_pt
     """One exchange point of a column-sharded decode step (csrc/exchange.hip, hqq_hip_exchange): this rank's [1, N_loc[j]] slices go
     straight into every rank's full row of layer j, in the reference's column order; returns when enqueued (the kernel finishes once all
     `world` ranks have delivered).  full_ptrs[p][j] / flag_ptrs[p]: raw device addresses (see hqq_amd.shard.PeerExchange, which owns them)."""
-    import ctypes
     n = len(y_loc)
     if not 1 <= n <= GEMV_MAX_GROUP:
         raise ValueError(f"hqq_amd: an exchange point holds 1..{GEMV_MAX_GROUP} layers, got {n}")
@@ -526,9 +539,9 @@ def gemm(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None, opts=None
 
 
 # Which path `forward` takes by the number of activation rows M (measured on MI355X, tools/prefill_routes.py -> profiles/r04_prefill_routes_int4.txt):
-#   M <= 16 (<= 64 where skinny_covers): the weight-streaming decode kernels;
-#   65 <= M <= 2560 (hqq_hip_forward_prefers_fused): the pipelined split-K fused MFMA dequant-GEMM (gemm_pipe.hip);
-#   beyond: the HIP dequantise kernel + the in-tree dense MFMA GEMM (hqq_hip_gemm_dense, gemm_dense.hip) — one extra write + read of the
+#   the decode routes (route() in DECODE_ROUTES): the weight-streaming decode kernels;
+#   beyond, where hqq_hip_forward_prefers_fused says so (to 2560 rows): the pipelined split-K fused MFMA dequant-GEMM (gemm_pipe.hip);
+#   else: the HIP dequantise kernel + the in-tree dense MFMA GEMM (hqq_hip_gemm_dense, gemm_dense.hip) — one extra write + read of the
 #       fp16 weights (11-36 us), then the weights are rebuilt once, not once per 256-token tile: 1.0-1.2 PFLOP/s at M = 8192 against
 #       0.87-0.95 for the fused kernel.  No library GEMM on any product path (`library_gemm=True` is the bench's comparison leg).
 # `fused=True` forces the fused kernels for every M.  LIBRARY_GEMM_MIN_M (a historical name: the composition's GEMM is the in-tree one) applies to
@@ -537,27 +550,15 @@ LIBRARY_GEMM_MIN_M = 17
 
 
 def skinny_covers(dtype, M, N, K, group_size, nbits, w3s: bool = False) -> bool:
-    """a batch of up to SKINNY_MAX_M rows that the weight-streaming skinny-GEMM kernel serves (csrc/skinny.hip: skinny_covers); 3-bit layers
-    in the stream layout only (w3s=True)"""
-    if nbits == 3:
-        return bool(w3s) and dtype in (torch.float16, torch.bfloat16) and group_size == 64 and 5 <= M <= SKINNY_MAX_M and K % 256 == 0 and K >= 512 and N % 2 == 0
-    return (dtype in (torch.float16, torch.bfloat16) and nbits in (8, 4, 2) and group_size == 64 and 5 <= M <= SKINNY_MAX_M and K % 256 == 0 and K >= 512
-            and N % (8 // nbits) == 0)
+    """a batch that the weight-streaming skinny-GEMM kernel serves (ROUTE_SKINNY); 3-bit layers in the stream layout only (w3s=True)"""
+    return route(dtype, M, (N,), K, group_size, nbits, OPT_W3S if w3s else 0) == ROUTE_SKINNY
 
 
 def decode_covers(dtype, M, N, K, group_size, nbits) -> bool:
-    """what hqq_hip_gemv serves for M <= GEMV_MAX_M rows (include/hqq_hip.h); everything else is composed in `forward`"""
-    if M > GEMV_MAX_M or not group_size or K % group_size:
-        return False
-    if nbits == 3:   # x (+ a 16-group tail) is staged in LDS: 144 KiB bound M * K; a row's groups must fit inside one slab
-        G = K // 64
-        return (dtype == torch.float16 and group_size == 64 and M <= 4 and M * (K + 1024) * 2 + 256 <= 144 * 1024
-                and (N * G + 9) // 10 >= G)
-    if nbits not in (8, 4, 2, 1) or group_size % 16 or K % 16 or N % (8 // nbits):
-        return False
-    if dtype == torch.bfloat16:
-        return nbits in (4, 2) and M <= 4
-    return dtype == torch.float16 and (M <= 4 or K % 64 == 0)
+    """what hqq_hip_gemv serves for M <= GEMV_MAX_M rows with exact weights; everything else is composed in `forward`.  (bf16 batches of 5..16 rows
+    exist only on the skinny route: skinny_covers() reports those.)"""
+    r = route(dtype, M, (N,), K, group_size, nbits)
+    return M <= GEMV_MAX_M and r in DECODE_ROUTES and not (r == ROUTE_SKINNY and dtype == torch.bfloat16)
 
 
 def decode_axis0_covers(dtype, M, N, K, group_size, nbits) -> bool:
@@ -657,11 +658,11 @@ def _compose(x, W, bias, out, N, K, library: bool) -> Tensor:
 
 
 def forward(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None, fused=None, opts=None, library_gemm: bool = False, axis: int = 1) -> Tensor:
-    """y = x @ dequantize(W_q)^T (+ bias).  M <= 16 (<= 64 where the skinny-GEMM kernel applies): weight-streaming decode kernels;
-    larger M: fused MFMA dequant-GEMM to 2560 rows, beyond — and for what the fused kernels do not cover, unless fused=True — the dequantise
+    """y = x @ dequantize(W_q)^T (+ bias).  The decode routes (route(); include/hqq_hip.h): weight-streaming decode kernels; larger M: fused MFMA
+    dequant-GEMM where hqq_hip_forward_prefers_fused says so, beyond — and for what the fused kernels do not cover, unless fused=True — the dequantise
     kernel + the in-tree dense MFMA GEMM (library_gemm=True: a library GEMM instead, the bench's comparison; also the residual route for
-    K % 64 != 0 or N % 4 != 0).  Same dequantised weights either way.  fused=None also composes the few decode-sized cases the kernels do not cover (3-bit beyond 4 rows,
-    bf16 beyond 4 rows outside the skinny-GEMM kernel, 5..16 rows with K % 64 != 0); fused=True never composes: an uncovered configuration raises.
+    K % 64 != 0 or N % 4 != 0).  Same dequantised weights either way.  fused=None also composes the decode-sized cases no route covers;
+    fused=True never composes: an uncovered configuration raises.
     axis=0: a layer quantised along axis 0 — decode_axis0_covers() shapes through hqq_hip_gemv_axis0, the rest through the dequantise kernel +
     torch.matmul (`fused` and `library_gemm` do not apply)."""
     M = x.numel() // K if K else 0
@@ -671,22 +672,15 @@ def forward(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None, fused=
         return _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts)
     if axis != 1:
         raise ValueError(f"hqq_amd: axis must be 0 or 1, got {axis}")
-    if nbits == 3 and (_opts(opts) & OPT_W3S):
-        # the 3-bit stream layout: the 4-bit container's kernels (1..4 rows: row-per-wave GEMV; 5..64: the skinny GEMM); beyond, the reference
-        # container is restored on the fly for the dequantise kernel + dense GEMM (long prompts of a patched 3-bit layer)
-        if M <= 4 or (M <= SKINNY_MAX_M and group_size == 64 and K % 256 == 0 and K >= 512 and x.dtype in (torch.float16, torch.bfloat16)) or fused or \
-                (fused is None and M > SKINNY_MAX_M and x.dtype in _DT and bool(_C.lib().hqq_hip_forward_prefers_fused(4, M, int(N), int(K), int(group_size or 0), _dt(x.dtype)))):   # (asked as a 4-bit layer: same kernels, same plan; 5..64 rows outside the batched-decode kernels' shapes compose below)
-            return _fwd("hqq_hip_forward", x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts)
-        W = dequantize(w3s_unpack(W_q, N, K), scale.reshape(-1), zero.reshape(-1), N, K, group_size, 3, 1)
-        return _compose(x, W, bias, out, N, K, library_gemm)
+    w3s = nbits == 3 and bool(_opts(opts) & OPT_W3S)   # the 3-bit stream layout (w3s_pack)
     if fused is None:
-        fused = skinny_covers(x.dtype, M, N, K, group_size, nbits) or \
-            (decode_covers(x.dtype, M, N, K, group_size, nbits) and not (LIBRARY_GEMM_MIN_M and M >= LIBRARY_GEMM_MIN_M)) or \
-            (M > GEMV_MAX_M and x.is_cuda and nbits in (8, 4, 2) and x.dtype in _DT and
-             bool(_C.lib().hqq_hip_forward_prefers_fused(int(nbits), M, int(N), int(K), int(group_size or 0), _dt(x.dtype))))
+        # asked for the layer's layout, not its arithmetic bits.  The stream layout composes 5..64 rows outside the skinny kernel.
+        r = route(x.dtype, M, (int(N),), int(K), group_size, nbits, OPT_W3S if w3s else 0)
+        fused = (r == ROUTE_SKINNY or (r in DECODE_ROUTES and not (LIBRARY_GEMM_MIN_M and M >= LIBRARY_GEMM_MIN_M)) or
+                 (r == ROUTE_GEMM_PIPE and M > (SKINNY_MAX_M if w3s else GEMV_MAX_M) and x.is_cuda and prefers_fused(x.dtype, M, int(N), int(K), group_size, nbits, w3s)))
     if fused:
         return _fwd("hqq_hip_forward", x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts)
-    W = dequantize(W_q, scale.reshape(-1), zero.reshape(-1), N, K, group_size, nbits, 1)
+    W = dequantize(w3s_unpack(W_q, N, K) if w3s else W_q, scale.reshape(-1), zero.reshape(-1), N, K, group_size, nbits, 1)
     return _compose(x, W, bias, out, N, K, library_gemm)
 
 

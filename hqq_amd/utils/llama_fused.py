@@ -289,21 +289,17 @@ class FusedLlamaStep:
 def batch_covers(dtype, B: int, layers, opts: int = 0) -> bool:
     """whether the fused decode kernels serve every layer of `layers` — (N, K, group_size, nbits, w3s) each — at M = B activation rows (a pure
     function of the shapes: no device needed).  The grouped launch (hqq_hip_gemv_grouped) takes a group of layers at B rows where each of them is
-    served on its own, so the rule is per layer: the weight-streaming skinny kernel (ops.skinny_covers: 5..64 rows, group_size 64, K % 256 == 0,
-    K >= 512, fp16 / bf16, 3-bit in the stream layout) or else the decode kernels (ops.decode_covers: fp16 up to 16 rows, bf16 4 / 2-bit and
-    3-bit up to 4; with OPT_FACTORED in `opts` fp16 up to 8).  The 3-bit stream layout outside the skinny kernel: up to 4 rows."""
+    served on its own, so the rule is per layer: a decode route (ops.route, asked for the layer's layout)."""
     B = int(B)
     if B < 1:
         return False
     factored = bool(int(opts) & ops.OPT_FACTORED) and dtype == torch.float16
-    for (N, K, gs, nbits, w3s) in layers:
-        if ops.skinny_covers(dtype, B, N, K, gs, nbits, w3s):
-            continue
-        if w3s:
-            ok = nbits == 3 and dtype in (torch.float16, torch.bfloat16) and B <= 4 and ops.w3s_covers(N, K, gs)
-        else:
-            ok = ops.decode_covers(dtype, B, N, K, gs, nbits) and not (factored and B > 8)
-        if not ok:
+    for (N, K, gs, nbits, w3s) in set(layers):   # (a model repeats a few shapes)
+        r = ops.route(dtype, B, (N,), K, gs, nbits, ops.OPT_W3S if w3s else 0)
+        if r not in ops.DECODE_ROUTES:
+            return False
+        # a policy, not a kernel limit: FACTORED batches beyond 8 rows only on the skinny kernel (the row-per-wave kernel would serve them in launches of 8)
+        if factored and B > 8 and r != ops.ROUTE_SKINNY:
             return False
     return True
 

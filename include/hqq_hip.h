@@ -79,22 +79,33 @@ int hqq_hip_dequantize(int nbits, const void* Wq, const void* scale, const void*
  *   to hqq_hip_dequantize, fp32 accumulation, one rounding to `dtype` (+ one for the bias add).
  * hqq_hip_gemv : small M (decode), HBM-bandwidth bound (MFMA only as a free dot-product unit).  1 <= M <= HQQ_GEMV_MAX_M
  * hqq_hip_gemm : large M (prefill), MFMA f16/bf16.                          any M >= 1
- * hqq_hip_forward picks one of the two by M.
- * Covered by hqq_hip_gemv: nbits in {8,4,2,1} with N % (8/nbits) == 0, group_size % 16 == 0, K % group_size == 0, fp16,
- * M <= 16 (bf16: nbits 4/2, M <= 4; up to HQQ_GEMV_MAX_M_SKINNY = 64 rows for fp16 and bf16, nbits 8/4/2, group_size 64,
- * K % 256 == 0, K >= 512: the weight-streaming skinny-GEMM kernel); nbits 3 with group_size 64, fp16, M <= 4.
+ * hqq_hip_forward picks one of the two by M; the routes below say which kernel serves a call.  Anything uncovered -> HQQ_ERR_UNSUPPORTED
+ * (the caller may compose hqq_hip_dequantize + its own GEMM).
  * Workspace: launches of 5..64 rows that split K, and 3-bit launches of >= 19 MB of packed weights, park fp32 partial sums (and
  * arrival counters) in a caller-owned workspace of hqq_hip_gemv_workspace_bytes(...) bytes (0 = this call needs none; then
  * workspace may be NULL).  Contract: 16-byte aligned device memory, ZERO when first used — the caller clears it once when
  * allocating it; every call leaves the counter area zero again — and not shared by calls that may run concurrently.  A larger
  * workspace than asked for is fine: one buffer sized for the largest launch serves a whole model.
- * hqq_hip_gemm: fp16 / bf16, nbits in {8,4,2} with group_size 64, K % 128 == 0 (the pipelined kernel: all operands by LDS-DMA, K split
- * across workgroups until the chip is full, fp32 partial tiles parked in the workspace and summed in split order by a second launch;
- * any M); fp16, nbits in {4,2}, K % 64 == 0, group_size % 16 == 0 (the output-tile kernels: the other group sizes, any M).
- * Anything else -> HQQ_ERR_UNSUPPORTED (the caller may compose hqq_hip_dequantize + its own GEMM).
+ *
+ * Routes: which kernel serves a call.  One planner in the library decides it for every entry point and query; hqq_hip_forward_route asks it
+ * for hqq_hip_forward (n_layers = 1) or a group (hqq_hip_gemv_grouped / hqq_hip_gemm_grouped) without launching: a route, or the negative
+ * HQQ_ERR_* the call returns (message in hqq_hip_last_error()).  The 3-bit stream layout is asked as itself (nbits 3, HQQ_OPT_W3S).
+ *   1 ROWWISE      1..4 rows (FACTORED 1..16, 8 per launch); nbits 8/4/2/1, fp16 (bf16: 4/2), gs % 16 == 0, K % 16 == 0, x fits LDS
+ *   2 ROWWISE_W3S  1..4;  stream layout, fp16 / bf16, gs 64, N % 2 == 0
+ *   3 GEMV3_ROWS   1..4;  3-bit container, fp16, gs 64, a row's groups within one slab, x fits LDS
+ *   4 GEMV3_SLABS  the same layers from 19 MB of packed weights (HQQ_OPT_GEMV3_ROWWISE / _SLABS force one); workspace
+ *   5 MFMA16       5..16, exact weights; nbits 8/4/2/1, fp16, K % 64 == 0
+ *   6 SKINNY       5..64 (FACTORED 9..64); nbits 8/4/2 or stream layout, fp16 / bf16, gs 64, K % 256 == 0, K >= 512; workspace
+ *   7 GEMM_PIPE    beyond; nbits 8/4/2 or stream layout, fp16 / bf16, gs 64, K % 128 == 0, (N / per) % 4 == 0; workspace
+ *   8 GEMM_TILE    beyond, or with HQQ_OPT_GEMM_REGTILE / _CLASSIC; nbits 4/2, fp16, gs % 16 == 0, K % 64 == 0, N % (4 per) == 0
+ * Every route needs N % per == 0.  hqq_hip_gemv serves 1-6, hqq_hip_gemm 7-8; hqq_hip_forward takes hqq_hip_gemv up to HQQ_GEMV_MAX_M rows
+ * (3-bit: 4) and on skinny shapes.  "workspace": parks partial sums when the plan splits K.
  * ------------------------------------------------------------------------------------------- */
+enum { HQQ_ROUTE_ROWWISE = 1, HQQ_ROUTE_ROWWISE_W3S, HQQ_ROUTE_GEMV3_ROWS, HQQ_ROUTE_GEMV3_SLABS, HQQ_ROUTE_MFMA16, HQQ_ROUTE_SKINNY,
+       HQQ_ROUTE_GEMM_PIPE, HQQ_ROUTE_GEMM_TILE };
+int hqq_hip_forward_route(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts);
 #define HQQ_GEMV_MAX_M 16
-#define HQQ_GEMV_MAX_M_SKINNY 64   /* fp16 / bf16, 8-/4-/2-bit, group_size 64, K % 256 == 0, K >= 512: the skinny-GEMM kernel */
+#define HQQ_GEMV_MAX_M_SKINNY 64   /* HQQ_ROUTE_SKINNY */
 #define HQQ_GEMV_MAX_GROUP 4
 /* per-call options */
 #define HQQ_OPT_FACTORED       1u   /* decode arithmetic: the group affine map is factored out of the dot product and applied in fp32
@@ -276,8 +287,8 @@ int hqq_hip_rope_attn_decode_batched(const void* q, const void* k, const void* v
                                      void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype,
                                      int64_t splits, void* workspace, size_t workspace_bytes, void* stream);
 
-/* workspace of hqq_hip_forward / hqq_hip_gemm for one layer at M rows (0 = none needed, workspace may be NULL): the decode kernels'
- * (hqq_hip_gemv_workspace_bytes) up to HQQ_GEMV_MAX_M_SKINNY rows, the split-K fused GEMM's fp32 partial tiles beyond.  Same contract. */
+/* workspace of hqq_hip_forward / hqq_hip_gemm for one layer at M rows (0 = none needed, workspace may be NULL): what the call's route parks
+ * (the routes table above marks the ones that need workspace).  Same contract. */
 size_t hqq_hip_forward_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts);
 /* introspection (host arithmetic only): how the pipelined fused GEMM would run this shape — out8 = {waves per workgroup, tokens per tile,
  * feature tiles, token tiles, K splits, steps per split, tiles that run unsplit before the split ones, workgroups}; HQQ_ERR_UNSUPPORTED
@@ -285,7 +296,8 @@ size_t hqq_hip_forward_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t 
 int hqq_hip_gemm_plan(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, int* out8);
 size_t hqq_hip_gemm_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts);   /* hqq_hip_gemm called directly, any M */
 /* 1 when, for this shape, the fused kernels behind hqq_hip_forward are measured faster on MI355X than hqq_hip_dequantize + a library
- * GEMM on the result (the caller's alternative for M > HQQ_GEMV_MAX_M_SKINNY), else 0: a speed hint, never a correctness matter. */
+ * GEMM on the result (the caller's alternative beyond the decode routes), else 0: a speed hint, never a correctness matter.  Always 1 up to
+ * HQQ_GEMV_MAX_M rows; beyond, 1 on the skinny route and on the pipelined route while it is ahead (to 2560 rows). */
 int hqq_hip_forward_prefers_fused(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype);
 int hqq_hip_gemm(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias,
                  void* y, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes,
