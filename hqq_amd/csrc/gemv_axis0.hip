@@ -17,6 +17,10 @@
 // Weights: round(round(q - z) * s) in the compute dtype, the two roundings of Quantizer.dequantize — bit-identical to hqq_hip_dequantize.
 // Split-K: every wave parks its fp32 partial sums in the caller's workspace (past the counter head, which stays untouched); a second
 // launch sums the splits in split order, rounds once and adds the bias (one more rounding): deterministic, shape-only split rule.
+// Grouped (hqq_hip_gemv_axis0_grouped): up to three layers on the same x — q|k|v, gate|up — as ONE contraction launch over their concatenated work
+// items and ONE reduce launch; each layer keeps its own plan and partial-sum area, so its output is the single-layer call's bit for bit.  The
+// reduce can finish gate|up as silu(gate) * up (HQQ_BLOCK_SILU, block_math.h's silu_mul_el on the two rounded outputs).
+#include "block_math.h"
 #include "decode_common.h"
 
 namespace hqq {
@@ -121,16 +125,15 @@ struct A0Slabs {
   }
 };
 
+// one work item — (class, block of the class, K split) number `item` of ONE layer's plan — by the calling wave: shared by the single-layer kernel
+// and the grouped one, so that a layer's partial sums are the same bits in either
 template <int NBITS, bool BF16>
-__global__ __launch_bounds__(A0_WAVES * 64) void gemv_axis0_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ Wq,
-                                                                  const uint16_t* __restrict__ scale, const uint16_t* __restrict__ zero,
-                                                                  float* __restrict__ part, int M, int N, int K, int S, int P, int nblocks,
-                                                                  int upc, int units, int64_t items) {
+__device__ __forceinline__ void a0_item(const uint16_t* __restrict__ x, const uint8_t* __restrict__ Wq, const uint16_t* __restrict__ scale,
+                                        const uint16_t* __restrict__ zero, float* __restrict__ part, int M, int N, int K, int S, int P, int nblocks,
+                                        int upc, int units, int64_t item) {
   constexpr int PER = 8 / NBITS;
   constexpr int TB = NBITS;   // tiles of 16 packed rows per wave: TB * 16 * PER = 128 output rows
   const int lane = threadIdx.x & 63;
-  const int64_t item = static_cast<int64_t>(blockIdx.x) * A0_WAVES + (threadIdx.x >> 6);
-  if (item >= items) return;
   const int b = static_cast<int>(item % nblocks);
   const int64_t rest = item / nblocks;
   const int r = static_cast<int>(rest % S);
@@ -204,15 +207,47 @@ __global__ __launch_bounds__(A0_WAVES * 64) void gemv_axis0_kernel(const uint16_
   }
 }
 
-// y[m, n] = round(sum over splits, in split order) (+ bias: `out += bias` on the rounded result, quantize.py:896-897)
-template <bool BF16>
-__global__ __launch_bounds__(256) void gemv_axis0_reduce_kernel(const float* __restrict__ part, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
-                                                                int M, int N, int splits) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-  const int64_t MN = static_cast<int64_t>(M) * N;
-  if (i >= MN) return;
-  // the loads of eight splits are issued together (independent), then added in split order: a thread is one chain of dependent adds, not of
-  // dependent round trips to memory
+template <int NBITS, bool BF16>
+__global__ __launch_bounds__(A0_WAVES * 64) void gemv_axis0_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ Wq,
+                                                                  const uint16_t* __restrict__ scale, const uint16_t* __restrict__ zero,
+                                                                  float* __restrict__ part, int M, int N, int K, int S, int P, int nblocks,
+                                                                  int upc, int units, int64_t items) {
+  const int64_t item = static_cast<int64_t>(blockIdx.x) * A0_WAVES + (threadIdx.x >> 6);
+  if (item >= items) return;
+  a0_item<NBITS, BF16>(x, Wq, scale, zero, part, M, N, K, S, P, nblocks, upc, units, item);
+}
+
+// hqq_hip_gemv_axis0_grouped: the work items of up to A0_MAX_GROUP layers that read the same x, concatenated.  Item i belongs to the first layer whose
+// running total `end` exceeds it and is item i - (the previous layer's end) of that layer's OWN plan (a0_plan of the layer alone)
+constexpr int A0_MAX_GROUP = 3;
+struct A0Member {
+  const uint8_t* Wq;
+  const uint16_t* scale;
+  const uint16_t* zero;
+  float* part;      // the layer's own partial-sum area [splits, M, N]
+  int64_t end;      // work items of this layer and the ones before it (layers past n_layers repeat the total)
+  int N, S, P, nblocks, upc, splits;
+};
+struct A0Group {
+  A0Member l[A0_MAX_GROUP];
+};
+
+template <int NBITS, bool BF16>
+__global__ __launch_bounds__(A0_WAVES * 64) void gemv_axis0_grouped_kernel(const uint16_t* __restrict__ x, const A0Group g, int M, int K, int units) {
+  // (the wave index through readfirstlane: the member is then picked with scalar loads from the kernel arguments)
+  const int64_t item = static_cast<int64_t>(blockIdx.x) * A0_WAVES + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  if (item >= g.l[A0_MAX_GROUP - 1].end) return;
+  int li = 0;
+  int64_t first = 0;
+  if (item >= g.l[0].end) { li = 1; first = g.l[0].end; }
+  if (item >= g.l[1].end) { li = 2; first = g.l[1].end; }
+  const A0Member& m = g.l[li];
+  a0_item<NBITS, BF16>(x, m.Wq, m.scale, m.zero, m.part, M, m.N, K, m.S, m.P, m.nblocks, m.upc, units, item - first);
+}
+
+// the partial sums of output i over the splits, in split order.  The loads of eight splits are issued together (independent), then added in split
+// order: a thread is one chain of dependent adds, not of dependent round trips to memory
+static __device__ __forceinline__ float a0_sum_splits(const float* __restrict__ part, int64_t MN, int64_t i, int splits) {
   float s = 0.f;
   int c = 0;
   for (; c + 8 <= splits; c += 8) {
@@ -223,15 +258,60 @@ __global__ __launch_bounds__(256) void gemv_axis0_reduce_kernel(const float* __r
     for (int j = 0; j < 8; ++j) s += v[j];
   }
   for (; c < splits; ++c) s += part[c * MN + i];
-  const int n = static_cast<int>(i % N);
+  return s;
+}
+
+// round(s) (+ bias: `out += bias` on the rounded result, quantize.py:896-897), as raw bits of the compute dtype
+template <bool BF16>
+static __device__ __forceinline__ uint16_t a0_finish(float s, const uint16_t* __restrict__ bias, int n) {
   if constexpr (BF16) {
     uint16_t o = f32_to_bf16(s);
     if (bias) o = f32_to_bf16(bf16_to_f32(o) + bf16_to_f32(bias[n]));
-    y[i] = o;
+    return o;
   } else {
     half_t o = static_cast<half_t>(s);
     if (bias) o = o + __builtin_bit_cast(half_t, bias[n]);
-    y[i] = __builtin_bit_cast(uint16_t, o);
+    return __builtin_bit_cast(uint16_t, o);
+  }
+}
+
+// y[m, n] = round(sum over splits, in split order) (+ bias)
+template <bool BF16>
+__global__ __launch_bounds__(256) void gemv_axis0_reduce_kernel(const float* __restrict__ part, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
+                                                                int M, int N, int splits) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t MN = static_cast<int64_t>(M) * N;
+  if (i >= MN) return;
+  const float s = a0_sum_splits(part, MN, i, splits);
+  y[i] = a0_finish<BF16>(s, bias, static_cast<int>(i % N));
+}
+
+// the grouped call's reduce, one launch for every member.  Plain: blockIdx.y is the member, finished as gemv_axis0_reduce_kernel finishes a layer.
+// SILU (two members of equal N, hence equal plans): thread i finishes gate[i] and up[i] as above — both rounded to the compute dtype — and writes
+// y[0][i] = silu_mul_el(gate, up), the bits hqq_hip_silu_mul gives on the two separately written outputs
+struct A0ReduceMember {
+  const float* part;
+  const uint16_t* bias;
+  uint16_t* y;
+  int N, splits;
+};
+struct A0ReduceGroup {
+  A0ReduceMember l[A0_MAX_GROUP];
+};
+
+template <bool BF16, bool SILU>
+__global__ __launch_bounds__(256) void gemv_axis0_grouped_reduce_kernel(const A0ReduceGroup g, int M) {
+  const A0ReduceMember& m = g.l[SILU ? 0 : blockIdx.y];
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t MN = static_cast<int64_t>(M) * m.N;
+  if (i >= MN) return;
+  const int n = static_cast<int>(i % m.N);
+  const uint16_t a = a0_finish<BF16>(a0_sum_splits(m.part, MN, i, m.splits), m.bias, n);
+  if constexpr (SILU) {
+    const uint16_t u = a0_finish<BF16>(a0_sum_splits(g.l[1].part, MN, i, g.l[1].splits), g.l[1].bias, n);
+    m.y[i] = silu_mul_el<BF16>(a, u);
+  } else {
+    m.y[i] = a;
   }
 }
 
@@ -259,6 +339,28 @@ static int a0_validate(int nbits, int64_t M, int64_t N, int64_t K, int64_t group
   return 0;
 }
 
+// the grouped call: every member must be a layer hqq_hip_gemv_axis0 covers (a0_validate names the first that is not), then the flags
+static int a0g_validate(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype, uint32_t opts, uint32_t flags) {
+  if (n_layers < 1 || n_layers > A0_MAX_GROUP) { set_error("hqq_hip_gemv_axis0_grouped: n_layers=%d outside [1,%d]", n_layers, A0_MAX_GROUP); return HQQ_ERR_SHAPE; }
+  if (!N) { set_error("hqq_hip_gemv_axis0_grouped: null argument"); return HQQ_ERR_SHAPE; }
+  for (int i = 0; i < n_layers; ++i)
+    if (const int rc = a0_validate(nbits, M, N[i], K, group_size, dtype, opts)) return rc;
+  if (flags & ~HQQ_BLOCK_SILU) {
+    set_error("hqq_hip_gemv_axis0_grouped: flags 0x%x are not covered (0 or HQQ_BLOCK_SILU)", flags);
+    return HQQ_ERR_UNSUPPORTED;
+  }
+  if ((flags & HQQ_BLOCK_SILU) && (n_layers != 2 || N[0] != N[1])) {
+    set_error("hqq_hip_gemv_axis0_grouped: HQQ_BLOCK_SILU is not covered here: it takes two layers (gate, up) of equal N");
+    return HQQ_ERR_UNSUPPORTED;
+  }
+  return 0;
+}
+
+// bytes of one member's partial-sum area (what hqq_hip_gemv_axis0_workspace_bytes adds to the counter head for the layer alone)
+static size_t a0_part_bytes(const A0Plan& p, int64_t M, int64_t N) {
+  return (static_cast<size_t>(p.splits) * M * N * sizeof(float) + 15) & ~static_cast<size_t>(15);
+}
+
 }  // namespace hqq
 
 using namespace hqq;
@@ -266,7 +368,7 @@ using namespace hqq;
 extern "C" size_t hqq_hip_gemv_axis0_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype) {
   if (a0_validate(nbits, M, N, K, group_size, dtype, 0)) return 0;
   const A0Plan p = a0_plan(nbits, N, K, group_size);
-  return WS_COUNTER_BYTES + ((static_cast<size_t>(p.splits) * M * N * sizeof(float) + 15) & ~static_cast<size_t>(15));
+  return WS_COUNTER_BYTES + a0_part_bytes(p, M, N);
 }
 
 extern "C" int hqq_hip_gemv_axis0(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias, void* y,
@@ -312,4 +414,80 @@ extern "C" int hqq_hip_gemv_axis0(int nbits, const void* x, const void* Wq, cons
   else
     hipLaunchKernelGGL(gemv_axis0_reduce_kernel<false>, dim3(rgrid), dim3(256), 0, st, part, static_cast<const uint16_t*>(bias), static_cast<uint16_t*>(y), Mi, Ni, p.splits);
   return check_launch("hqq_hip_gemv_axis0");
+}
+
+extern "C" size_t hqq_hip_gemv_axis0_grouped_workspace_bytes(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype,
+                                                            uint32_t flags) {
+  if (a0g_validate(nbits, n_layers, N, M, K, group_size, dtype, 0, flags)) return 0;
+  size_t bytes = WS_COUNTER_BYTES;
+  for (int i = 0; i < n_layers; ++i) bytes += a0_part_bytes(a0_plan(nbits, N[i], K, group_size), M, N[i]);
+  return bytes;
+}
+
+extern "C" int hqq_hip_gemv_axis0_grouped(int nbits, int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero,
+                                          const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype,
+                                          uint32_t opts, uint32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+  clear_stale_error();
+  if (const int rc = a0g_validate(nbits, n_layers, N, M, K, group_size, dtype, opts, flags)) return rc;
+  const bool silu = flags & HQQ_BLOCK_SILU;
+  if (!x || !Wq || !scale || !zero || !y) { set_error("hqq_hip_gemv_axis0_grouped: null argument"); return HQQ_ERR_SHAPE; }
+  if (!aligned16(x)) { set_error("hqq_hip_gemv_axis0_grouped: pointers must be 16-byte aligned"); return HQQ_ERR_ALIGN; }
+  for (int i = 0; i < n_layers; ++i) {
+    if (!Wq[i] || !scale[i] || !zero[i] || (!y[i] && !(silu && i == 1))) { set_error("hqq_hip_gemv_axis0_grouped: null argument (layer %d)", i); return HQQ_ERR_SHAPE; }
+    if (!aligned16(Wq[i]) || !aligned16(scale[i]) || !aligned16(zero[i])) {
+      set_error("hqq_hip_gemv_axis0_grouped: pointers must be 16-byte aligned (layer %d)", i);
+      return HQQ_ERR_ALIGN;
+    }
+  }
+  const size_t need = hqq_hip_gemv_axis0_grouped_workspace_bytes(nbits, n_layers, N, M, K, group_size, dtype, flags);
+  if (!workspace || workspace_bytes < need || !aligned16(workspace)) {
+    set_error("hqq_hip_gemv_axis0_grouped: needs %zu bytes of 16-byte aligned workspace (got %zu)", need, workspace_bytes);
+    return HQQ_ERR_WORKSPACE;
+  }
+  A0Group g;
+  A0ReduceGroup rg;
+  uint8_t* area = static_cast<uint8_t*>(workspace) + WS_COUNTER_BYTES;
+  int64_t items = 0, max_mn = 0;
+  for (int i = 0; i < A0_MAX_GROUP; ++i) {
+    A0Member& m = g.l[i];
+    A0ReduceMember& r = rg.l[i];
+    if (i >= n_layers) {   // never selected: no item reaches `end`, no reduce workgroup carries the index
+      m = A0Member{nullptr, nullptr, nullptr, nullptr, items, 0, 1, 1, 1, 1, 1};
+      r = A0ReduceMember{nullptr, nullptr, nullptr, 0, 0};
+      continue;
+    }
+    const A0Plan p = a0_plan(nbits, N[i], K, group_size);
+    items += p.items;
+    m = A0Member{static_cast<const uint8_t*>(Wq[i]), static_cast<const uint16_t*>(scale[i]), static_cast<const uint16_t*>(zero[i]),
+                 reinterpret_cast<float*>(area), items, static_cast<int>(N[i]), p.S, p.P, p.nblocks, p.upc, p.splits};
+    r = A0ReduceMember{m.part, bias ? static_cast<const uint16_t*>(bias[i]) : nullptr, static_cast<uint16_t*>(y[i]), m.N, p.splits};
+    area += a0_part_bytes(p, M, N[i]);
+    if (M * N[i] > max_mn) max_mn = M * N[i];
+  }
+  hipStream_t st = as_stream(stream);
+  const int grid = static_cast<int>((items + A0_WAVES - 1) / A0_WAVES);
+  const auto* xs = static_cast<const uint16_t*>(x);
+  const int Mi = static_cast<int>(M), Ki = static_cast<int>(K), units = static_cast<int>(K / A0_KU);
+#define HQQ_A0G_LAUNCH(NB, BF) hipLaunchKernelGGL((gemv_axis0_grouped_kernel<NB, BF>), dim3(grid), dim3(A0_WAVES * 64), 0, st, xs, g, Mi, Ki, units)
+  if (dtype == HQQ_BF16) {
+    if (nbits == 4) HQQ_A0G_LAUNCH(4, true); else HQQ_A0G_LAUNCH(2, true);
+  } else {
+    switch (nbits) {
+      case 8: HQQ_A0G_LAUNCH(8, false); break;
+      case 4: HQQ_A0G_LAUNCH(4, false); break;
+      case 2: HQQ_A0G_LAUNCH(2, false); break;
+      default: HQQ_A0G_LAUNCH(1, false); break;
+    }
+  }
+#undef HQQ_A0G_LAUNCH
+  if (const int rc = check_launch("hqq_hip_gemv_axis0_grouped")) return rc;
+  const dim3 rgrid(static_cast<unsigned>((max_mn + 255) / 256), silu ? 1u : static_cast<unsigned>(n_layers));
+  if (dtype == HQQ_BF16) {
+    if (silu) hipLaunchKernelGGL((gemv_axis0_grouped_reduce_kernel<true, true>), rgrid, dim3(256), 0, st, rg, Mi);
+    else hipLaunchKernelGGL((gemv_axis0_grouped_reduce_kernel<true, false>), rgrid, dim3(256), 0, st, rg, Mi);
+  } else {
+    if (silu) hipLaunchKernelGGL((gemv_axis0_grouped_reduce_kernel<false, true>), rgrid, dim3(256), 0, st, rg, Mi);
+    else hipLaunchKernelGGL((gemv_axis0_grouped_reduce_kernel<false, false>), rgrid, dim3(256), 0, st, rg, Mi);
+  }
+  return check_launch("hqq_hip_gemv_axis0_grouped");
 }

@@ -602,6 +602,75 @@ def gemv_axis0(x: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, bias, N: int
     return out.reshape(*x.shape[:-1], N)
 
 
+AXIS0_MAX_GROUP = 3   # layers per hqq_hip_gemv_axis0_grouped call
+
+
+def axis0_grouped_covers(dtype, M, Ns, K, group_size, nbits, flags: int = 0) -> bool:
+    """what hqq_hip_gemv_axis0_grouped serves: 1..AXIS0_MAX_GROUP layers, each one decode_axis0_covers() takes at M rows (group_size None is
+    the one-group-per-column setting and needs every N equal, since the group shares one group_size); flags 0, or BLOCK_SILU on two layers
+    of equal N"""
+    Ns = tuple(int(n) for n in Ns)
+    if not 1 <= len(Ns) <= AXIS0_MAX_GROUP:
+        return False
+    if group_size is None:
+        if len(set(Ns)) != 1:
+            return False
+        group_size = Ns[0]
+    if not all(decode_axis0_covers(dtype, M, N, K, group_size, nbits) for N in Ns):
+        return False
+    flags = int(flags)
+    if flags & ~BLOCK_SILU:
+        return False
+    return not (flags & BLOCK_SILU) or (len(Ns) == 2 and Ns[0] == Ns[1])
+
+
+def gemv_axis0_grouped(x: Tensor, layers, K: int, group_size, nbits: int, outs=None, flags: int = 0):
+    """gemv_axis0 for up to AXIS0_MAX_GROUP axis-0 layers that consume the same x [*, K] of 1..GEMV_MAX_M rows, in one launch + one reduce
+    (hqq_hip_gemv_axis0_grouped).  layers: sequence of (W_q, scale, zero, bias_or_None, N), sharing group_size (None = N, all N equal) and
+    nbits.  Returns the list of outputs [*, N_i], each the bits gemv_axis0 gives for that layer.  flags=BLOCK_SILU (layers = gate, up of
+    equal N): ONE output, silu_mul(gate's output, up's output) bit for bit.  Raises NotImplementedError outside axis0_grouped_covers()."""
+    n = len(layers)
+    if not 1 <= n <= AXIS0_MAX_GROUP:
+        raise ValueError(f"hqq_amd: an axis-0 GEMV group holds 1..{AXIS0_MAX_GROUP} layers, got {n}")
+    if x.shape[-1] != K:
+        raise ValueError(f"hqq_amd: x has {x.shape[-1]} features, layers expect {K}")
+    Ns = [int(L[4]) for L in layers]
+    if group_size is None and len(set(Ns)) != 1:
+        raise ValueError("hqq_amd: group_size None (one group per column) needs layers of equal N in one group")
+    gs = Ns[0] if group_size is None else int(group_size)
+    for (W_q, s, z, b, N) in layers:
+        _dev(x, W_q, s, z, b)
+        if x.dtype != s.dtype or z.dtype != s.dtype or (b is not None and b.dtype != s.dtype):
+            raise TypeError("hqq_amd: x / scale / zero / bias must share the compute dtype")
+        if s.numel() != (N * K) // gs or z.numel() != (N * K) // gs:
+            raise ValueError(f"hqq_amd: gemv_axis0_grouped needs {(N * K) // gs} scale / zero values per layer (N * K / group_size), got {s.numel()} / {z.numel()}")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    flags = int(flags)
+    out_Ns = Ns[:1] if flags & BLOCK_SILU else Ns
+    if outs is None:
+        outs = [torch.empty((M, N), dtype=x.dtype, device=x.device) for N in out_Ns]
+    if len(outs) != len(out_Ns) or any(o.numel() != M * N or o.dtype != x.dtype or not o.is_contiguous() for o, N in zip(outs, out_Ns)):
+        raise ValueError(f"hqq_amd: gemv_axis0_grouped writes {len(out_Ns)} dense outputs of {M} x {out_Ns} elements in x's dtype")
+    if M > 0:
+        L = _C.lib()
+        VP = ctypes.c_void_p * n
+        Nc = (ctypes.c_int64 * n)(*Ns)
+        has_bias = any(Lr[3] is not None for Lr in layers)
+        keep = [[t.contiguous() for t in Lr[:3]] for Lr in layers]   # (alive until the launch is enqueued)
+        with torch.cuda.device(x.device):
+            need = int(L.hqq_hip_gemv_axis0_grouped_workspace_bytes(int(nbits), n, Nc, M, int(K), gs, _dt(x.dtype), flags))
+            ws = reserve_workspace(x.device, need) if need else None
+            rc = L.hqq_hip_gemv_axis0_grouped(
+                int(nbits), n, _p(x2), VP(*[_p(k[0]) for k in keep]), VP(*[_p(k[1]) for k in keep]), VP(*[_p(k[2]) for k in keep]),
+                VP(*[_p(Lr[3]) for Lr in layers]) if has_bias else None, VP(*([_p(o) for o in outs] + [None] * (n - len(outs)))), Nc,
+                M, int(K), gs, _dt(x.dtype), 0, flags, _p(ws), 0 if ws is None else ws.numel(), _stream())
+        _C.check(rc, "hqq_hip_gemv_axis0_grouped")
+    return [o.reshape(*x.shape[:-1], N) for o, N in zip(outs, out_Ns)]
+
+
 def _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts) -> Tensor:
     """axis-0 layers: decode sizes through hqq_hip_gemv_axis0; everything else as HQQLinear has always run them — the HIP dequantise kernel
     (axis 0) + torch.matmul, then `out += bias` (quantize.py:880-898)"""

@@ -56,14 +56,21 @@ class GraphedGreedyDecoder:
     """fused=True (default): a Llama-shaped model whose decoder linears are HQQLinearHIP layers decodes through hqq_amd.utils.llama_fused —
     RMSNorm (+ the residual adds), rotary + KV-cache write and SiLU * up as one HIP kernel each around the grouped GEMVs, HF's own attention
     function on HF's cache: the same tokens in a third of the launches; since round 5 (glue="auto") the RMSNorms, the residual adds and SiLU * up
-    ride inside the GEMV launches themselves: 5 launches + attention per decoder block.  Any other model, or fused=False: the model's own forward."""
+    ride inside the GEMV launches themselves: 5 launches + attention per decoder block.  Any other model, or fused=False: the model's own forward.
+    axis0: what a model quantised along AXIS 0 decodes through.  "model" (default): the model's own forward, as before.  "fused" (opt-in): where
+    llama_fused.supports_axis0 accepts the model, the fused step with q|k|v and gate|up (+ SiLU * up) as one grouped axis-0 launch each
+    (`fused_axis0`; `fused` stays the axis-1 flag), and generate_batch's batched step where supports_axis0_batch accepts the batch."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
-                 do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5):
+                 do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model"):
         from transformers import StaticCache
         from . import llama_fused
+        if axis0 not in ("model", "fused"):
+            raise ValueError("axis0: 'model' or 'fused'")
         self.model = model.eval()
         self.fused = bool(fused) and llama_fused.supports(model)
+        self.axis0 = axis0
+        self.fused_axis0 = bool(fused) and axis0 == "fused" and not self.fused and llama_fused.supports_axis0(model)
         self._fused_mod = llama_fused
         self.attention = attention   # "sdpa": HF's attention function (token-identical to model(...)); "hip": the decode-attention kernel (faster, within rounding)
         self.glue = glue             # "auto" / "folded": RMSNorm, residual adds and SiLU * up inside the GEMV launches (csrc/gemv_block.hip); "kernels": round 4's separate glue kernels
@@ -174,9 +181,10 @@ class GraphedGreedyDecoder:
             self.pos = torch.tensor([T], device=self.device)
             self._state = (self.tok, self.next_tok, self.pos)
             self.step = None
-            if self.fused:
+            if self.fused or self.fused_axis0:
                 try:
-                    self.step = self._fused_mod.FusedLlamaStep(self.model, self.cache, self.max_cache_len, attention=self.attention, glue=self.glue)
+                    self.step = self._fused_mod.FusedLlamaStep(self.model, self.cache, self.max_cache_len, attention=self.attention,
+                                                               glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0)
                 except ValueError:   # a cache layout / attention configuration the fused step does not restate: the model's own forward serves
                     self.step = None
             self.graph = None
@@ -314,7 +322,7 @@ class GraphedGreedyDecoder:
     def _batch_state(self, B: int):
         """the kept state of generate_batch at B rows, or None when the batched step does not serve the model there"""
         fm = self._fused_mod
-        if not (self.fused and fm.supports_batch(self.model, B)):
+        if not ((self.fused and fm.supports_batch(self.model, B)) or (self.fused_axis0 and fm.supports_axis0_batch(self.model, B))):
             return None
         cfg = self.model.config
         n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
@@ -322,7 +330,7 @@ class GraphedGreedyDecoder:
         cache = self._StaticCache(config=cfg, max_cache_len=self.max_cache_len)
         cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
         try:
-            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention)
+            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0)
         except ValueError:
             return None
         st = {"B": B, "cache": cache, "scratch": self._StaticCache(config=cfg, max_cache_len=self.max_cache_len), "step": step,
@@ -420,9 +428,11 @@ class HFGenerator:
     a prompt that leaves less than max_new_tokens of cache generates what fits."""
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
-                 compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True):
+                 compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
+        if axis0 not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts an axis-0 model into the fused decode step)
+            raise ValueError("axis0: 'model' or 'fused'")
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -434,7 +444,7 @@ class HFGenerator:
         self.is_compiled = compile is not None
         self.use_graph = compile is not None
         self.compile_options = compile_options
-        self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k)
+        self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0)
         self.init()
 
     @staticmethod

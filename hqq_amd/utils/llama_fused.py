@@ -12,6 +12,11 @@ ONE paired gate|up layer (RMSNorm prologue, SiLU * up epilogue) -> down with the
 HF's function on HF's cache tensors, so the step emits the same tokens as `model(...)` does on the same kernels — and as the same model
 under HQQBackend.PYTORCH_FORWARD does on the reference's arithmetic (tests/test_model_gpu.py).
 
+Models quantised along AXIS 0 (supports_axis0; opt-in through GraphedGreedyDecoder(axis0="fused")) take the glue="kernels" sequence with the axis-0 kernels:
+    add_rmsnorm -> q|k|v (ops.gemv_axis0_grouped) -> rope_cache -> attention -> o (ops.gemv_axis0) -> add_rmsnorm -> gate|up (ops.gemv_axis0_grouped with
+    SiLU * up in its reduce) -> down (ops.gemv_axis0)
+= 11 launches + the attention's (10 with attention="hip"), on the layers' own tensors.
+
 Only what the step needs is taken from the model: module weights and the HF StaticCache's tensors are used in place (nothing is copied).
 """
 from __future__ import annotations
@@ -86,16 +91,63 @@ def supports(model) -> bool:
         return False
 
 
+def _supports_axis0_rows(model, M: int) -> bool:
+    if not arch_supported(model):
+        return False
+    try:
+        inner = model.model
+        dt = inner.norm.weight.dtype
+        if dt not in (torch.float16, torch.bfloat16):
+            return False
+        if not hasattr(inner, "rotary_emb") or not hasattr(inner, "embed_tokens") or not hasattr(model, "lm_head"):
+            return False
+        for blk in inner.layers:
+            at, mlp = blk.self_attn, blk.mlp
+            lin = [_hip(getattr(at, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
+            if not all(isinstance(L, HQQLinearHIP) and L.bias is None and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == 0 for L in lin):
+                return False
+            q, k, v, o, g, u, d = lin
+            if len({(L.nbits, L.group_size, L.in_features) for L in (q, k, v)}) != 1 or len({(L.nbits, L.group_size, L.in_features, L.out_features) for L in (g, u)}) != 1:
+                return False
+            if not ops.axis0_grouped_covers(dt, M, [L.out_features for L in (q, k, v)], q.in_features, q.group_size, q.nbits) or \
+                    not ops.axis0_grouped_covers(dt, M, [g.out_features, u.out_features], g.in_features, g.group_size, g.nbits, ops.BLOCK_SILU):
+                return False
+            if not all(ops.decode_axis0_covers(dt, M, L.out_features, L.in_features, L.group_size, L.nbits) for L in (o, d)):
+                return False
+            for nrm in (blk.input_layernorm, blk.post_attention_layernorm):
+                if nrm.weight.dtype != dt or nrm.weight.shape[0] % 8:
+                    return False
+        return True
+    except AttributeError:
+        return False
+
+
+def supports_axis0(model) -> bool:
+    """supports() for a model quantised along AXIS 0: an allow-listed architecture (arch_supported), fp16 or bf16, every decoder linear an HQQLinearHIP
+    with axis == 0 and no bias; q|k|v share (nbits, group_size) and gate|up share them with equal N, so that each group is ONE grouped launch
+    (ops.axis0_grouped_covers, gate|up with BLOCK_SILU); o and down on the single-layer kernel (ops.decode_axis0_covers)"""
+    return _supports_axis0_rows(model, 1)
+
+
+def supports_axis0_batch(model, B: int) -> bool:
+    """supports_axis0(model) with every launch taking B activation rows (1 <= B <= ops.GEMV_MAX_M)"""
+    B = int(B)
+    return 1 <= B <= ops.GEMV_MAX_M and _supports_axis0_rows(model, B)
+
+
 class FusedLlamaStep:
     """decode step t -> logits of token t + 1, on the model's own weights and an HF StaticCache that a prefill has filled"""
 
-    def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto"):
+    def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
         glue: "folded" — RMSNorm in the q|k|v / gate|up launches' prologue, the residual adds in o's / down's epilogue, SiLU * up in the epilogue of ONE
         paired gate|up layer (csrc/gemv_block.hip: 4 launches + rotary / attention per block; costs a second copy of gate / up's packed levels in the
         paired layout); "kernels" — round 4's separate glue kernels (9 launches per block); "auto": folded where hqq_hip_gemv_block covers the model."""
+        # axis0: the model's linears are quantised along axis 0 (supports_axis0).  The step is the glue="kernels" sequence with q|k|v and gate|up through
+        # ops.gemv_axis0_grouped (gate|up's reduce applies SiLU * up: no silu_mul launch) and o / down through ops.gemv_axis0, on the layers' own tensors
+        # (nothing re-laid out); the folded launches read axis-1 meta and are never taken.
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
         self.model = model
@@ -118,9 +170,15 @@ class FusedLlamaStep:
         self.attention = attention
         if glue not in ("auto", "folded", "kernels"):
             raise ValueError("glue: 'auto', 'folded' or 'kernels'")
+        self.axis0 = bool(axis0)
+        if self.axis0 and not supports_axis0(model):
+            raise ValueError("hqq_amd: axis0=True needs a model supports_axis0() accepts")
+        if self.axis0 and glue == "folded":
+            raise ValueError("hqq_amd: glue='folded' reads axis-1 meta; an axis-0 model takes the separate glue kernels")
         lins = [_hip(getattr(b.self_attn, n)) for b in inner.layers for n in ("q_proj", "o_proj")] + [_hip(getattr(b.mlp, n)) for b in inner.layers for n in ("gate_proj", "down_proj")]
         can_fold = all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=(i % 2 == 0)) for i, L in enumerate(lins)) and \
-            all(_hip(b.mlp.gate_proj).out_features == _hip(b.mlp.up_proj).out_features for b in inner.layers) and not (ops._default_opts & ops.OPT_FACTORED)
+            all(_hip(b.mlp.gate_proj).out_features == _hip(b.mlp.up_proj).out_features for b in inner.layers) and not (ops._default_opts & ops.OPT_FACTORED) and \
+            not self.axis0
         if glue == "folded" and not can_fold:
             raise ValueError("hqq_amd: glue='folded' needs fp16 / bf16 layers of 4 / 2 bits or the 3-bit stream layout, group_size 64, hidden size <= 8192")
         self.folded = can_fold and glue != "kernels"
@@ -206,7 +264,7 @@ class FusedLlamaStep:
         self.ninf = torch.full((), float("-inf"), dtype=dt, device=dev)
         # the front of a step as one launch (ops.token_prologue) where it is a plain table lookup: an ordinary nn.Embedding in the compute dtype and precomputed rotary tables
         emb = inner.embed_tokens
-        self.one_launch_front = bool(glue != "kernels" and self.cos_tab is not None and type(emb) is torch.nn.Embedding and emb.max_norm is None and emb.weight.dtype == dt
+        self.one_launch_front = bool((glue != "kernels" or self.axis0) and self.cos_tab is not None and type(emb) is torch.nn.Embedding and emb.max_norm is None and emb.weight.dtype == dt
                                      and emb.weight.is_contiguous() and emb.weight.device == self.h.device and self.H % 8 == 0 and dt in (torch.float16, torch.bfloat16))
         self.cos_v = torch.empty(self.hd, dtype=dt, device=dev)
         self.sin_v = torch.empty(self.hd, dtype=dt, device=dev)
@@ -253,7 +311,10 @@ class FusedLlamaStep:
                 ops.gemv_block(h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], [b["q"], b["k"], b["v"]], ops.BLOCK_NORM, opts=b["qkv_opts"])
             else:
                 ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
-                ops.gemv_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]], opts=b["qkv_opts"])
+                if self.axis0:
+                    ops.gemv_axis0_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]])
+                else:
+                    ops.gemv_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]], opts=b["qkv_opts"])
             if self.attention == "hip":   # rotary + cache write + attention: one launch
                 att = ops.rope_attn_decode(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
                                            workspace=self.attn_ws.get(splits))
@@ -268,6 +329,13 @@ class FusedLlamaStep:
                                opts=ops.layer_opts(o.opts))
                 ops.gemv_block(h, b["n2"].weight, b["n2"].variance_epsilon, b["gu_pair"], K, b["gu_gs"], b["gu_nbits"], [b["a"]], ops.BLOCK_NORM | ops.BLOCK_SILU, opts=b["gu_pair_opts"])
                 ops.gemv_block(b["a"], None, 0.0, [(d.W_q, d.scale, d.zero, d.out_features)], d.in_features, d.group_size, d.nbits, [h], ops.BLOCK_RESID, opts=ops.layer_opts(d.opts))
+                continue
+            if self.axis0:   # o -> norm -> gate|up with SiLU * up in its reduce -> down: the layers' own axis-0 tensors
+                ops.gemv_axis0(att.reshape(1, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta)
+                ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
+                ops.gemv_axis0_grouped(self.xn, b["gu"], K, b["gu_gs"], b["gu_nbits"], outs=[b["a"]], flags=ops.BLOCK_SILU)
+                ops.gemv_axis0(b["a"], d.W_q, d.scale, d.zero, None, d.out_features, d.in_features, d.group_size, d.nbits, out=self.delta)
+                delta = self.delta
                 continue
             ops.gemv(att.reshape(1, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta,
                      opts=ops.layer_opts(o.opts))
@@ -327,7 +395,9 @@ class FusedLlamaBatchStep:
     rope_attn_decode_batched.  Row b of every glue kernel gives the bits of the batch-1 kernel for sequence b alone; the linears run at M = B
     (supports_batch).  The folded launches (ops.gemv_block) are batch-1 only and never used here."""
 
-    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa"):
+    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False):
+        """axis0: the model is quantised along axis 0 (supports_axis0_batch): q|k|v and gate|up through ops.gemv_axis0_grouped (SiLU * up in gate|up's
+        reduce, no silu_mul launch), o and down through ops.gemv_axis0, as in FusedLlamaStep(axis0=True)"""
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
         self.model = model
@@ -349,8 +419,10 @@ class FusedLlamaBatchStep:
                                    or max_cache_len > 30000):
             raise ValueError("hqq_amd: the decode-attention kernel covers plain softmax attention with head_dim 64 / 128 / 256 and caches of <= 30000 positions")
         self.attention = attention
-        if not supports_batch(model, B):
-            raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows (supports_batch)")
+        self.axis0 = bool(axis0)
+        if not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
+            raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows "
+                             f"({'supports_axis0_batch' if self.axis0 else 'supports_batch'})")
         self.blocks = []
         for li, (blk, (q, k, v, o, g, u, d)) in enumerate(zip(inner.layers, _decoder_linears(model))):
             lay = cache.layers[li]
@@ -418,7 +490,10 @@ class FusedLlamaBatchStep:
         for b in self.blocks:
             at = b["attn"]
             ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
-            ops.gemv_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]], opts=b["qkv_opts"])
+            if self.axis0:
+                ops.gemv_axis0_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]])
+            else:
+                ops.gemv_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]], opts=b["qkv_opts"])
             if self.attention == "hip":   # rotary + cache write + attention: one launch
                 att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
                                                    workspace=self.attn_ws.get(splits))
@@ -426,6 +501,13 @@ class FusedLlamaBatchStep:
                 ops.rope_cache_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
                 att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :, :kvl], b["vc"][:, :, :kvl], mask, dropout=0.0, scaling=at.scaling)
             o, d = b["o"], b["d"]
+            if self.axis0:
+                ops.gemv_axis0(att.reshape(B, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta)
+                ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
+                ops.gemv_axis0_grouped(self.xn, b["gu"], K, b["gu_gs"], b["gu_nbits"], outs=[b["a"]], flags=ops.BLOCK_SILU)
+                ops.gemv_axis0(b["a"], d.W_q, d.scale, d.zero, None, d.out_features, d.in_features, d.group_size, d.nbits, out=self.delta)
+                delta = self.delta
+                continue
             ops.gemv(att.reshape(B, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta,
                      opts=ops.layer_opts(o.opts))
             ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)

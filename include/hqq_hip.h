@@ -339,6 +339,22 @@ size_t hqq_hip_gemv_axis0_workspace_bytes(int nbits, int64_t M, int64_t N, int64
 int hqq_hip_gemv_axis0(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias, void* y,
                        int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* hqq_hip_gemv_axis0 for 1 <= n_layers <= 3 axis-0 layers that consume the SAME activation rows x[M, K] (q|k|v, gate|up), in one contraction launch
+ * and one reduce launch.  Per-layer arguments are host arrays of n_layers entries as in hqq_hip_gemv_grouped (read during the call, not kept;
+ * bias may be NULL or hold NULL entries); the layers share K, group_size, nbits and dtype, each has its own N[i], and each must be a layer
+ * hqq_hip_gemv_axis0 covers (same error codes; validated before anything is launched).  The layers' work items are concatenated, every layer keeps
+ * the K split it has on its own and its partial sums are added in split order: y[i] holds the bits a hqq_hip_gemv_axis0 call on layer i gives.
+ * flags: 0, or HQQ_BLOCK_SILU (below) — n_layers == 2 with N[0] == N[1] (gate, up): the reduce finishes both outputs as above (rounded to dtype, bias
+ * added with one more rounding) and writes only y[0][m, n] = T(silu(gate)) * up, the bits hqq_hip_silu_mul gives on the two outputs of the unflagged
+ * call; y[1] is not read.  Every other flag, and HQQ_BLOCK_SILU on another group: HQQ_ERR_UNSUPPORTED.
+ * Workspace: hqq_hip_gemv_axis0_grouped_workspace_bytes(...) — the counter head (untouched) plus the sum of the layers' partial-sum areas, i.e. of
+ * hqq_hip_gemv_axis0_workspace_bytes(layer i) minus the head; 0 where the call would be refused.
+ * The two symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits. */
+size_t hqq_hip_gemv_axis0_grouped_workspace_bytes(int nbits, int n_layers, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype,
+                                                  uint32_t flags);
+int hqq_hip_gemv_axis0_grouped(int nbits, int n_layers, const void* x, const void* const* Wq, const void* const* scale, const void* const* zero,
+                               const void* const* bias, void* const* y, const int64_t* N, int64_t M, int64_t K, int64_t group_size, int dtype,
+                               uint32_t opts, uint32_t flags, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
