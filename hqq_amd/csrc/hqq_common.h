@@ -158,7 +158,8 @@ template <> struct CD<bf16_t> {
 
 // Layout of the caller-owned decode workspace (hqq_hip_gemv_workspace_bytes): [arrival counters | fp32 partial sums].  The head holds
 // one int per (panel, row group) of a split-K launch (skinny.hip) and must be zero whenever a call starts — every kernel that uses
-// counters leaves them zero — so kernels that only park partial sums (gemv3s.hip) keep out of it.
+// counters leaves them zero — so kernels that only park partial sums (gemv3s.hip, gemm_pipe.hip, gemv_axis0.hip) keep out of it.  The partial
+// sums behind the head hold anything on entry: every kernel writes a slot before it reads it (tests/test_workspace_contract_gpu.py).
 constexpr size_t WS_COUNTER_BYTES = size_t(256) << 10;
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

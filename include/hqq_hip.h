@@ -83,9 +83,12 @@ int hqq_hip_dequantize(int nbits, const void* Wq, const void* scale, const void*
  * (the caller may compose hqq_hip_dequantize + its own GEMM).
  * Workspace: launches of 5..64 rows that split K, and 3-bit launches of >= 19 MB of packed weights, park fp32 partial sums (and
  * arrival counters) in a caller-owned workspace of hqq_hip_gemv_workspace_bytes(...) bytes (0 = this call needs none; then
- * workspace may be NULL).  Contract: 16-byte aligned device memory, ZERO when first used — the caller clears it once when
- * allocating it; every call leaves the counter area zero again — and not shared by calls that may run concurrently.  A larger
- * workspace than asked for is fine: one buffer sized for the largest launch serves a whole model.
+ * workspace may be NULL).  Contract: 16-byte aligned device memory, not shared by calls that may run concurrently.  Only its first
+ * 256 KiB — the arrival counters — must be ZERO when a call starts: the caller clears them once when allocating the buffer, and every
+ * call leaves them zero again (only HQQ_ROUTE_SKINNY uses them; every other route keeps out of them).  What lies behind them is
+ * unspecified on entry and on return: every call writes each partial sum before it reads it, so no result depends on what the buffer
+ * held — routes may alternate on one buffer.  A larger workspace than asked for is fine: one buffer sized for the largest launch serves
+ * a whole model.
  *
  * Routes: which kernel serves a call.  One planner in the library decides it for every entry point and query; hqq_hip_forward_route asks it
  * for hqq_hip_forward (n_layers = 1) or a group (hqq_hip_gemv_grouped / hqq_hip_gemm_grouped) without launching: a route, or the negative

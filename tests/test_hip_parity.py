@@ -309,6 +309,9 @@ def test_skinny_split_k_reproducible_bits(ops):
     for _ in range(200):
         for y, want in zip(ops.gemv_grouped(x, layers, K, gs, nbits), first): assert torch.equal(y, want)
         assert torch.equal(ops.gemv(x, *layers[0][:4], 4096, K, gs, nbits), single)
+    torch.cuda.synchronize()
+    head = ops._ws_cur[torch.cuda.current_device()][:256 << 10]   # WS_COUNTER_BYTES: one arrival counter per (panel, row group)
+    assert int(torch.count_nonzero(head)) == 0, "the finishing split of every row group must leave its arrival counter at zero"
 
 
 def test_skinny_gemm_grouped_and_capture(ops):
