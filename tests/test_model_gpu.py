@@ -241,7 +241,9 @@ def _toy_llama_hip(nbits):
 def test_decode_attention_kernel_against_fp64_softmax_attention_and_sdpa(n_heads, n_kv, hd, L, pos, dt):
     """hqq_hip_attn_decode (opt-in replacement of the SDPA call of a decode step): one query per head over the first pos + 1 cache positions —
     against softmax attention in float64 on the same fp16 inputs (1e-3 + one fp16 ulp of the output) and against torch's SDPA with the additive
-    mask the fused step builds (2e-3: SDPA itself rounds the probabilities to fp16); positions beyond pos are NaN-poisoned and must not be read"""
+    mask the fused step builds (2e-3: SDPA itself rounds the probabilities to fp16); positions beyond pos are NaN-poisoned and must not be read.
+    With randn inputs one key carries about 1 / n of the output, so this tolerance does not resolve a single dropped, duplicated or mis-weighted
+    key above about 1000 positions: tests/test_attn_keys_gpu.py pins the kernel key by key"""
     from hqq_amd import ops
     g = torch.Generator(device="cuda").manual_seed(n_heads * 1000 + pos)
     q = torch.randn(n_heads, hd, device="cuda", generator=g).to(dt)
