@@ -64,6 +64,9 @@ SYMBOLS = {
     # up to three axis-0 layers on the same rows in one launch (+ one reduce, optionally with SiLU * up)
     "hqq_hip_gemv_axis0_grouped_workspace_bytes": (_sz, [_i32, _i32, _vp, _i64, _i64, _i64, _i32, _u32]),
     "hqq_hip_gemv_axis0_grouped": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _u32, _u32, _vp, _sz, _vp]),
+    # axis-0 layers at 17..256 rows (csrc/gemm_axis0.hip)
+    "hqq_hip_gemm_axis0_workspace_bytes": (_sz, [_i32, _i64, _i64, _i64, _i64, _i32]),
+    "hqq_hip_gemm_axis0": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _sz, _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

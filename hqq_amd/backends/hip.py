@@ -82,7 +82,7 @@ class HQQLinearHIP(nn.Module):
         m = getattr(hqq_layer, "meta", None)
         if m is None or not m.get("packing"):
             return False
-        if m["axis"] == 0:   # the axis-0 decode kernel (hqq_hip_gemv_axis0) at one row: byte containers, channel-wise meta
+        if m["axis"] == 0:   # the layers the axis-0 kernels take (asked at one row; ops.forward(axis=0) picks the kernel by the rows of each call): byte containers, channel-wise meta
             N, K = (int(v) for v in m["shape"])
             gs = int(m["group_size"]) if m["group_size"] else N
             return (m["packing"] in ("8bit_u8", "4bit_u8", "2bit_u8", "1bit_u8") and gs > 0 and N % gs == 0 and m["scale"].numel() == N * K // gs
@@ -111,7 +111,8 @@ class HQQLinearHIP(nn.Module):
         rows = x.numel() // x.shape[-1]
         # every number of rows through ops.forward: decode kernels, skinny GEMM, pipelined GEMM, and beyond them (long prompts, shapes the fused
         # kernels do not cover) the dequantise kernel + the in-tree dense GEMM; a 3-bit layer in the stream layout says so in its option bits.
-        # Axis-0 layers: the axis-0 decode kernel up to 16 rows, beyond it the route HQQLinear takes (dequantise kernel + torch.matmul)
+        # Axis-0 layers: the axis-0 decode kernel up to 16 rows, hqq_hip_gemm_axis0 from 17 to ops.AXIS0_GEMM_ROUTE_MAX_M rows, beyond it the route
+        # HQQLinear takes (dequantise kernel + torch.matmul)
         return ops.forward(x, self.W_q, self.scale, self.zero, self.bias, self.out_features, self.in_features, self.group_size, self.nbits,
                            opts=ops.layer_opts(self.opts), axis=self.axis)
 

@@ -482,16 +482,17 @@ class HQQLinear(nn.Module):
     def _fused_ok(self, x: Tensor) -> bool:
         """fp16 / bf16 layers quantised along axis 1 go through hqq_amd.ops.forward for every number of rows: the fused kernels where they
         cover the shape, the HIP dequantise kernel + the in-tree dense MFMA GEMM elsewhere (ops.forward decides).  Anything else —
-        fp32 compute dtype, axis 0 (decode sizes: _axis0_decode_ok), group sizes that are not multiples of 16, quantised meta — keeps the reference's
+        fp32 compute dtype, axis 0 (up to ops.AXIS0_GEMM_ROUTE_MAX_M rows: _axis0_kernel_ok), group sizes that are not multiples of 16, quantised meta — keeps the reference's
         dequantise + matmul"""
         m = self.meta
         return (m["axis"] == 1 and bool(m["group_size"]) and m["group_size"] % 16 == 0 and x.dtype == m["scale"].dtype
                 and x.dtype in (float16, torch.bfloat16) and m["packing"] in ("8bit_u8", "4bit_u8", "3bit_32", "2bit_u8", "1bit_u8")
                 and x.is_cuda and self.W_q.is_cuda)
 
-    def _axis0_decode_ok(self, x: Tensor) -> bool:
-        """a layer quantised along axis 0 whose call the axis-0 decode kernel serves (hqq_amd.ops.decode_axis0_covers: byte containers, fp16 / bf16,
-        group_size % 16 == 0 dividing out_features, in_features % 64 == 0, at most 16 rows); every other axis-0 call keeps dequantise + matmul"""
+    def _axis0_kernel_ok(self, x: Tensor) -> bool:
+        """a layer quantised along axis 0 whose call an axis-0 kernel serves through hqq_amd.ops.forward(axis=0): byte containers, fp16 / bf16,
+        group_size % 16 == 0 dividing out_features, in_features % 64 == 0; at most 16 rows on the decode kernel (ops.decode_axis0_covers), from 17 to
+        ops.AXIS0_GEMM_ROUTE_MAX_M rows on hqq_hip_gemm_axis0 (ops.gemm_axis0_covers); every other axis-0 call keeps dequantise + matmul"""
         m = self.meta
         if m["axis"] != 0 or m["packing"] not in ("8bit_u8", "4bit_u8", "2bit_u8", "1bit_u8") or not (x.is_cuda and self.W_q.is_cuda):
             return False
@@ -499,7 +500,8 @@ class HQQLinear(nn.Module):
         gs = int(m["group_size"]) if m["group_size"] else N
         if gs <= 0 or N % gs or m["scale"].numel() != N * K // gs or x.dtype != m["scale"].dtype or m["zero"].dtype != x.dtype:
             return False   # (channel_wise=False stores one constant pair for the whole tensor)
-        return ops.decode_axis0_covers(x.dtype, x.numel() // K, N, K, gs, Quantizer._packing_bits[m["packing"]])
+        rows, nbits = x.numel() // K, Quantizer._packing_bits[m["packing"]]
+        return ops.decode_axis0_covers(x.dtype, rows, N, K, gs, nbits) or (rows <= ops.AXIS0_GEMM_ROUTE_MAX_M and ops.gemm_axis0_covers(x.dtype, rows, N, K, gs, nbits))
 
     def forward_hip(self, x: Tensor) -> Tensor:
         """Fused unpack -> dequantize -> GEMV / GEMM (one launch); shapes and prompt lengths the fused kernels do not cover run the HIP
@@ -530,11 +532,11 @@ class HQQLinear(nn.Module):
         return c[1], c[2]   # (in-place edits through W_q.data / meta[...].data bypass the version counters: call .cuda(device) again — it drops the copy — after such an edit)
 
     def _matmul_hip(self, x: Tensor, transpose: bool = True, bias=None) -> Tensor:
-        if transpose and self._axis0_decode_ok(x):
+        if transpose and self._axis0_kernel_ok(x):
             m = self.meta
             N, K = m["shape"]
             W_q = self.W_q.view(m["unpack_view_dtype"]) if m["view_as_float"] else self.W_q
-            return ops.gemv_axis0(x, W_q, m["scale"], m["zero"], bias, int(N), int(K), m["group_size"], Quantizer._packing_bits[m["packing"]], opts=0)
+            return ops.forward(x, W_q, m["scale"], m["zero"], bias, int(N), int(K), m["group_size"], Quantizer._packing_bits[m["packing"]], opts=0, axis=0)
         if transpose and self._fused_ok(x):
             m = self.meta
             N, K = m["shape"]

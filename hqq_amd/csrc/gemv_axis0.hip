@@ -20,13 +20,12 @@
 // Grouped (hqq_hip_gemv_axis0_grouped): up to three layers on the same x — q|k|v, gate|up — as ONE contraction launch over their concatenated work
 // items and ONE reduce launch; each layer keeps its own plan and partial-sum area, so its output is the single-layer call's bit for bit.  The
 // reduce can finish gate|up as silu(gate) * up (HQQ_BLOCK_SILU, block_math.h's silu_mul_el on the two rounded outputs).
+#include "axis0_common.h"
 #include "block_math.h"
-#include "decode_common.h"
 
 namespace hqq {
 
 constexpr int A0_WAVES = 4;             // waves per workgroup (independent work items, no LDS)
-constexpr int A0_KU = 64;               // k per unit: 16 per lane group
 constexpr int A0_TARGET_WAVES = 2048;   // ~8 waves per CU before K is split further
 constexpr int A0_MAX_SPLITS = 64;
 
@@ -53,77 +52,6 @@ static A0Plan a0_plan(int nbits, int64_t N, int64_t K, int64_t gs) {
   p.items = base * p.splits;
   return p;
 }
-
-static __device__ __forceinline__ u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p); }
-static __device__ __forceinline__ u32x4 ld16_nt(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
-
-// fp16: the 16 weights of slab SL of one packed 16-byte vector, (q - z) then * s per element, as two MFMA A operands
-template <int NBITS, int SL>
-__device__ __forceinline__ void rebuild_f16(const u32x4& w, const half2_t (&zz)[8], const half2_t (&ss)[8], h8_t& a0, h8_t& a1, uint32_t magic) {
-  constexpr int sh = NBITS * (8 / NBITS - 1 - SL);
-  constexpr float inv = 1.0f / static_cast<float>(1 << sh);
-  const half2_t k1 = {static_cast<half_t>(inv), static_cast<half_t>(inv)};
-  const half2_t k2 = {static_cast<half_t>(-1024.0f * inv), static_cast<half_t>(-1024.0f * inv)};
-  half2_t q[8];
-  uint32_t o[8];
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    q[2 * d] = biased_levels<NBITS, SL>(w[d], magic);            // bytes (4d+0, 4d+2)
-    q[2 * d + 1] = biased_levels<NBITS, SL>(w[d] >> 8, magic);   // bytes (4d+1, 4d+3)
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) q[i] = __builtin_elementwise_fma(q[i], k1, k2);   // exact integer level
-#pragma unroll
-  for (int i = 0; i < 8; ++i) q[i] = q[i] - zz[i];                               // rounding 1
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = __builtin_bit_cast(uint32_t, q[i] * ss[i]);   // rounding 2
-  a0 = __builtin_bit_cast(h8_t, u32x4{o[0], o[1], o[2], o[3]});
-  a1 = __builtin_bit_cast(h8_t, u32x4{o[4], o[5], o[6], o[7]});
-}
-
-// bf16: the same through fp32 (gfx950 has no packed bf16 arithmetic): q - z in fp32, rounded to bf16, times s (exact in fp32), rounded again
-template <int NBITS, int SL>
-__device__ __forceinline__ void rebuild_bf16(const u32x4& w, const uint32_t (&zz)[8], const uint32_t (&ss)[8], bf16x8_t& a0, bf16x8_t& a1) {
-  constexpr int sh = NBITS * (8 / NBITS - 1 - SL);
-  constexpr uint32_t mask = (NBITS == 8) ? 0xFFu : ((1u << NBITS) - 1u);
-  uint32_t o[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int d = i >> 1, b0 = i & 1;                  // bytes (4d + b0, 4d + b0 + 2)
-    const float q0 = static_cast<float>((w[d] >> (8 * b0 + sh)) & mask);
-    const float q1 = static_cast<float>((w[d] >> (8 * b0 + 16 + sh)) & mask);
-    const f32x2_t dq = {q0 - __uint_as_float(zz[i] << 16), q1 - __uint_as_float(zz[i] & 0xFFFF0000u)};
-    const bf16x2_t dr = __builtin_convertvector(dq, bf16x2_t);                                           // rounding 1
-    const uint32_t du = __builtin_bit_cast(uint32_t, dr);
-    const f32x2_t pw = {__uint_as_float(du << 16) * __uint_as_float(ss[i] << 16),
-                        __uint_as_float(du & 0xFFFF0000u) * __uint_as_float(ss[i] & 0xFFFF0000u)};   // exact: two 8-bit significands
-    o[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pw, bf16x2_t));                          // rounding 2
-  }
-  a0 = __builtin_bit_cast(bf16x8_t, u32x4{o[0], o[1], o[2], o[3]});
-  a1 = __builtin_bit_cast(bf16x8_t, u32x4{o[4], o[5], o[6], o[7]});
-}
-
-// every slab of one packed 16-byte vector against the same meta and x: rebuild, then one MFMA pair per slab
-template <int NBITS, int SL>
-struct A0Slabs {
-  static constexpr int PER = 8 / NBITS;
-  static __device__ __forceinline__ void f16(const u32x4& w, const half2_t (&zz)[8], const half2_t (&ss)[8], const h8_t& b0, const h8_t& b1,
-                                             f32x4 (&acc)[PER], uint32_t magic) {
-    h8_t a0, a1;
-    rebuild_f16<NBITS, SL>(w, zz, ss, a0, a1, magic);
-    acc[SL] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b0, acc[SL], 0, 0, 0);
-    acc[SL] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b1, acc[SL], 0, 0, 0);
-    if constexpr (SL + 1 < PER) A0Slabs<NBITS, SL + 1>::f16(w, zz, ss, b0, b1, acc, magic);
-  }
-  static __device__ __forceinline__ void bf16(const u32x4& w, const uint32_t (&zz)[8], const uint32_t (&ss)[8], const bf16x8_t& b0, const bf16x8_t& b1,
-                                              f32x4 (&acc)[PER]) {
-    bf16x8_t a0, a1;
-    rebuild_bf16<NBITS, SL>(w, zz, ss, a0, a1);
-    acc[SL] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[SL], 0, 0, 0);
-    acc[SL] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[SL], 0, 0, 0);
-    if constexpr (SL + 1 < PER) A0Slabs<NBITS, SL + 1>::bf16(w, zz, ss, b0, b1, acc);
-  }
-};
 
 // one work item — (class, block of the class, K split) number `item` of ONE layer's plan — by the calling wave: shared by the single-layer kernel
 // and the grouped one, so that a layer's partial sums are the same bits in either
@@ -245,36 +173,6 @@ __global__ __launch_bounds__(A0_WAVES * 64) void gemv_axis0_grouped_kernel(const
   a0_item<NBITS, BF16>(x, m.Wq, m.scale, m.zero, m.part, M, m.N, K, m.S, m.P, m.nblocks, m.upc, units, item - first);
 }
 
-// the partial sums of output i over the splits, in split order.  The loads of eight splits are issued together (independent), then added in split
-// order: a thread is one chain of dependent adds, not of dependent round trips to memory
-static __device__ __forceinline__ float a0_sum_splits(const float* __restrict__ part, int64_t MN, int64_t i, int splits) {
-  float s = 0.f;
-  int c = 0;
-  for (; c + 8 <= splits; c += 8) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = part[(c + j) * MN + i];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += v[j];
-  }
-  for (; c < splits; ++c) s += part[c * MN + i];
-  return s;
-}
-
-// round(s) (+ bias: `out += bias` on the rounded result, quantize.py:896-897), as raw bits of the compute dtype
-template <bool BF16>
-static __device__ __forceinline__ uint16_t a0_finish(float s, const uint16_t* __restrict__ bias, int n) {
-  if constexpr (BF16) {
-    uint16_t o = f32_to_bf16(s);
-    if (bias) o = f32_to_bf16(bf16_to_f32(o) + bf16_to_f32(bias[n]));
-    return o;
-  } else {
-    half_t o = static_cast<half_t>(s);
-    if (bias) o = o + __builtin_bit_cast(half_t, bias[n]);
-    return __builtin_bit_cast(uint16_t, o);
-  }
-}
-
 // y[m, n] = round(sum over splits, in split order) (+ bias)
 template <bool BF16>
 __global__ __launch_bounds__(256) void gemv_axis0_reduce_kernel(const float* __restrict__ part, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
@@ -317,26 +215,7 @@ __global__ __launch_bounds__(256) void gemv_axis0_grouped_reduce_kernel(const A0
 
 // what the kernel covers, checked before anything is launched: 0, or an HQQ_ERR_* with the message set
 static int a0_validate(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts) {
-  if (opts & ~HQQ_OPT_ALL) { set_error("hqq_hip_gemv_axis0: unknown option bits 0x%x", opts & ~HQQ_OPT_ALL); return HQQ_ERR_SHAPE; }
-  if (nbits != 8 && nbits != 4 && nbits != 3 && nbits != 2 && nbits != 1) { set_error("hqq_hip_gemv_axis0: nbits=%d", nbits); return HQQ_ERR_NBITS; }
-  if (nbits == 3) { set_error("hqq_hip_gemv_axis0: 3-bit containers are not covered"); return HQQ_ERR_UNSUPPORTED; }
-  if (dtype == HQQ_F32) { set_error("hqq_hip_gemv_axis0: fp32 is not covered (fp16 / bf16)"); return HQQ_ERR_UNSUPPORTED; }
-  if (dtype != HQQ_F16 && dtype != HQQ_BF16) { set_error("hqq_hip_gemv_axis0: dtype %d", dtype); return HQQ_ERR_DTYPE; }
-  if (dtype == HQQ_BF16 && nbits != 4 && nbits != 2) { set_error("hqq_hip_gemv_axis0: bf16 with nbits=%d is not covered (4 / 2)", nbits); return HQQ_ERR_UNSUPPORTED; }
-  if (M < 1 || N < 1 || K < 1 || group_size < 1) { set_error("hqq_hip_gemv_axis0: bad M/N/K/group_size"); return HQQ_ERR_SHAPE; }
-  if (M > HQQ_GEMV_MAX_M) { set_error("hqq_hip_gemv_axis0: M=%lld is not covered (at most %d rows)", (long long)M, HQQ_GEMV_MAX_M); return HQQ_ERR_UNSUPPORTED; }
-  if (group_size % 16 || N % group_size || K % A0_KU) {
-    set_error("hqq_hip_gemv_axis0: not covered: needs group_size %% 16 == 0, N %% group_size == 0, K %% %d == 0 (N=%lld K=%lld gs=%lld)", A0_KU,
-              (long long)N, (long long)K, (long long)group_size);
-    return HQQ_ERR_UNSUPPORTED;
-  }
-  // (N / per) * K packed bytes and N K / gs meta elements per layer, M N fp32 partial sums per split: 32-bit offsets stay in range
-  if (N > INT32_MAX || K > INT32_MAX || (N / (8 / nbits)) * K > static_cast<int64_t>(UINT32_MAX) || (N / group_size) * K > INT32_MAX ||
-      M * N * A0_MAX_SPLITS > INT32_MAX) {
-    set_error("hqq_hip_gemv_axis0: size overflow");
-    return HQQ_ERR_SHAPE;
-  }
-  return 0;
+  return a0_validate_rows("hqq_hip_gemv_axis0", 1, HQQ_GEMV_MAX_M, A0_MAX_SPLITS, nbits, M, N, K, group_size, dtype, opts);
 }
 
 // the grouped call: every member must be a layer hqq_hip_gemv_axis0 covers (a0_validate names the first that is not), then the flags

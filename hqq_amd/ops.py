@@ -671,12 +671,62 @@ def gemv_axis0_grouped(x: Tensor, layers, K: int, group_size, nbits: int, outs=N
     return [o.reshape(*x.shape[:-1], N) for o, N in zip(outs, out_Ns)]
 
 
-def _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts) -> Tensor:
-    """axis-0 layers: decode sizes through hqq_hip_gemv_axis0; everything else as HQQLinear has always run them — the HIP dequantise kernel
-    (axis 0) + torch.matmul, then `out += bias` (quantize.py:880-898)"""
+GEMM_AXIS0_MAX_M = 256   # HQQ_GEMM_AXIS0_MAX_M
+# the last row count at which `forward(axis=0)` takes hqq_hip_gemm_axis0 by default: the largest M of tools/axis0_gemm_bench.py at which the kernel is at
+# least 10 % ahead of dequantise + torch.matmul on every measured shape.  profiles/axis0_gemm_summary.md: 1.38x to 5.9x ahead at 17 / 32 / 64 / 128 rows on
+# every shape; at 256 rows ahead on the int4 shapes but 0.72x on int2 bf16 4096 x 4096, so the route ends at 128.  (16 would mean "opt-in only".)
+AXIS0_GEMM_ROUTE_MAX_M = 128
+
+
+@functools.lru_cache(maxsize=4096)
+def gemm_axis0_covers(dtype, M, N, K, group_size, nbits) -> bool:
+    """what hqq_hip_gemm_axis0 serves: the layers of decode_axis0_covers() at GEMV_MAX_M < M <= GEMM_AXIS0_MAX_M rows whose offsets the library accepts —
+    its workspace query is 0 exactly where the call refuses, so the answer is the library's (32-bit offset guards included)"""
+    if not (GEMV_MAX_M < M <= GEMM_AXIS0_MAX_M and decode_axis0_covers(dtype, 1, N, K, group_size, nbits)):
+        return False
+    gs = N if group_size is None else int(group_size)
+    return int(_C.lib().hqq_hip_gemm_axis0_workspace_bytes(int(nbits), int(M), int(N), int(K), gs, _DT[dtype])) > 0
+
+
+def gemm_axis0(x: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, bias, N: int, K: int, group_size, nbits: int, out: Tensor | None = None,
+               opts=None) -> Tensor:
+    """y = x @ dequantize(W_q, axis=0)^T (+ bias) for x [*, K] of GEMV_MAX_M + 1 .. GEMM_AXIS0_MAX_M rows (hqq_hip_gemm_axis0): arguments as gemv_axis0.
+    Raises NotImplementedError outside gemm_axis0_covers()."""
+    _dev(x, W_q, scale, zero, bias)
+    if x.dtype != scale.dtype or zero.dtype != scale.dtype or (bias is not None and bias.dtype != scale.dtype):
+        raise TypeError("hqq_amd: x / scale / zero / bias must share the compute dtype")
+    if x.shape[-1] != K:
+        raise ValueError(f"hqq_amd: x has {x.shape[-1]} features, layer expects {K}")
+    gs = N if group_size is None else int(group_size)
+    if scale.numel() != (N * K) // gs or zero.numel() != (N * K) // gs:
+        raise ValueError(f"hqq_amd: gemm_axis0 needs {(N * K) // gs} scale / zero values (N * K / group_size), got {scale.numel()} / {zero.numel()}")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    elif out.numel() != M * N or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError(f"hqq_amd: gemm_axis0 writes a dense output of {M} x {N} elements in x's dtype")
+    L = _C.lib()
+    with torch.cuda.device(x.device):
+        need = int(L.hqq_hip_gemm_axis0_workspace_bytes(int(nbits), M, int(N), int(K), gs, _dt(x.dtype)))
+        ws = reserve_workspace(x.device, need) if need else None
+        rc = L.hqq_hip_gemm_axis0(int(nbits), _p(x2), _p(W_q.contiguous()), _p(scale.contiguous()), _p(zero.contiguous()), _p(bias), _p(out),
+                                  M, int(N), int(K), gs, _dt(x.dtype), _opts(opts), _p(ws), 0 if ws is None else ws.numel(), _stream())
+    _C.check(rc, "hqq_hip_gemm_axis0")
+    return out.reshape(*x.shape[:-1], N)
+
+
+def _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts, library_gemm: bool = False) -> Tensor:
+    """axis-0 layers: decode sizes through hqq_hip_gemv_axis0; GEMV_MAX_M + 1 .. AXIS0_GEMM_ROUTE_MAX_M rows through hqq_hip_gemm_axis0 (unless
+    library_gemm); everything else as HQQLinear has always run them — the HIP dequantise kernel (axis 0) + torch.matmul, then `out += bias`
+    (quantize.py:880-898)"""
     M = x.numel() // K if K else 0
     if x.is_cuda and decode_axis0_covers(x.dtype, M, N, K, group_size, nbits):
         return gemv_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=out, opts=opts)
+    if x.is_cuda and not library_gemm and M <= AXIS0_GEMM_ROUTE_MAX_M and gemm_axis0_covers(x.dtype, M, N, K, group_size, nbits):
+        return gemm_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None if out is None else out.reshape(-1, N), opts=opts)
     gs = N if group_size is None else int(group_size)
     W = dequantize(W_q, scale.reshape(-1), zero.reshape(-1), N, K, gs, nbits, 0)
     y = torch.matmul(x.reshape(-1, K), W.t(), out=None if out is None else out.reshape(-1, N))
@@ -732,13 +782,14 @@ def forward(x, W_q, scale, zero, bias, N, K, group_size, nbits, out=None, fused=
     kernel + the in-tree dense MFMA GEMM (library_gemm=True: a library GEMM instead, the bench's comparison; also the residual route for
     K % 64 != 0 or N % 4 != 0).  Same dequantised weights either way.  fused=None also composes the decode-sized cases no route covers;
     fused=True never composes: an uncovered configuration raises.
-    axis=0: a layer quantised along axis 0 — decode_axis0_covers() shapes through hqq_hip_gemv_axis0, the rest through the dequantise kernel +
-    torch.matmul (`fused` and `library_gemm` do not apply)."""
+    axis=0: a layer quantised along axis 0 — decode_axis0_covers() shapes through hqq_hip_gemv_axis0, gemm_axis0_covers() shapes up to
+    AXIS0_GEMM_ROUTE_MAX_M rows through hqq_hip_gemm_axis0, the rest through the dequantise kernel + torch.matmul (library_gemm=True: that route
+    from 17 rows on, the comparison leg; `fused` does not apply)."""
     M = x.numel() // K if K else 0
     if x.dtype != scale.dtype or zero.dtype != scale.dtype or (bias is not None and bias.dtype != scale.dtype):
         raise TypeError("hqq_amd: x / scale / zero / bias must share the compute dtype")
     if axis == 0:
-        return _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts)
+        return _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts, library_gemm)
     if axis != 1:
         raise ValueError(f"hqq_amd: axis must be 0 or 1, got {axis}")
     w3s = nbits == 3 and bool(_opts(opts) & OPT_W3S)   # the 3-bit stream layout (w3s_pack)

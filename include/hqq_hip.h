@@ -360,6 +360,25 @@ int hqq_hip_gemv_axis0_grouped(int nbits, int n_layers, const void* x, const voi
                                uint32_t opts, uint32_t flags, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * HQQLinear.forward for layers quantised along AXIS 0 at 17 .. HQQ_GEMM_AXIS0_MAX_M activation rows (short prompts, batches wider than the decode
+ * kernel's): y[M,N] = x[M,K] . dequantize(Wq)^T (+ bias[N]) in one pass over the packed bytes and the meta per 64 rows (csrc/gemm_axis0.hip).  What it
+ * replaces is hqq/core/quantize.py:880-898 as HQQLinear runs it for these layers: Quantizer.dequantize writes the whole fp16 / bf16 weight, torch.matmul
+ * reads it back, `out += bias`.  Arguments, layout, weights (the bits of hqq_hip_dequantize(axis = 0)), rounding (fp32 accumulation, one rounding, one
+ * more for the bias) and coverage are hqq_hip_gemv_axis0's, except for the rows: HQQ_GEMV_MAX_M < M <= HQQ_GEMM_AXIS0_MAX_M, anything else
+ * HQQ_ERR_UNSUPPORTED ("not covered").  A row's output bits do not depend on the contents or order of the other
+ * rows of the call (they depend on M only through the number of 64-row passes, which sets the K split).
+ * Workspace: hqq_hip_gemm_axis0_workspace_bytes(...) bytes — the counter head (untouched) plus fp32 partial sums of the K splits; linear in M, 0 where
+ * the call would be refused.  Two launches: the contraction and a reduce that sums the splits in split order (deterministic; the split depends on
+ * nbits, N, K, group_size and the number of 64-row passes only).
+ * The two symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+#define HQQ_GEMM_AXIS0_MAX_M 256
+size_t hqq_hip_gemm_axis0_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype);
+int hqq_hip_gemm_axis0(int nbits, const void* x, const void* Wq, const void* scale, const void* zero, const void* bias, void* y,
+                       int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
