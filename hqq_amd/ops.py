@@ -928,108 +928,28 @@ def add_rmsnorm(h: Tensor, delta, weight: Tensor, eps: float, out: Tensor | None
     return out
 
 
-def rope_cache(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
-    """one token: q_out = rotary(q); rotary(k) and v go into the static caches [n_kv_heads, cache_len, head_dim] at position pos[0] (device int64)"""
-    _dev(q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
-    hd = cos.shape[-1]
-    if pos.dtype != torch.int64 or k_cache.shape[-1] != hd or not k_cache.is_contiguous() or not v_cache.is_contiguous():
-        raise ValueError("hqq_amd: rope_cache takes an int64 position tensor and dense [n_kv_heads, cache_len, head_dim] caches")
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_rope_cache(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), _p(q_out), _p(k_cache), _p(v_cache), q.numel() // hd, k.numel() // hd, hd,
-                                         k_cache.shape[-2], _dt(q.dtype), _stream())
-    _C.check(rc, "hqq_hip_rope_cache")
-    return q_out
-
-
-def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
-    """one query per head against the static KV cache's first pos + 1 positions (fp16 / bf16; within rounding of SDPA, not bit-identical):
-    q [n_heads, hd] (any view of n_heads * hd contiguous values), k_cache / v_cache [n_kv, cache_len, hd], pos int64[1] on the device, out [n_heads * hd];
-    splits > 1: the keys of a head shared out over that many workgroups + a merging launch (long caches; attn_splits / attn_workspace)"""
-    _dev(q, k_cache, v_cache, pos, out)
-    n_kv, L, hd = k_cache.shape
-    n_heads = q.numel() // hd
-    if splits > 1 and workspace is None:
-        workspace = attn_workspace(q.device, n_heads, hd, splits)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_decode(_p(q), _p(k_cache), _p(v_cache), _p(pos), _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
-                                          int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
-    _C.check(rc, "hqq_hip_attn_decode")
-    return out
-
-
-def attn_splits(kv_len: int) -> int:
-    """how many workgroups share a head's keys in the decode-attention kernel when up to kv_len of them are visible (1: no second launch)"""
-    return 1 if kv_len <= 1024 else min(16, int(kv_len) // 512)
-
-
-def attn_workspace(device, n_heads: int, head_dim: int, splits: int):
-    """the (uninitialised) record buffer of a split launch, or None"""
-    nb = int(_C.lib().hqq_hip_attn_decode_workspace_bytes(int(n_heads), int(head_dim), int(splits)))
-    return torch.empty(nb, dtype=torch.uint8, device=device) if nb else None
-
-
-def rope_attn_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, out: Tensor, scaling: float,
-                     splits: int = 1, workspace: Tensor | None = None) -> Tensor:
-    """rope_cache + attn_decode in one launch: raw q / k / v projections in, rotary applied in the kernel, the new key / value used from on-chip
-    memory and written to the cache at `pos` for the following steps (the cache ends up bit-identical to rope_cache's)"""
-    _dev(q, k, v, cos, sin, pos, k_cache, v_cache, out)
-    n_kv, L, hd = k_cache.shape
-    n_heads = q.numel() // hd
-    if splits > 1 and workspace is None:
-        workspace = attn_workspace(q.device, n_heads, hd, splits)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_rope_attn_decode(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), _p(k_cache), _p(v_cache), _p(out), n_heads, n_kv, hd, L,
-                                                float(scaling), _dt(q.dtype), int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
-    _C.check(rc, "hqq_hip_rope_attn_decode")
-    return out
-
-
-def token_prologue(tok: Tensor, pos: Tensor, embed: Tensor, h: Tensor, cos_tab=None, sin_tab=None, cos=None, sin=None, mask=None) -> None:
-    """The front of a decode step in one launch (csrc/block.hip, hqq_hip_token_prologue): h[H] = embed[tok]; cos / sin = row pos of the rotary tables
-    [L, head_dim] (skipped when the tables are None); mask[L] = 0 up to pos, -inf beyond (skipped when None).  tok [1, 1] / pos [1] int64 on the device:
-    graph-replay safe.  Copies and compares only: the same bits as embed_tokens(tok), index_select and torch.where produce."""
-    _dev(tok, pos, embed, h)
-    if tok.dtype != torch.int64 or pos.dtype != torch.int64 or embed.dim() != 2 or not embed.is_contiguous() or h.numel() != embed.shape[1] or h.dtype != embed.dtype:
-        raise ValueError("hqq_amd: token_prologue takes int64 tok / pos, a dense [vocab, H] embedding and h [H] of its dtype")
-    L, hd = 1, 0
-    if cos_tab is not None:
-        _dev(cos_tab, sin_tab, cos, sin)
-        if cos_tab.shape != sin_tab.shape or cos_tab.dim() != 2 or not (cos_tab.is_contiguous() and sin_tab.is_contiguous()) or cos.numel() != cos_tab.shape[1] or \
-                sin.numel() != cos_tab.shape[1] or any(t.dtype != embed.dtype for t in (cos_tab, sin_tab, cos, sin)):
-            raise ValueError("hqq_amd: token_prologue takes dense [L, head_dim] rotary tables and [head_dim] outputs of the compute dtype")
-        L, hd = int(cos_tab.shape[0]), int(cos_tab.shape[1])
-    if mask is not None:
-        _dev(mask)
-        if mask.dtype != embed.dtype or not mask.is_contiguous() or (cos_tab is not None and mask.numel() != L):
-            raise ValueError("hqq_amd: token_prologue's mask is a dense [L] tensor of the compute dtype, L the rotary tables' rows")
-        L = int(mask.numel())
-    with torch.cuda.device(h.device):
-        rc = _C.lib().hqq_hip_token_prologue(_p(tok), _p(pos), _p(embed), int(embed.shape[0]), int(embed.shape[1]), _p(cos_tab), _p(sin_tab), L, hd, _p(h), _p(cos), _p(sin),
-                                             _p(mask), _dt(embed.dtype), _stream())
-    _C.check(rc, "hqq_hip_token_prologue")
-
-
-def argmax_advance(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, pos: Tensor | None = None) -> None:
-    """The back of a greedy decode step in one launch (hqq_hip_argmax_advance): next_tok[0] = logits.argmax() (the first index of the largest value, as torch.argmax),
-    tok[0] = the same, pos[0] += 1 (each skipped when None).  int64 tensors on the device: graph-replay safe."""
-    _dev(logits, next_tok)
-    if not logits.is_contiguous() or next_tok.dtype != torch.int64 or (tok is not None and tok.dtype != torch.int64) or (pos is not None and pos.dtype != torch.int64):
-        raise ValueError("hqq_amd: argmax_advance takes dense logits and int64 token / position tensors")
-    with torch.cuda.device(logits.device):
-        rc = _C.lib().hqq_hip_argmax_advance(_p(logits), logits.numel(), _dt(logits.dtype), _p(next_tok), _p(tok), _p(pos), _stream())
-    _C.check(rc, "hqq_hip_argmax_advance")
-
-
-# ---- the same for a batch of B independent sequences, one decode step each (the *_batched entry points: row b gives the bits the batch-1 call gives
-#      for sequence b alone).  tok / pos: int64 [B] on the device; every other tensor is dense, one row (or cache) per sequence ----------------------
+# ---- the glue kernels of a decode step for B independent sequences (csrc/block.hip, the *_batched entry points: the sequence is a grid index, and row b
+#      gives the bits a launch for sequence b alone gives).  tok / pos: int64 [B] on the device; every other tensor is dense, one row (or cache) per
+#      sequence.  Each kernel has ONE implementation here, the *_batched function: it validates and calls the library.  The single-sequence function
+#      of the same name is that call on views of its arguments as a batch of one ------------------------------------------------------------------
 def _batch_of(pos: Tensor, who: str) -> int:
     if pos.dtype != torch.int64 or not pos.is_contiguous() or pos.numel() < 1:
         raise ValueError(f"hqq_amd: {who} takes a dense int64 position tensor of B >= 1 elements")
     return pos.numel()
 
 
+def _seq1(pos):
+    """a single sequence's position tensor (int64 [1]; None stays None) as the batch of one: its first element, the same memory"""
+    return None if pos is None else pos.view(-1)[:1]
+
+
+def _cache1(cache: Tensor) -> Tensor:
+    """a single sequence's cache [n_kv_heads, cache_len, head_dim] as the batch of one [1, n_kv_heads, cache_len, head_dim], the same memory"""
+    return cache.view(1, *cache.shape[-3:])
+
+
 def token_prologue_batched(tok: Tensor, pos: Tensor, embed: Tensor, h: Tensor, cos_tab=None, sin_tab=None, cos=None, sin=None, mask=None) -> None:
-    """token_prologue for B sequences in one launch (hqq_hip_token_prologue_batched): h [B, H] = embed[tok[b]]; cos / sin [B, head_dim] = row pos[b] of the
+    """The front of a decode step for B sequences in one launch (hqq_hip_token_prologue_batched): h [B, H] = embed[tok[b]]; cos / sin [B, head_dim] = row pos[b] of the
     rotary tables [L, head_dim] (skipped when the tables are None); mask [B, L] = 0 up to pos[b], -inf beyond (skipped when None).  tok [B] or [B, 1] / pos [B]
     int64 on the device: graph-replay safe.  Copies and compares only: per row the same bits as embed_tokens, index_select and torch.where."""
     _dev(tok, pos, embed, h)
@@ -1055,8 +975,13 @@ def token_prologue_batched(tok: Tensor, pos: Tensor, embed: Tensor, h: Tensor, c
     _C.check(rc, "hqq_hip_token_prologue_batched")
 
 
+def token_prologue(tok: Tensor, pos: Tensor, embed: Tensor, h: Tensor, cos_tab=None, sin_tab=None, cos=None, sin=None, mask=None) -> None:
+    """token_prologue_batched for one sequence: tok [1, 1] / pos [1], h [H] (or [1, H]), cos / sin [head_dim], mask [L]"""
+    token_prologue_batched(tok, _seq1(pos), embed, h, cos_tab, sin_tab, cos, sin, mask)
+
+
 def rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
-    """rope_cache for B sequences in one launch: q_out [B, n_heads * hd] = rotary(q [B, n_heads * hd]) with cos / sin [B, hd]; rotary(k) and v ([B, n_kv * hd])
+    """one token of B sequences in one launch: q_out [B, n_heads * hd] = rotary(q [B, n_heads * hd]) with cos / sin [B, hd]; rotary(k) and v ([B, n_kv * hd])
     go into row b of the caches [B, n_kv_heads, cache_len, head_dim] (HF's StaticCache tensors of batch B) at position pos[b]; a position outside the cache writes nothing"""
     _dev(q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
     B = _batch_of(pos, "rope_cache_batched")
@@ -1073,6 +998,11 @@ def rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor
     return q_out
 
 
+def rope_cache(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
+    """rope_cache_batched for one sequence: cos / sin [hd], the static caches [n_kv_heads, cache_len, head_dim], position pos[0] (device int64)"""
+    return rope_cache_batched(q, k, v, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), q_out)
+
+
 def _attn_batched_args(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, who: str):
     B = _batch_of(pos, who)
     if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
@@ -1083,14 +1013,27 @@ def _attn_batched_args(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor,
     return B, q.numel() // (B * hd), n_kv, L, hd
 
 
+def attn_splits(kv_len: int) -> int:
+    """how many workgroups share a head's keys in the decode-attention kernel when up to kv_len of them are visible (1: no second launch)"""
+    return 1 if kv_len <= 1024 else min(16, int(kv_len) // 512)
+
+
 def attn_workspace_batched(device, batch: int, n_heads: int, head_dim: int, splits: int):
-    """the record buffer of a split batched launch (hqq_hip_attn_decode_workspace_bytes(batch * n_heads, ...)), or None"""
-    return attn_workspace(device, int(batch) * int(n_heads), head_dim, splits)
+    """the (uninitialised) record buffer of a split launch for `batch` sequences (hqq_hip_attn_decode_workspace_bytes(batch * n_heads, ...)), or None"""
+    nb = int(_C.lib().hqq_hip_attn_decode_workspace_bytes(int(batch) * int(n_heads), int(head_dim), int(splits)))
+    return torch.empty(nb, dtype=torch.uint8, device=device) if nb else None
+
+
+def attn_workspace(device, n_heads: int, head_dim: int, splits: int):
+    """attn_workspace_batched for one sequence"""
+    return attn_workspace_batched(device, 1, n_heads, head_dim, splits)
 
 
 def attn_decode_batched(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
-    """attn_decode for B sequences in one launch: q / out [B, n_heads * hd], caches [B, n_kv, cache_len, hd], pos int64 [B]; sequence b attends over its own first
-    pos[b] + 1 keys.  splits is one for the whole launch (pick it from the largest position, attn_splits): a sequence with fewer visible keys than splits
+    """one query per head and sequence against the static KV caches, B sequences in one launch (fp16 / bf16; within rounding of SDPA, not bit-identical):
+    q / out [B, n_heads * hd] (any dense view of those values), caches [B, n_kv, cache_len, hd], pos int64 [B] on the device; sequence b attends over its own first
+    pos[b] + 1 keys.  splits > 1: the keys of a head shared out over that many workgroups + a merging launch (long caches; attn_splits / attn_workspace_batched).
+    splits is one for the whole launch (pick it from the largest position): a sequence with fewer visible keys than splits
     leaves the surplus shares empty, and the merging launch ignores them"""
     _dev(q, k_cache, v_cache, pos, out)
     B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "attn_decode_batched")
@@ -1103,10 +1046,16 @@ def attn_decode_batched(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor
     return out
 
 
+def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_batched for one sequence: q [n_heads, hd] (any dense view of n_heads * hd values), k_cache / v_cache [n_kv, cache_len, hd], pos int64[1], out [n_heads * hd]"""
+    return attn_decode_batched(q, _cache1(k_cache), _cache1(v_cache), _seq1(pos), out, scaling, splits=splits, workspace=workspace)
+
+
 def rope_attn_decode_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, out: Tensor, scaling: float,
                              splits: int = 1, workspace: Tensor | None = None) -> Tensor:
-    """rope_attn_decode for B sequences in one launch: raw q [B, n_heads * hd], k / v [B, n_kv * hd], cos / sin [B, hd]; each sequence's new key / value go to its
-    own cache row at pos[b] (bit-identical to rope_cache_batched's); splits as in attn_decode_batched"""
+    """rope_cache_batched + attn_decode_batched in one launch: raw q [B, n_heads * hd], k / v [B, n_kv * hd], cos / sin [B, hd]; rotary applied in the kernel, each
+    sequence's new key / value used from on-chip memory and written to its own cache row at pos[b] for the following steps (the caches end up bit-identical to
+    rope_cache_batched's); splits as in attn_decode_batched"""
     _dev(q, k, v, cos, sin, pos, k_cache, v_cache, out)
     B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "rope_attn_decode_batched")
     if cos.numel() != B * hd or sin.numel() != B * hd or k.numel() != B * n_kv * hd or v.numel() != k.numel() or \
@@ -1121,9 +1070,16 @@ def rope_attn_decode_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: 
     return out
 
 
+def rope_attn_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, out: Tensor, scaling: float,
+                     splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """rope_attn_decode_batched for one sequence: cos / sin [hd], caches [n_kv, cache_len, hd], pos int64[1]"""
+    return rope_attn_decode_batched(q, k, v, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), out, scaling, splits=splits, workspace=workspace)
+
+
 def argmax_advance_batched(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, pos: Tensor | None = None) -> None:
-    """argmax_advance for B sequences in one launch, one workgroup per row (hqq_hip_argmax_advance_batched): next_tok[b] = logits[b].argmax() (torch.argmax's
-    tie and NaN rule), tok[b] = the same, pos[b] += 1 (each skipped when None).  logits [B, vocab] dense; int64 tensors of B elements on the device."""
+    """The back of a greedy decode step for B sequences in one launch, one workgroup per row (hqq_hip_argmax_advance_batched): next_tok[b] = logits[b].argmax() (the first
+    index of the largest value; torch.argmax's tie and NaN rule), tok[b] = the same, pos[b] += 1 (each skipped when None).  logits [B, vocab] dense; int64 tensors of
+    B elements on the device: graph-replay safe."""
     _dev(logits, next_tok)
     B = next_tok.numel()
     if logits.dim() != 2 or logits.shape[0] != B or not logits.is_contiguous() or next_tok.dtype != torch.int64 or not next_tok.is_contiguous() or \
@@ -1132,6 +1088,11 @@ def argmax_advance_batched(logits: Tensor, next_tok: Tensor, tok: Tensor | None 
     with torch.cuda.device(logits.device):
         rc = _C.lib().hqq_hip_argmax_advance_batched(_p(logits), B, logits.shape[1], _dt(logits.dtype), _p(next_tok), _p(tok), _p(pos), _stream())
     _C.check(rc, "hqq_hip_argmax_advance_batched")
+
+
+def argmax_advance(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, pos: Tensor | None = None) -> None:
+    """argmax_advance_batched for one sequence: logits of any dense shape holding one row, next_tok / tok [1, 1], pos [1]"""
+    argmax_advance_batched(logits.view(1, -1), next_tok, tok, _seq1(pos))
 
 
 def silu_mul(gate: Tensor, up: Tensor, out: Tensor | None = None) -> Tensor:

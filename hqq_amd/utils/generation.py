@@ -59,7 +59,10 @@ class GraphedGreedyDecoder:
     ride inside the GEMV launches themselves: 5 launches + attention per decoder block.  Any other model, or fused=False: the model's own forward.
     axis0: what a model quantised along AXIS 0 decodes through.  "model" (default): the model's own forward, as before.  "fused" (opt-in): where
     llama_fused.supports_axis0 accepts the model, the fused step with q|k|v and gate|up (+ SiLU * up) as one grouped axis-0 launch each
-    (`fused_axis0`; `fused` stays the axis-1 flag), and generate_batch's batched step where supports_axis0_batch accepts the batch."""
+    (`fused_axis0`; `fused` stays the axis-1 flag), and generate_batch's batched step where supports_axis0_batch accepts the batch.
+    generate() and generate_batch() prefill differently and keep different caches, but advance through the same routine (_advance) over a small state
+    holder: the device tensors tok / next_tok / pos that the captured graphs read and write, the step (None: the model's own forward), the dictionary
+    its graphs are kept in with the key of an attended length in it, and the rule for that length."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model"):
@@ -82,12 +85,16 @@ class GraphedGreedyDecoder:
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.max_cache_len = max_cache_len
         self._StaticCache = StaticCache
-        self.graph = None      # the graph of the last step taken
         self.graphs = {}       # attended cache length -> captured step
         self.cache = None      # HF StaticCache, kept between generate() calls (reset in place)
-        self._state = None     # (tok, next_tok, pos): the device tensors the captured graphs read and write
-        self._batch = {}       # B -> the kept state of generate_batch (B-row cache, batch-1 prefill cache, batched step, tok / next_tok / pos)
+        self._state = None     # the state holder of generate(): its tok / next_tok / pos are self.tok / .next_tok / .pos, its step self.step, its graphs self.graphs
+        self._batch = {}       # B -> the state holder of generate_batch at B rows (with its B-row cache and its batch-1 prefill cache)
         self.batch_graphs = {} # (B, attended cache length) -> captured batched step
+
+    @property
+    def graph(self):
+        """the graph of the last generate() step that was replayed (None: none yet)"""
+        return None if self._state is None else self._state["graph"]
 
     def _kv_len(self, p: int) -> int:
         """how much of the static cache a step at position p attends over.  HF's attention function costs what it is given (the whole masked cache:
@@ -99,7 +106,7 @@ class GraphedGreedyDecoder:
         return kv_bucket(p, self.attention, self.max_cache_len)
 
     def _pick(self, logits: Tensor) -> Tensor:
-        """logits [1, vocab] -> the next token [1, 1].  Greedy: argmax.  do_sample: temperature, then the top_k cut, then one draw from the softmax by the
+        """logits [B, vocab] -> the next tokens [B, 1].  Greedy: argmax.  do_sample: temperature, then the top_k cut, then one draw from the softmax by the
         exponential-race form of a categorical draw (argmax of p / e, e ~ Exp(1)): elementwise kernels + two reductions, nothing leaves the device"""
         if not self.do_sample:
             return logits.argmax(-1, keepdim=True)
@@ -111,19 +118,20 @@ class GraphedGreedyDecoder:
         return (p / torch.empty_like(p).exponential_(1.0)).argmax(-1, keepdim=True)
 
     @torch.no_grad()
-    def _decode_once(self, kv_len=None):
-        """one whole transition: logits at self.pos -> next_tok, tok = next_tok, pos += 1 (all on the device, so the captured graph carries the loop state forward by itself)"""
-        if self.step is not None:
-            logits = self.step(self.tok, self.pos, kv_len)
-            if not self.do_sample and self.glue != "kernels" and logits.dtype in (torch.float16, torch.bfloat16) and logits.is_contiguous():
-                ops.argmax_advance(logits, self.next_tok, self.tok, self.pos)   # argmax + hand-over + position increment: one launch (csrc/block.hip)
+    def _decode_once(self, st, kv_len=None) -> None:
+        """one whole transition of every row: logits at pos -> next_tok, tok = next_tok, pos += 1 (all on the device, so the captured graph carries the loop state forward by itself)"""
+        tok, next_tok, pos = st["tok"], st["next_tok"], st["pos"]
+        if st["step"] is not None:
+            logits = st["step"](tok, pos, kv_len)
+            if st["argmax_advance"] and not self.do_sample and logits.dtype in (torch.float16, torch.bfloat16) and logits.is_contiguous():
+                ops.argmax_advance_batched(logits, next_tok, tok, pos)   # per row: argmax + hand-over + position increment, one launch (csrc/block.hip)
                 return
-            self.next_tok.copy_(self._pick(logits))
-        else:
-            out = self.model(self.tok, past_key_values=self.cache, cache_position=self.pos, use_cache=True)
-            self.next_tok.copy_(self._pick(out.logits[:, -1]))
-        self.tok.copy_(self.next_tok)
-        self.pos += 1
+            next_tok.copy_(self._pick(logits))
+        else:   # (generate() only)
+            out = self.model(tok, past_key_values=self.cache, cache_position=pos, use_cache=True)
+            next_tok.copy_(self._pick(out.logits[:, -1]))
+        tok.copy_(next_tok)
+        pos += 1
 
     def _fingerprint(self):
         """what the kept state was built from: identity, storage and version of every quantised layer's packed weights and scale, and the forward HQQLinear is
@@ -144,7 +152,6 @@ class GraphedGreedyDecoder:
         by itself when the model's quantised layers are no longer the ones the state was built from (_fingerprint)"""
         self.cache = None
         self.step = None
-        self.graph = None
         self.graphs = {}
         self._state = None
         self._batch = {}
@@ -172,14 +179,10 @@ class GraphedGreedyDecoder:
         out = self.model(ids, past_key_values=self.cache, cache_position=torch.arange(T, device=self.device), use_cache=True)   # prefill
         first = self._pick(out.logits[:, -1])
         if kept:
-            self.tok, self.next_tok, self.pos = self._state   # the tensors the captured graphs read and write
-            self.tok.copy_(first)
-            self.pos.fill_(T)
+            st = self._state   # (its tensors are the ones the captured graphs read and write)
+            st["tok"].copy_(first)
+            st["pos"].fill_(T)
         else:
-            self.tok = first
-            self.next_tok = torch.empty_like(self.tok)
-            self.pos = torch.tensor([T], device=self.device)
-            self._state = (self.tok, self.next_tok, self.pos)
             self.step = None
             if self.fused or self.fused_axis0:
                 try:
@@ -187,13 +190,16 @@ class GraphedGreedyDecoder:
                                                                glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0)
                 except ValueError:   # a cache layout / attention configuration the fused step does not restate: the model's own forward serves
                     self.step = None
-            self.graph = None
             self.graphs = {}
+            # (glue="kernels" is the comparison leg with the separate front and back: its argmax, hand-over and increment stay torch ops)
+            st = self._state = {"step": self.step, "tok": first, "next_tok": torch.empty_like(first), "pos": torch.tensor([T], device=self.device), "graphs": self.graphs,
+                                "key": lambda kv: kv, "kv_len": self._kv_len, "argmax_advance": self.glue != "kernels", "graph": None}
+        self.tok, self.next_tok, self.pos = st["tok"], st["next_tok"], st["pos"]
         toks = [self.tok.clone()]
         done = 0        # tokens the host has looked at
         n = max_new_tokens
         for i in range(max_new_tokens - 1):
-            self._advance(T + i, use_graph and (kept or i >= 1))   # (a fresh decoder's step 0 runs eagerly: lazy initialisation inside the model)
+            self._advance(st, T + i, use_graph and (kept or i >= 1))   # (a fresh decoder's step 0 runs eagerly: lazy initialisation inside the model)
             toks.append(self.tok.clone())
             if eos_token_id is not None and (len(toks) - done >= check_every or i == max_new_tokens - 2):
                 seen = torch.cat(toks[done:], dim=1)[0].tolist()   # one host read per check_every tokens
@@ -208,59 +214,63 @@ class GraphedGreedyDecoder:
         return torch.cat([ids] + toks[:n], dim=1)
 
     @torch.no_grad()
-    def _advance(self, p: int, use_graph: bool) -> None:
-        """one decode step at position p (the host's copy of self.pos): replay the graph of p's cache bucket, capturing it first if need be"""
-        kv = self._kv_len(p)
-        g = self.graphs.get(kv) if use_graph else None
+    def _advance(self, st, p: int, use_graph: bool) -> None:
+        """one decode step of the state holder st at position p (the host's copy of its LARGEST row position): replay the graph of p's cache bucket, capturing it first if need be"""
+        kv = st["kv_len"](p)
+        key = st["key"](kv)
+        g = st["graphs"].get(key) if use_graph else None
         if use_graph and g is None:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                snap = (self.tok.clone(), self.pos.clone())
-                self._decode_once(kv)                    # warm-up on the side stream (writes cache slot pos, re-written below)
-                self.tok.copy_(snap[0]); self.pos.copy_(snap[1])
+                snap = (st["tok"].clone(), st["pos"].clone())
+                self._decode_once(st, kv)                # warm-up on the side stream (writes cache slot pos, re-written below)
+                st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._decode_once(kv)
-            self.graphs[kv] = g                          # the capture itself does not execute: replay for this step
+                self._decode_once(st, kv)
+            st["graphs"][key] = g                        # the capture itself does not execute: replay for this step
         if g is not None:
             g.replay()
-            self.graph = g
+            st["graph"] = g
         else:
-            self._decode_once(kv)
+            self._decode_once(st, kv)
+
+    @torch.no_grad()
+    def _timed_steps(self, st, p: int, new_tokens: int, warmup: int) -> float:
+        """`warmup` steps of the state holder st from position p on (the host's copy of every row's position), then `new_tokens` timed ones (HIP events on
+        the current stream; the argmax feeds the next step on the device, the host only replays): ms per step"""
+        for _ in range(warmup):
+            self._advance(st, p, True)
+            p += 1
+        for q in range(p, p + new_tokens):                    # buckets the timed steps will enter: captured before the clock starts
+            if st["key"](st["kv_len"](q)) not in st["graphs"]:
+                snap = (st["tok"].clone(), st["pos"].clone())
+                self._advance(st, q, True)
+                st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(new_tokens):
+            self._advance(st, p, True)
+            p += 1
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / new_tokens
 
     @torch.no_grad()
     def benchmark(self, input_ids: Tensor, new_tokens: int = 64, warmup: int = 8) -> dict:
-        """end-to-end decode rate: prefill `input_ids`, capture the decode step, then time `new_tokens` replays of it (HIP events on
-        the current stream; the argmax feeds the next step on the device, the host only replays).  Returns tok/s and ms per token."""
+        """end-to-end decode rate: prefill `input_ids`, capture the decode step, then time `new_tokens` replays of it (_timed_steps).  Returns tok/s and ms per token."""
         assert input_ids.shape[0] == 1
         T = input_ids.shape[1]
         assert T + warmup + new_tokens + 4 <= self.max_cache_len
         self.generate(input_ids, 3, use_graph=True)          # prefill + eager step + captured step (leaves self.graphs, self.tok, self.pos)
         assert self.graph is not None
-        p = T + 2                                             # the host's copy of self.pos
-        for _ in range(warmup):
-            self._advance(p, True)
-            p += 1
-        for q in range(p, p + new_tokens):                    # buckets the timed steps will enter: captured before the clock starts
-            if self._kv_len(q) not in self.graphs:
-                snap = (self.tok.clone(), self.pos.clone())
-                self._advance(q, True)
-                self.tok.copy_(snap[0]); self.pos.copy_(snap[1])
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(new_tokens):
-            self._advance(p, True)
-            p += 1
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / new_tokens
+        ms = self._timed_steps(self._state, T + 2, new_tokens, warmup)   # (T + 2: the host's copy of self.pos)
         return {"ms_per_token": ms, "tok_s": 1e3 / ms, "new_tokens": new_tokens, "prompt_tokens": T}
 
-
-    # ---- a batch of prompts through ONE fused step per token (llama_fused.FusedLlamaBatchStep) ----------------------------------------------------------------
+    # ---- a batch of prompts through ONE fused step per token (llama_fused.FusedLlamaStep with batch = B) ----------------------------------------------------------
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens: int, use_graph: bool = True, eos_token_id: int | None = None, check_every: int = 16) -> list:
         """continuations of B prompts of any lengths (a list of 1-D or [1, T_b] int64 tensors), decoded together: each decode step runs the B sequences
@@ -307,7 +317,7 @@ class GraphedGreedyDecoder:
         done = 0
         n = max_new_tokens
         for i in range(max_new_tokens - 1):
-            self._advance_batch(st, [T + i for T in lengths], use_graph and (kept or i >= 1))   # (a fresh state's step 0 runs eagerly, as in generate())
+            self._advance(st, max(lengths) + i, use_graph and (kept or i >= 1))   # (a fresh state's step 0 runs eagerly, as in generate())
             toks.append(st["tok"].clone())
             if eos_token_id is not None and (len(toks) - done >= check_every or i == max_new_tokens - 2):
                 seen = torch.cat(toks, dim=1).tolist()   # one host read per check_every steps
@@ -320,7 +330,7 @@ class GraphedGreedyDecoder:
         return [torch.cat([ids[b], rows[b:b + 1, :keep[b]]], dim=1) for b in range(B)]
 
     def _batch_state(self, B: int):
-        """the kept state of generate_batch at B rows, or None when the batched step does not serve the model there"""
+        """the kept state holder of generate_batch at B rows, or None when the batched step does not serve the model there"""
         fm = self._fused_mod
         if not ((self.fused and fm.supports_batch(self.model, B)) or (self.fused_axis0 and fm.supports_axis0_batch(self.model, B))):
             return None
@@ -329,57 +339,22 @@ class GraphedGreedyDecoder:
         hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         cache = self._StaticCache(config=cfg, max_cache_len=self.max_cache_len)
         cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
-        try:
+        try:   # (without the decoder's `glue`: the batched step has the one-launch front and back wherever they apply)
             step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0)
         except ValueError:
             return None
         st = {"B": B, "cache": cache, "scratch": self._StaticCache(config=cfg, max_cache_len=self.max_cache_len), "step": step,
               "tok": torch.zeros(B, 1, dtype=torch.int64, device=self.device), "next_tok": torch.zeros(B, 1, dtype=torch.int64, device=self.device),
-              "pos": torch.zeros(B, dtype=torch.int64, device=self.device)}
+              "pos": torch.zeros(B, dtype=torch.int64, device=self.device), "graphs": self.batch_graphs, "key": lambda kv: (B, kv),
+              # the bucket of the LARGEST row position (batch_kv_bucket's rule): every row attends within it, each masked beyond its own position
+              "kv_len": lambda p: kv_bucket(p, self.attention, self.max_cache_len) if self.bucket_cache else self.max_cache_len,
+              "argmax_advance": True, "graph": None}
         self._batch[B] = st
         return st
 
     @torch.no_grad()
-    def _decode_once_batch(self, st, kv_len) -> None:
-        """one transition of every row: logits at pos -> next_tok, tok = next_tok, pos += 1 (on the device)"""
-        logits = st["step"](st["tok"], st["pos"], kv_len)
-        if not self.do_sample and logits.dtype in (torch.float16, torch.bfloat16) and logits.is_contiguous():
-            ops.argmax_advance_batched(logits, st["next_tok"], st["tok"], st["pos"])   # per row: argmax + hand-over + position increment, one launch
-            return
-        st["next_tok"].copy_(self._pick(logits))
-        st["tok"].copy_(st["next_tok"])
-        st["pos"] += 1
-
-    def _batch_kv_len(self, positions) -> int:
-        """_kv_len for a batched step: the bucket of the largest row position"""
-        return batch_kv_bucket(positions, self.attention, self.max_cache_len) if self.bucket_cache else self.max_cache_len
-
-    @torch.no_grad()
-    def _advance_batch(self, st, positions, use_graph: bool) -> None:
-        """one batched step at the host's copy of the row positions: replay the graph of (B, the largest position's bucket), capturing it first if need be"""
-        kv = self._batch_kv_len(positions)
-        key = (st["B"], kv)
-        g = self.batch_graphs.get(key) if use_graph else None
-        if use_graph and g is None:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                snap = (st["tok"].clone(), st["pos"].clone())
-                self._decode_once_batch(st, kv)          # warm-up on the side stream (writes cache slots pos, re-written below)
-                st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._decode_once_batch(st, kv)
-            self.batch_graphs[key] = g
-        if g is not None:
-            g.replay()
-        else:
-            self._decode_once_batch(st, kv)
-
-    @torch.no_grad()
     def benchmark_batch(self, input_ids: Tensor, new_tokens: int = 64, warmup: int = 8) -> dict:
-        """benchmark() for a batch: prefill the B rows of input_ids [B, T], capture the batched step, time `new_tokens` replays of it (HIP events).
+        """benchmark() for a batch: prefill the B rows of input_ids [B, T], capture the batched step, time `new_tokens` replays of it (_timed_steps).
         Returns the step time and the aggregate rate (B tokens per step).  Needs a model the batched step covers at B rows."""
         B, T = input_ids.shape
         assert T + warmup + new_tokens + 4 <= self.max_cache_len
@@ -389,24 +364,7 @@ class GraphedGreedyDecoder:
         self.generate_batch(list(input_ids), 3, use_graph=True)
         st = self._batch.get(B)
         assert st is not None, "hqq_amd: the batched step does not serve this model at this batch (llama_fused.supports_batch)"
-        p = T + 2
-        for _ in range(warmup):
-            self._advance_batch(st, [p] * B, True)
-            p += 1
-        for q in range(p, p + new_tokens):
-            if (B, self._batch_kv_len([q])) not in self.batch_graphs:
-                snap = (st["tok"].clone(), st["pos"].clone())
-                self._advance_batch(st, [q] * B, True)
-                st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(new_tokens):
-            self._advance_batch(st, [p] * B, True)
-            p += 1
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / new_tokens
+        ms = self._timed_steps(st, T + 2, new_tokens, warmup)
         return {"ms_per_step": ms, "tok_s": B * 1e3 / ms, "batch": B, "new_tokens": new_tokens, "prompt_tokens": T}
 
 

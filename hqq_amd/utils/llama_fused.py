@@ -1,11 +1,15 @@
 """One decode step of a Llama-type HF model whose decoder linears are HQQLinearHIP layers, with the steps either side of the fused
 GEMVs fused too (the loop the reference's headline tok/s is measured on: hqq/utils/generation_hf.py:117-540, Readme.md:153).
+ONE step class, FusedLlamaStep, serves a single sequence and a batch of B independent sequences: the batch size is a parameter (`batch`), every
+buffer has B rows, every launch takes the B rows at once and the glue kernels are the *_batched entry points of csrc/block.hip (row b gives the bits
+the batch-1 kernel gives for sequence b alone).
 
 HF's decoder block around the seven linears is ~25 eager kernels per block at batch 1 (RMSNorm 5-6, rotary 8, cache update 2, SiLU * up 2,
 residual adds 2, ...): 79 % of a token once the linears are fused.  Here a block is
     add_rmsnorm -> q|k|v (one grouped GEMV) -> rope_cache -> attention (HF's own attention function on the static cache) -> o ->
     add_rmsnorm (the residual add of o rides in it) -> gate|up (one grouped GEMV) -> silu_mul -> down (its residual add rides in the next block's add_rmsnorm)
-= 8 launches + the attention's (glue="kernels").  Round 5 folds the glue into the launches either side of it (glue="folded", the default where
+= 8 launches + the attention's (glue="kernels"; the only sequence at batch > 1, where the linears run at M = B, supports_batch).  Round 5 folds the glue
+into the launches either side of it (glue="folded", batch 1 only, the default where
 csrc/gemv_block.hip covers the model): q|k|v with the RMSNorm in its prologue -> rope_cache -> attention -> o with the residual add in its epilogue ->
 ONE paired gate|up layer (RMSNorm prologue, SiLU * up epilogue) -> down with the residual add in its epilogue; and with q / k in the rotary-paired row order
 (ops.rotary_pair_layout) the rotary embedding and the cache write ride in the q|k|v launch's epilogue too = 4 launches + the attention's.  The three glue kernels (csrc/block.hip) restate the HF modules rounding for rounding and the attention is
@@ -58,93 +62,124 @@ def arch_supported(model) -> bool:
         return False
 
 
+def _decoder_linears(model):
+    """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers"""
+    return [[_hip(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
+            for b in model.model.layers]
+
+
+def _structure(model, axis: int):
+    """The structural half of supports() and supports_axis0*(): an allow-listed architecture (arch_supported), fp16 or bf16, the rotary / embedding /
+    lm_head modules the step calls, every decoder linear an HQQLinearHIP of the compute dtype without bias, quantised along `axis`, on the GPU, and
+    RMSNorm weights of that dtype with a multiple of 8 features.  Returns (dtype, _decoder_linears(model)), or None where the model is not of that shape;
+    which kernels cover the layers is the callers' question."""
+    if not arch_supported(model):
+        return None
+    try:
+        inner = model.model
+        dt = inner.norm.weight.dtype
+        if dt not in (torch.float16, torch.bfloat16):
+            return None
+        if not hasattr(inner, "rotary_emb") or not hasattr(inner, "embed_tokens") or not hasattr(model, "lm_head"):
+            return None
+        blocks = _decoder_linears(model)
+        for blk, lin in zip(inner.layers, blocks):
+            if not all(isinstance(L, HQQLinearHIP) and L.bias is None and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == axis for L in lin):
+                return None
+            for nrm in (blk.input_layernorm, blk.post_attention_layernorm):
+                if nrm.weight.dtype != dt or nrm.weight.shape[0] % 8:
+                    return None
+        return dt, blocks
+    except AttributeError:
+        return None
+
+
 def supports(model) -> bool:
     """a LlamaForCausalLM-shaped model of an allow-listed architecture (arch_supported) — model.model.layers[*].self_attn.{q,k,v,o}_proj,
     .mlp.{gate,up,down}_proj, RMSNorm without bias —, fp16 or bf16, every decoder linear an HQQLinearHIP without bias, quantised along axis 1 (the folded
     block kernels read axis-1 meta), whose group can share one launch"""
-    if not arch_supported(model):
+    found = _structure(model, 1)
+    if found is None:
         return False
-    try:
-        inner = model.model
-        dt = inner.norm.weight.dtype
-        if dt not in (torch.float16, torch.bfloat16):
+    dt, blocks = found
+    for lin in blocks:
+        if len({(L.nbits, L.group_size, L.w3s) for L in lin[:3]}) != 1 or len({(L.nbits, L.group_size, L.w3s) for L in lin[4:6]}) != 1:
             return False
-        layers = inner.layers
-        if not hasattr(inner, "rotary_emb") or not hasattr(inner, "embed_tokens") or not hasattr(model, "lm_head"):
+        if not ops.decode_covers(dt, 1, lin[0].out_features, lin[0].in_features, lin[0].group_size, lin[0].nbits) and not lin[0].w3s:
             return False
-        for blk in layers:
-            at, mlp = blk.self_attn, blk.mlp
-            lin = [_hip(getattr(at, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
-            if not all(isinstance(L, HQQLinearHIP) and L.bias is None and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == 1 for L in lin):
-                return False
-            if len({(L.nbits, L.group_size, L.w3s) for L in lin[:3]}) != 1 or len({(L.nbits, L.group_size, L.w3s) for L in lin[4:6]}) != 1:
-                return False
-            if not ops.decode_covers(dt, 1, lin[0].out_features, lin[0].in_features, lin[0].group_size, lin[0].nbits) and not lin[0].w3s:
-                return False
-            if type(getattr(mlp, "act_fn", None)).__name__ not in ("SiLUActivation", "SiLU"):
-                return False
-            for nrm in (blk.input_layernorm, blk.post_attention_layernorm):
-                if nrm.weight.dtype != dt or nrm.weight.shape[0] % 8:
-                    return False
-        return True
-    except AttributeError:
-        return False
+    return True
 
 
-def _supports_axis0_rows(model, M: int) -> bool:
-    if not arch_supported(model):
+def supports_axis0_batch(model, B: int) -> bool:
+    """supports_axis0(model) with every launch taking B activation rows (1 <= B <= ops.GEMV_MAX_M)"""
+    M = int(B)
+    found = _structure(model, 0) if 1 <= M <= ops.GEMV_MAX_M else None
+    if found is None:
         return False
-    try:
-        inner = model.model
-        dt = inner.norm.weight.dtype
-        if dt not in (torch.float16, torch.bfloat16):
+    dt, blocks = found
+    for (q, k, v, o, g, u, d) in blocks:
+        if len({(L.nbits, L.group_size, L.in_features) for L in (q, k, v)}) != 1 or len({(L.nbits, L.group_size, L.in_features, L.out_features) for L in (g, u)}) != 1:
             return False
-        if not hasattr(inner, "rotary_emb") or not hasattr(inner, "embed_tokens") or not hasattr(model, "lm_head"):
+        if not ops.axis0_grouped_covers(dt, M, [L.out_features for L in (q, k, v)], q.in_features, q.group_size, q.nbits) or \
+                not ops.axis0_grouped_covers(dt, M, [g.out_features, u.out_features], g.in_features, g.group_size, g.nbits, ops.BLOCK_SILU):
             return False
-        for blk in inner.layers:
-            at, mlp = blk.self_attn, blk.mlp
-            lin = [_hip(getattr(at, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
-            if not all(isinstance(L, HQQLinearHIP) and L.bias is None and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == 0 for L in lin):
-                return False
-            q, k, v, o, g, u, d = lin
-            if len({(L.nbits, L.group_size, L.in_features) for L in (q, k, v)}) != 1 or len({(L.nbits, L.group_size, L.in_features, L.out_features) for L in (g, u)}) != 1:
-                return False
-            if not ops.axis0_grouped_covers(dt, M, [L.out_features for L in (q, k, v)], q.in_features, q.group_size, q.nbits) or \
-                    not ops.axis0_grouped_covers(dt, M, [g.out_features, u.out_features], g.in_features, g.group_size, g.nbits, ops.BLOCK_SILU):
-                return False
-            if not all(ops.decode_axis0_covers(dt, M, L.out_features, L.in_features, L.group_size, L.nbits) for L in (o, d)):
-                return False
-            for nrm in (blk.input_layernorm, blk.post_attention_layernorm):
-                if nrm.weight.dtype != dt or nrm.weight.shape[0] % 8:
-                    return False
-        return True
-    except AttributeError:
-        return False
+        if not all(ops.decode_axis0_covers(dt, M, L.out_features, L.in_features, L.group_size, L.nbits) for L in (o, d)):
+            return False
+    return True
 
 
 def supports_axis0(model) -> bool:
     """supports() for a model quantised along AXIS 0: an allow-listed architecture (arch_supported), fp16 or bf16, every decoder linear an HQQLinearHIP
     with axis == 0 and no bias; q|k|v share (nbits, group_size) and gate|up share them with equal N, so that each group is ONE grouped launch
     (ops.axis0_grouped_covers, gate|up with BLOCK_SILU); o and down on the single-layer kernel (ops.decode_axis0_covers)"""
-    return _supports_axis0_rows(model, 1)
+    return supports_axis0_batch(model, 1)
 
 
-def supports_axis0_batch(model, B: int) -> bool:
-    """supports_axis0(model) with every launch taking B activation rows (1 <= B <= ops.GEMV_MAX_M)"""
+def batch_covers(dtype, B: int, layers, opts: int = 0) -> bool:
+    """whether the fused decode kernels serve every layer of `layers` — (N, K, group_size, nbits, w3s) each — at M = B activation rows (a pure
+    function of the shapes: no device needed).  The grouped launch (hqq_hip_gemv_grouped) takes a group of layers at B rows where each of them is
+    served on its own, so the rule is per layer: a decode route (ops.route, asked for the layer's layout)."""
     B = int(B)
-    return 1 <= B <= ops.GEMV_MAX_M and _supports_axis0_rows(model, B)
+    if B < 1:
+        return False
+    factored = bool(int(opts) & ops.OPT_FACTORED) and dtype == torch.float16
+    for (N, K, gs, nbits, w3s) in set(layers):   # (a model repeats a few shapes)
+        r = ops.route(dtype, B, (N,), K, gs, nbits, ops.OPT_W3S if w3s else 0)
+        if r not in ops.DECODE_ROUTES:
+            return False
+        # a policy, not a kernel limit: FACTORED batches beyond 8 rows only on the skinny kernel (the row-per-wave kernel would serve them in launches of 8)
+        if factored and B > 8 and r != ops.ROUTE_SKINNY:
+            return False
+    return True
+
+
+def supports_batch(model, B: int) -> bool:
+    """supports(model), and every decoder linear served by a fused decode kernel at B rows (batch_covers, with this module's default option bits)"""
+    if not supports(model):
+        return False
+    specs = [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lins in _decoder_linears(model) for L in lins]
+    return batch_covers(model.model.norm.weight.dtype, B, specs, ops._default_opts)
+
+
+def _gopts(Ls) -> int:
+    lay = ops.OPT_W3S if Ls[0].w3s else 0
+    return ops.layer_opts((ops.OPT_META_SCALABLE if all(L.opts & ops.OPT_META_SCALABLE for L in Ls) else 0) | lay)
 
 
 class FusedLlamaStep:
-    """decode step t -> logits of token t + 1, on the model's own weights and an HF StaticCache that a prefill has filled"""
+    """decode step t of `batch` independent sequences -> logits of their tokens t + 1, on the model's own weights and an HF StaticCache of that batch
+    that a prefill has filled (layer.keys / .values [batch, n_kv, max_cache_len, hd], used in place).  Each sequence has its own position; row b of
+    every glue kernel gives the bits of the batch-1 kernel for sequence b alone, and the linears run at M = batch."""
 
-    def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False):
+    def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
         glue: "folded" — RMSNorm in the q|k|v / gate|up launches' prologue, the residual adds in o's / down's epilogue, SiLU * up in the epilogue of ONE
         paired gate|up layer (csrc/gemv_block.hip: 4 launches + rotary / attention per block; costs a second copy of gate / up's packed levels in the
-        paired layout); "kernels" — round 4's separate glue kernels (9 launches per block); "auto": folded where hqq_hip_gemv_block covers the model."""
+        paired layout); "kernels" — round 4's separate glue kernels (9 launches per block); "auto": folded where hqq_hip_gemv_block covers the model.
+        batch: the number of sequences.  Beyond 1 the model must be one supports_batch (supports_axis0_batch with axis0) accepts at that many rows;
+        the folded launches serve one activation row, so a batch takes the separate glue kernels whatever `glue` allows."""
         # axis0: the model's linears are quantised along axis 0 (supports_axis0).  The step is the glue="kernels" sequence with q|k|v and gate|up through
         # ops.gemv_axis0_grouped (gate|up's reduce applies SiLU * up: no silu_mul launch) and o / down through ops.gemv_axis0, on the layers' own tensors
         # (nothing re-laid out); the folded launches read axis-1 meta and are never taken.
@@ -154,8 +189,9 @@ class FusedLlamaStep:
         inner = model.model
         self.inner = inner
         cfg = model.config
-        self.device = inner.embed_tokens.weight.device
+        self.device = dev = inner.embed_tokens.weight.device
         self.dt = dt = inner.norm.weight.dtype   # fp16 or bf16 (supports())
+        self.B = B = int(batch)
         self.n_heads = cfg.num_attention_heads
         self.n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
         self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
@@ -171,16 +207,18 @@ class FusedLlamaStep:
         if glue not in ("auto", "folded", "kernels"):
             raise ValueError("glue: 'auto', 'folded' or 'kernels'")
         self.axis0 = bool(axis0)
-        if self.axis0 and not supports_axis0(model):
-            raise ValueError("hqq_amd: axis0=True needs a model supports_axis0() accepts")
+        # (a single sequence of an axis-1 model is not asked: its callers ask supports(), and models construct here that it refuses)
+        if (B != 1 or self.axis0) and not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
+            raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows "
+                             f"({'axis0=True: supports_axis0_batch' if self.axis0 else 'supports_batch'})")
         if self.axis0 and glue == "folded":
             raise ValueError("hqq_amd: glue='folded' reads axis-1 meta; an axis-0 model takes the separate glue kernels")
-        lins = [_hip(getattr(b.self_attn, n)) for b in inner.layers for n in ("q_proj", "o_proj")] + [_hip(getattr(b.mlp, n)) for b in inner.layers for n in ("gate_proj", "down_proj")]
-        can_fold = all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=(i % 2 == 0)) for i, L in enumerate(lins)) and \
-            all(_hip(b.mlp.gate_proj).out_features == _hip(b.mlp.up_proj).out_features for b in inner.layers) and not (ops._default_opts & ops.OPT_FACTORED) and \
-            not self.axis0
+        blocks = _decoder_linears(model)
+        can_fold = all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
+                       for (q, _, _, o, g, _, d) in blocks for L, norm in ((q, True), (o, False), (g, True), (d, False))) and \
+            all(g.out_features == u.out_features for (_, _, _, _, g, u, _) in blocks) and not (ops._default_opts & ops.OPT_FACTORED) and not self.axis0 and B == 1
         if glue == "folded" and not can_fold:
-            raise ValueError("hqq_amd: glue='folded' needs fp16 / bf16 layers of 4 / 2 bits or the 3-bit stream layout, group_size 64, hidden size <= 8192")
+            raise ValueError("hqq_amd: glue='folded' needs one sequence and fp16 / bf16 layers of 4 / 2 bits or the 3-bit stream layout, group_size 64, hidden size <= 8192")
         self.folded = can_fold and glue != "kernels"
         # The folded step keeps re-laid-out COPIES of q, k (rotary-paired rows) and of gate | up (one paired layer) beside the layers' own tensors: about
         # +60 % of the decoder's linear-weight bytes (7B at 4 bits: +1.9 GB).  glue="auto" takes them only when they fit with room to spare; a model that filled
@@ -189,8 +227,7 @@ class FusedLlamaStep:
         if self.folded:
             def _nbytes(L):
                 return L.W_q.numel() * L.W_q.element_size() + 2 * L.scale.numel() * L.scale.element_size()
-            need = sum(_nbytes(_hip(getattr(b.self_attn, n))) for b in inner.layers for n in ("q_proj", "k_proj")) + \
-                sum(_nbytes(_hip(getattr(b.mlp, n))) for b in inner.layers for n in ("gate_proj", "up_proj"))
+            need = sum(_nbytes(L) for (q, k, _, _, g, u, _) in blocks for L in (q, k, g, u))
             free_b = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else need * 4
             if glue == "auto" and free_b < need + need // 4 + (1 << 30):
                 import warnings
@@ -200,24 +237,21 @@ class FusedLlamaStep:
             else:
                 self.extra_weight_bytes = need
         self.blocks = []
-        dev = self.device
-        for li, blk in enumerate(inner.layers):
-            at, mlp = blk.self_attn, blk.mlp
-            q, k, v, o = (_hip(getattr(at, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj"))
-            g, u, d = (_hip(getattr(mlp, n)) for n in ("gate_proj", "up_proj", "down_proj"))
+        for li, (blk, (q, k, v, o, g, u, d)) in enumerate(zip(inner.layers, blocks)):
             lay = cache.layers[li]
-            if not getattr(lay, "is_initialized", False) or lay.keys.shape[0] != 1 or lay.keys.shape[2] != max_cache_len or not lay.keys.is_contiguous():
-                raise ValueError("hqq_amd: the fused decode step needs an HF StaticCache that a batch-1 prefill has initialised")
+            if not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (B, self.n_kv, max_cache_len, self.hd) or \
+                    not lay.keys.is_contiguous() or not lay.values.is_contiguous():
+                raise ValueError(f"hqq_amd: the fused decode step needs an initialised HF StaticCache of batch {B} and {max_cache_len} positions")
             self.blocks.append({
-                "attn": at, "n1": blk.input_layernorm, "n2": blk.post_attention_layernorm,
-                "qkv": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (q, k, v)], "qkv_opts": self._gopts((q, k, v)), "qkv_nbits": q.nbits, "qkv_gs": q.group_size, "gu_gs": g.group_size,
-                "o": o, "gu": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (g, u)], "gu_opts": self._gopts((g, u)), "gu_nbits": g.nbits, "d": d,
-                "kc": lay.keys[0], "vc": lay.values[0], "len": lay.cumulative_length,
+                "attn": blk.self_attn, "n1": blk.input_layernorm, "n2": blk.post_attention_layernorm,
+                "qkv": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (q, k, v)], "qkv_opts": _gopts((q, k, v)), "qkv_nbits": q.nbits, "qkv_gs": q.group_size, "gu_gs": g.group_size,
+                "o": o, "gu": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (g, u)], "gu_opts": _gopts((g, u)), "gu_nbits": g.nbits, "d": d,
+                "kc": lay.keys, "vc": lay.values, "len": lay.cumulative_length,
                 # outputs of the launches (static addresses: the step is captured in a hipGraph)
-                "q": torch.empty(1, q.out_features, dtype=dt, device=dev), "k": torch.empty(1, k.out_features, dtype=dt, device=dev),
-                "v": torch.empty(1, v.out_features, dtype=dt, device=dev), "qr": torch.empty(1, self.n_heads, 1, self.hd, dtype=dt, device=dev),
-                "g": torch.empty(1, g.out_features, dtype=dt, device=dev), "u": torch.empty(1, u.out_features, dtype=dt, device=dev),
-                "a": torch.empty(1, g.out_features, dtype=dt, device=dev),
+                "q": torch.empty(B, q.out_features, dtype=dt, device=dev), "k": torch.empty(B, k.out_features, dtype=dt, device=dev),
+                "v": torch.empty(B, v.out_features, dtype=dt, device=dev), "qr": torch.empty(B, self.n_heads, 1, self.hd, dtype=dt, device=dev),
+                "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
+                "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
             })
             if self.folded and attention != "hip" and self.hd % 2 == 0:
                 # q and k in the rotary-paired row order (ops.rotary_pair_layout): the q|k|v launch's epilogue applies the rotary embedding and writes the cache
@@ -243,14 +277,14 @@ class FusedLlamaStep:
                     sub = ops.meta_scalable(pair[1], pair[2], pair[3], g.in_features, g.group_size, g.nbits)
                 self.blocks[-1]["gu_pair"] = [pair]
                 self.blocks[-1]["gu_pair_opts"] = ops.layer_opts((ops.OPT_META_SCALABLE if sub else 0) | (ops.OPT_W3S if g.w3s else 0))
-        self.h = torch.empty(1, self.H, dtype=dt, device=dev)       # the residual stream
-        self.xn = torch.empty(1, self.H, dtype=dt, device=dev)      # its normalised copy, input of the next linears
-        self.delta = torch.empty(1, self.H, dtype=dt, device=dev)   # output of o / down, added by the next add_rmsnorm
-        self.att = torch.empty(1, self.n_heads * self.hd, dtype=dt, device=dev)   # attention output (attention="hip")
+        self.h = torch.empty(B, self.H, dtype=dt, device=dev)       # the residual stream
+        self.xn = torch.empty(B, self.H, dtype=dt, device=dev)      # its normalised copy, input of the next linears
+        self.delta = torch.empty(B, self.H, dtype=dt, device=dev)   # output of o / down, added by the next add_rmsnorm
+        self.att = torch.empty(B, self.n_heads * self.hd, dtype=dt, device=dev)   # attention output (attention="hip")
         self.attn_ws = {}                                                          # splits -> record buffer of the split attention launches
-        # the causal mask of one query over the static cache, in the additive form SDPA turns a boolean mask into on every call
+        # the causal mask of one query per sequence over the static cache, in the additive form SDPA turns a boolean mask into on every call
         # (where(mask, 0, -inf) in the query dtype): built once per token here instead of once per decoder block inside the attention function
-        self.mask = torch.zeros(1, 1, 1, max_cache_len, dtype=dt, device=dev)
+        self.mask = torch.zeros(B, 1, 1, max_cache_len, dtype=dt, device=dev)
         self.ar = torch.arange(max_cache_len, device=dev)
         # cos / sin of every cache position, from the model's own rotary module called once (elementwise in the position: the rows equal what a
         # per-token call returns); rope types whose frequencies depend on the sequence length ("dynamic", "longrope") keep the per-token call
@@ -262,212 +296,24 @@ class FusedLlamaStep:
             self.cos_tab, self.sin_tab = c[0].contiguous(), s_[0].contiguous()   # [max_cache_len, hd]
         self.zero = torch.zeros((), dtype=dt, device=dev)
         self.ninf = torch.full((), float("-inf"), dtype=dt, device=dev)
-        # the front of a step as one launch (ops.token_prologue) where it is a plain table lookup: an ordinary nn.Embedding in the compute dtype and precomputed rotary tables
+        # the front of a step as one launch (ops.token_prologue_batched) where it is a plain table lookup: an ordinary nn.Embedding in the compute dtype and
+        # precomputed rotary tables.  glue="kernels" on an axis-1 model is the comparison leg that keeps the separate front.
         emb = inner.embed_tokens
         self.one_launch_front = bool((glue != "kernels" or self.axis0) and self.cos_tab is not None and type(emb) is torch.nn.Embedding and emb.max_norm is None and emb.weight.dtype == dt
                                      and emb.weight.is_contiguous() and emb.weight.device == self.h.device and self.H % 8 == 0 and dt in (torch.float16, torch.bfloat16))
-        self.cos_v = torch.empty(self.hd, dtype=dt, device=dev)
-        self.sin_v = torch.empty(self.hd, dtype=dt, device=dev)
-
-    @staticmethod
-    def _gopts(Ls) -> int:
-        lay = ops.OPT_W3S if Ls[0].w3s else 0
-        return ops.layer_opts((ops.OPT_META_SCALABLE if all(L.opts & ops.OPT_META_SCALABLE for L in Ls) else 0) | lay)
-
-    @torch.no_grad()
-    def __call__(self, tok: Tensor, pos: Tensor, kv_len: int | None = None) -> Tensor:
-        """tok [1, 1] int64, pos [1] int64 (its position; both on the device) -> logits [1, vocab] of the next token.
-        kv_len (host integer > the position, default the whole cache): HF's attention function attends over the first kv_len cache positions only
-        (masked beyond pos as before) — its cost follows the length it is given, so a caller that knows the position passes a bucket just above it"""
-        inner = self.inner
-        h = self.h
-        # (the position itself is device memory — the step is graph-replayed —: the kernels that index the cache with it skip their
-        #  writes beyond the cache's last slot, csrc/block.hip; callers that know the position on the host check it there, generation.py)
-        if self.one_launch_front:   # embedding row, rotary table row and the causal mask in ONE launch (csrc/block.hip: copies and compares, the same bits as the ops below)
-            ops.token_prologue(tok, pos, inner.embed_tokens.weight, h, self.cos_tab, self.sin_tab, self.cos_v, self.sin_v, None if self.attention == "hip" else self.mask.view(-1))
-            cos, sin = self.cos_v, self.sin_v
-        else:
-            h.copy_(inner.embed_tokens(tok).view(1, self.H))
-            if self.cos_tab is not None:
-                cos, sin = self.cos_tab.index_select(0, pos).view(-1), self.sin_tab.index_select(0, pos).view(-1)
-            else:
-                cos, sin = inner.rotary_emb(h.view(1, 1, self.H), pos.view(1, 1))   # [1, 1, hd] each, the model's own rotary module
-                cos, sin = cos.reshape(-1).contiguous(), sin.reshape(-1).contiguous()
-            if self.attention != "hip":
-                torch.where(self.ar <= pos, self.zero, self.ninf, out=self.mask.view(-1))   # the causal mask of one query at `pos` over the static cache
-        kvl = self.L if kv_len is None else min(int(kv_len), self.L)
-        mask = self.mask[..., :kvl]
-        splits = ops.attn_splits(kvl) if self.attention == "hip" else 1   # (kernel attention: kv_len only picks how many workgroups share a head)
-        if splits > 1 and splits not in self.attn_ws:
-            self.attn_ws[splits] = ops.attn_workspace(self.device, self.n_heads, self.hd, splits)
-        delta = None
-        for b in self.blocks:
-            at = b["attn"]
-            K = self.H
-            if self.folded and "qkv_rope" in b:   # RMSNorm in the prologue, rotary embedding + cache write in the epilogue: q|k|v lands rotated in qr / the caches
-                ops.gemv_block(h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv_rope"], K, b["qkv_gs"], b["qkv_nbits"], [b["qr"], b["kc"], b["vc"]],
-                               ops.BLOCK_NORM | ops.BLOCK_ROPE, opts=b["qkv_rope_opts"], rope=(cos, sin, pos, self.hd, self.L))
-            elif self.folded:   # RMSNorm in the launch's prologue: every workgroup normalises h itself while its first weights are in flight
-                ops.gemv_block(h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], [b["q"], b["k"], b["v"]], ops.BLOCK_NORM, opts=b["qkv_opts"])
-            else:
-                ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
-                if self.axis0:
-                    ops.gemv_axis0_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]])
-                else:
-                    ops.gemv_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]], opts=b["qkv_opts"])
-            if self.attention == "hip":   # rotary + cache write + attention: one launch
-                att = ops.rope_attn_decode(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
-                                           workspace=self.attn_ws.get(splits))
-            else:
-                if not (self.folded and "qkv_rope" in b):
-                    ops.rope_cache(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
-                att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :kvl].unsqueeze(0), b["vc"][:, :kvl].unsqueeze(0), mask, dropout=0.0, scaling=at.scaling)
-            o, d = b["o"], b["d"]
-            if self.folded:
-                # o: h += o(att) in the epilogue; gate|up: RMSNorm prologue + silu(gate) * up epilogue on the paired layer; down: h += down(a) in the epilogue
-                ops.gemv_block(att.reshape(1, -1), None, 0.0, [(o.W_q, o.scale, o.zero, o.out_features)], o.in_features, o.group_size, o.nbits, [h], ops.BLOCK_RESID,
-                               opts=ops.layer_opts(o.opts))
-                ops.gemv_block(h, b["n2"].weight, b["n2"].variance_epsilon, b["gu_pair"], K, b["gu_gs"], b["gu_nbits"], [b["a"]], ops.BLOCK_NORM | ops.BLOCK_SILU, opts=b["gu_pair_opts"])
-                ops.gemv_block(b["a"], None, 0.0, [(d.W_q, d.scale, d.zero, d.out_features)], d.in_features, d.group_size, d.nbits, [h], ops.BLOCK_RESID, opts=ops.layer_opts(d.opts))
-                continue
-            if self.axis0:   # o -> norm -> gate|up with SiLU * up in its reduce -> down: the layers' own axis-0 tensors
-                ops.gemv_axis0(att.reshape(1, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta)
-                ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
-                ops.gemv_axis0_grouped(self.xn, b["gu"], K, b["gu_gs"], b["gu_nbits"], outs=[b["a"]], flags=ops.BLOCK_SILU)
-                ops.gemv_axis0(b["a"], d.W_q, d.scale, d.zero, None, d.out_features, d.in_features, d.group_size, d.nbits, out=self.delta)
-                delta = self.delta
-                continue
-            ops.gemv(att.reshape(1, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta,
-                     opts=ops.layer_opts(o.opts))
-            ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
-            ops.gemv_grouped(self.xn, b["gu"], K, b["gu_gs"], b["gu_nbits"], outs=[b["g"], b["u"]], opts=b["gu_opts"])
-            ops.silu_mul(b["g"], b["u"], out=b["a"])
-            ops.gemv(b["a"], d.W_q, d.scale, d.zero, None, d.out_features, d.in_features, d.group_size, d.nbits, out=self.delta, opts=ops.layer_opts(d.opts))
-            delta = self.delta
-        ops.add_rmsnorm(h, delta, inner.norm.weight, inner.norm.variance_epsilon, out=self.xn)
-        return self.model.lm_head(self.xn)
-
-    def account_tokens(self, n: int) -> None:
-        """StaticLayer.update's bookkeeping for the n tokens the fused steps appended (kept out of the captured step: one add per layer)"""
-        for b in self.blocks:
-            b["len"].add_(n)
-
-
-# ---- a decode step of B independent sequences ------------------------------------------------------------------------------------------------
-def batch_covers(dtype, B: int, layers, opts: int = 0) -> bool:
-    """whether the fused decode kernels serve every layer of `layers` — (N, K, group_size, nbits, w3s) each — at M = B activation rows (a pure
-    function of the shapes: no device needed).  The grouped launch (hqq_hip_gemv_grouped) takes a group of layers at B rows where each of them is
-    served on its own, so the rule is per layer: a decode route (ops.route, asked for the layer's layout)."""
-    B = int(B)
-    if B < 1:
-        return False
-    factored = bool(int(opts) & ops.OPT_FACTORED) and dtype == torch.float16
-    for (N, K, gs, nbits, w3s) in set(layers):   # (a model repeats a few shapes)
-        r = ops.route(dtype, B, (N,), K, gs, nbits, ops.OPT_W3S if w3s else 0)
-        if r not in ops.DECODE_ROUTES:
-            return False
-        # a policy, not a kernel limit: FACTORED batches beyond 8 rows only on the skinny kernel (the row-per-wave kernel would serve them in launches of 8)
-        if factored and B > 8 and r != ops.ROUTE_SKINNY:
-            return False
-    return True
-
-
-def _decoder_linears(model):
-    """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers"""
-    return [[_hip(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
-            for b in model.model.layers]
-
-
-def supports_batch(model, B: int) -> bool:
-    """supports(model), and every decoder linear served by a fused decode kernel at B rows (batch_covers, with this module's default option bits)"""
-    if not supports(model):
-        return False
-    specs = [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lins in _decoder_linears(model) for L in lins]
-    return batch_covers(model.model.norm.weight.dtype, B, specs, ops._default_opts)
-
-
-class FusedLlamaBatchStep:
-    """decode step t of B independent sequences -> logits of their tokens t + 1, on the model's own weights and an HF StaticCache of batch B
-    (layer.keys / .values [B, n_kv, max_cache_len, hd], used in place).  Each sequence has its own position; the block is FusedLlamaStep's
-    glue="kernels" route with every launch taking the B rows at once:
-        add_rmsnorm -> q|k|v (one grouped GEMV, M = B) -> rope_cache_batched -> attention -> o -> add_rmsnorm -> gate|up (one grouped GEMV) -> silu_mul -> down
-    Attention "sdpa": HF's attention function on the B-row cache with the [B, 1, 1, kv_len] mask of token_prologue_batched; "hip":
-    rope_attn_decode_batched.  Row b of every glue kernel gives the bits of the batch-1 kernel for sequence b alone; the linears run at M = B
-    (supports_batch).  The folded launches (ops.gemv_block) are batch-1 only and never used here."""
-
-    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False):
-        """axis0: the model is quantised along axis 0 (supports_axis0_batch): q|k|v and gate|up through ops.gemv_axis0_grouped (SiLU * up in gate|up's
-        reduce, no silu_mul launch), o and down through ops.gemv_axis0, as in FusedLlamaStep(axis0=True)"""
-        from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
-        from transformers.models.llama.modeling_llama import eager_attention_forward
-        self.model = model
-        inner = model.model
-        self.inner = inner
-        cfg = model.config
-        self.device = dev = inner.embed_tokens.weight.device
-        self.dt = dt = inner.norm.weight.dtype
-        self.B = B = int(batch)
-        self.n_heads = cfg.num_attention_heads
-        self.n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
-        self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-        self.H = cfg.hidden_size
-        self.L = max_cache_len
-        self.attn_fn = ALL_ATTENTION_FUNCTIONS.get_interface(cfg._attn_implementation, eager_attention_forward)
-        if attention not in ("sdpa", "hip"):
-            raise ValueError("attention: 'sdpa' or 'hip'")
-        if attention == "hip" and (self.hd not in (64, 128, 256) or getattr(cfg, "sliding_window", None) or getattr(cfg, "attn_logit_softcapping", None)
-                                   or max_cache_len > 30000):
-            raise ValueError("hqq_amd: the decode-attention kernel covers plain softmax attention with head_dim 64 / 128 / 256 and caches of <= 30000 positions")
-        self.attention = attention
-        self.axis0 = bool(axis0)
-        if not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
-            raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows "
-                             f"({'supports_axis0_batch' if self.axis0 else 'supports_batch'})")
-        self.blocks = []
-        for li, (blk, (q, k, v, o, g, u, d)) in enumerate(zip(inner.layers, _decoder_linears(model))):
-            lay = cache.layers[li]
-            if not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (B, self.n_kv, max_cache_len, self.hd) or \
-                    not lay.keys.is_contiguous() or not lay.values.is_contiguous():
-                raise ValueError(f"hqq_amd: the batched decode step needs an initialised HF StaticCache of batch {B} and {max_cache_len} positions")
-            self.blocks.append({
-                "attn": blk.self_attn, "n1": blk.input_layernorm, "n2": blk.post_attention_layernorm,
-                "qkv": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (q, k, v)], "qkv_opts": FusedLlamaStep._gopts((q, k, v)), "qkv_nbits": q.nbits,
-                "qkv_gs": q.group_size, "o": o, "gu": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (g, u)], "gu_opts": FusedLlamaStep._gopts((g, u)),
-                "gu_nbits": g.nbits, "gu_gs": g.group_size, "d": d, "kc": lay.keys, "vc": lay.values,
-                # outputs of the launches (static addresses: the step is captured in a hipGraph)
-                "q": torch.empty(B, q.out_features, dtype=dt, device=dev), "k": torch.empty(B, k.out_features, dtype=dt, device=dev),
-                "v": torch.empty(B, v.out_features, dtype=dt, device=dev), "qr": torch.empty(B, self.n_heads, 1, self.hd, dtype=dt, device=dev),
-                "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
-                "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
-            })
-        self.h = torch.empty(B, self.H, dtype=dt, device=dev)
-        self.xn = torch.empty(B, self.H, dtype=dt, device=dev)
-        self.delta = torch.empty(B, self.H, dtype=dt, device=dev)
-        self.att = torch.empty(B, self.n_heads * self.hd, dtype=dt, device=dev)
-        self.attn_ws = {}
-        self.mask = torch.zeros(B, 1, 1, max_cache_len, dtype=dt, device=dev)   # one query per sequence, additive form
-        self.ar = torch.arange(max_cache_len, device=dev)
-        self.cos_tab = self.sin_tab = None   # (FusedLlamaStep's tables: rope types whose frequencies follow the sequence length keep the per-token call)
-        if getattr(inner.rotary_emb, "rope_type", "default") in ("default", "linear", "llama3", "yarn") and \
-                max_cache_len <= getattr(cfg, "max_position_embeddings", max_cache_len):
-            with torch.no_grad():
-                c, s_ = inner.rotary_emb(torch.empty(1, 1, self.H, dtype=dt, device=dev), self.ar.view(1, -1))
-            self.cos_tab, self.sin_tab = c[0].contiguous(), s_[0].contiguous()
-        self.zero = torch.zeros((), dtype=dt, device=dev)
-        self.ninf = torch.full((), float("-inf"), dtype=dt, device=dev)
-        emb = inner.embed_tokens
-        self.one_launch_front = bool(self.cos_tab is not None and type(emb) is torch.nn.Embedding and emb.max_norm is None and emb.weight.dtype == dt
-                                     and emb.weight.is_contiguous() and emb.weight.device == self.h.device and self.H % 8 == 0)
         self.cos_v = torch.empty(B, self.hd, dtype=dt, device=dev)
         self.sin_v = torch.empty(B, self.hd, dtype=dt, device=dev)
 
     @torch.no_grad()
     def __call__(self, tok: Tensor, pos: Tensor, kv_len: int | None = None) -> Tensor:
-        """tok [B, 1] int64, pos [B] int64 (each sequence's position; both on the device) -> logits [B, vocab].  kv_len (host integer > the LARGEST
-        position, default the whole cache): HF's attention function attends over that many cache positions (each row masked beyond its own
-        position); the kernel attention takes its split count from it"""
+        """tok [B, 1] int64, pos [B] int64 (each sequence's position; both on the device) -> logits [B, vocab] of the next tokens.
+        kv_len (host integer > the LARGEST position, default the whole cache): HF's attention function attends over the first kv_len cache positions only
+        (each row masked beyond its own position) — its cost follows the length it is given, so a caller that knows the positions passes a bucket just
+        above them; the kernel attention takes its split count from it"""
         inner, B, h = self.inner, self.B, self.h
-        if self.one_launch_front:
+        # (the positions themselves are device memory — the step is graph-replayed —: the kernels that index the cache with them skip their
+        #  writes beyond the cache's last slot, csrc/block.hip; callers that know the positions on the host check them there, generation.py)
+        if self.one_launch_front:   # embedding rows, rotary table rows and the causal masks in ONE launch (csrc/block.hip: copies and compares, the same bits as the ops below)
             ops.token_prologue_batched(tok, pos, inner.embed_tokens.weight, h, self.cos_tab, self.sin_tab, self.cos_v, self.sin_v,
                                        None if self.attention == "hip" else self.mask.view(B, -1))
             cos, sin = self.cos_v, self.sin_v
@@ -479,41 +325,75 @@ class FusedLlamaBatchStep:
                 cos, sin = inner.rotary_emb(h.view(B, 1, self.H), pos.view(B, 1))   # [B, 1, hd] each, the model's own rotary module
                 cos, sin = cos.reshape(B, -1).contiguous(), sin.reshape(B, -1).contiguous()
             if self.attention != "hip":
-                torch.where(self.ar.view(1, -1) <= pos.view(-1, 1), self.zero, self.ninf, out=self.mask.view(B, -1))
+                torch.where(self.ar.view(1, -1) <= pos.view(-1, 1), self.zero, self.ninf, out=self.mask.view(B, -1))   # the causal mask of one query per row at its `pos`
         kvl = self.L if kv_len is None else min(int(kv_len), self.L)
         mask = self.mask[..., :kvl]
-        splits = ops.attn_splits(kvl) if self.attention == "hip" else 1
+        splits = ops.attn_splits(kvl) if self.attention == "hip" else 1   # (kernel attention: kv_len only picks how many workgroups share a head)
         if splits > 1 and splits not in self.attn_ws:
             self.attn_ws[splits] = ops.attn_workspace_batched(self.device, B, self.n_heads, self.hd, splits)
         delta = None
         K = self.H
         for b in self.blocks:
             at = b["attn"]
-            ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
-            if self.axis0:
-                ops.gemv_axis0_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]])
+            if self.folded and "qkv_rope" in b:   # RMSNorm in the prologue, rotary embedding + cache write in the epilogue: q|k|v lands rotated in qr / the caches
+                ops.gemv_block(h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv_rope"], K, b["qkv_gs"], b["qkv_nbits"], [b["qr"], b["kc"], b["vc"]],
+                               ops.BLOCK_NORM | ops.BLOCK_ROPE, opts=b["qkv_rope_opts"], rope=(cos, sin, pos, self.hd, self.L))
+            elif self.folded:   # RMSNorm in the launch's prologue: every workgroup normalises h itself while its first weights are in flight
+                ops.gemv_block(h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], [b["q"], b["k"], b["v"]], ops.BLOCK_NORM, opts=b["qkv_opts"])
             else:
-                ops.gemv_grouped(self.xn, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], outs=[b["q"], b["k"], b["v"]], opts=b["qkv_opts"])
+                ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
+                self._grouped(b, "qkv", [b["q"], b["k"], b["v"]])
             if self.attention == "hip":   # rotary + cache write + attention: one launch
                 att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
                                                    workspace=self.attn_ws.get(splits))
             else:
-                ops.rope_cache_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
+                if not (self.folded and "qkv_rope" in b):
+                    ops.rope_cache_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
                 att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :, :kvl], b["vc"][:, :, :kvl], mask, dropout=0.0, scaling=at.scaling)
             o, d = b["o"], b["d"]
-            if self.axis0:
-                ops.gemv_axis0(att.reshape(B, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta)
-                ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
-                ops.gemv_axis0_grouped(self.xn, b["gu"], K, b["gu_gs"], b["gu_nbits"], outs=[b["a"]], flags=ops.BLOCK_SILU)
-                ops.gemv_axis0(b["a"], d.W_q, d.scale, d.zero, None, d.out_features, d.in_features, d.group_size, d.nbits, out=self.delta)
-                delta = self.delta
+            if self.folded:
+                # o: h += o(att) in the epilogue; gate|up: RMSNorm prologue + silu(gate) * up epilogue on the paired layer; down: h += down(a) in the epilogue
+                ops.gemv_block(att.reshape(1, -1), None, 0.0, [(o.W_q, o.scale, o.zero, o.out_features)], o.in_features, o.group_size, o.nbits, [h], ops.BLOCK_RESID,
+                               opts=ops.layer_opts(o.opts))
+                ops.gemv_block(h, b["n2"].weight, b["n2"].variance_epsilon, b["gu_pair"], K, b["gu_gs"], b["gu_nbits"], [b["a"]], ops.BLOCK_NORM | ops.BLOCK_SILU, opts=b["gu_pair_opts"])
+                ops.gemv_block(b["a"], None, 0.0, [(d.W_q, d.scale, d.zero, d.out_features)], d.in_features, d.group_size, d.nbits, [h], ops.BLOCK_RESID, opts=ops.layer_opts(d.opts))
                 continue
-            ops.gemv(att.reshape(B, -1), o.W_q, o.scale, o.zero, None, o.out_features, o.in_features, o.group_size, o.nbits, out=self.delta,
-                     opts=ops.layer_opts(o.opts))
+            self._single(att.reshape(B, -1), o)
             ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
-            ops.gemv_grouped(self.xn, b["gu"], K, b["gu_gs"], b["gu_nbits"], outs=[b["g"], b["u"]], opts=b["gu_opts"])
-            ops.silu_mul(b["g"], b["u"], out=b["a"])
-            ops.gemv(b["a"], d.W_q, d.scale, d.zero, None, d.out_features, d.in_features, d.group_size, d.nbits, out=self.delta, opts=ops.layer_opts(d.opts))
+            if self.axis0:   # SiLU * up rides in the grouped launch's reduce: no silu_mul launch
+                self._grouped(b, "gu", [b["a"]], flags=ops.BLOCK_SILU)
+            else:
+                self._grouped(b, "gu", [b["g"], b["u"]])
+                ops.silu_mul(b["g"], b["u"], out=b["a"])
+            self._single(b["a"], d)
             delta = self.delta
         ops.add_rmsnorm(h, delta, inner.norm.weight, inner.norm.variance_epsilon, out=self.xn)
         return self.model.lm_head(self.xn)
+
+    def _grouped(self, b, which: str, outs, flags: int = 0) -> None:
+        """q|k|v ("qkv") or gate|up ("gu") of block b on the normalised rows self.xn: one grouped launch, on the layers' own tensors"""
+        if self.axis0:
+            ops.gemv_axis0_grouped(self.xn, b[which], self.H, b[which + "_gs"], b[which + "_nbits"], outs=outs, flags=flags)
+        else:
+            ops.gemv_grouped(self.xn, b[which], self.H, b[which + "_gs"], b[which + "_nbits"], outs=outs, opts=b[which + "_opts"])
+
+    def _single(self, x: Tensor, L) -> None:
+        """o or down: self.delta = L(x), added to the residual stream by the next add_rmsnorm"""
+        if self.axis0:
+            ops.gemv_axis0(x, L.W_q, L.scale, L.zero, None, L.out_features, L.in_features, L.group_size, L.nbits, out=self.delta)
+        else:
+            ops.gemv(x, L.W_q, L.scale, L.zero, None, L.out_features, L.in_features, L.group_size, L.nbits, out=self.delta, opts=ops.layer_opts(L.opts))
+
+    def account_tokens(self, n: int) -> None:
+        """StaticLayer.update's bookkeeping for the n tokens the fused steps appended (kept out of the captured step: one add per layer).  For the
+        single-sequence caller: the rows of a batch have different lengths, and nothing reads a B-row cache's cumulative_length"""
+        for b in self.blocks:
+            b["len"].add_(n)
+
+
+class FusedLlamaBatchStep(FusedLlamaStep):
+    """FusedLlamaStep under the name and positional signature the batched callers construct it by: no `glue` argument ("auto": the one-launch front
+    wherever the tables exist)"""
+
+    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False):
+        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch)
