@@ -67,6 +67,9 @@ SYMBOLS = {
     # axis-0 layers at 17..256 rows (csrc/gemm_axis0.hip)
     "hqq_hip_gemm_axis0_workspace_bytes": (_sz, [_i32, _i64, _i64, _i64, _i64, _i32]),
     "hqq_hip_gemm_axis0": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _u32, _vp, _sz, _vp]),
+    # dx = g . dequantize(W_q) for axis-1 layers (csrc/gemm_dgrad.hip)
+    "hqq_hip_gemm_dgrad_covers": (_i32, [_i32, _i64, _i64, _i64, _i64, _i32]),
+    "hqq_hip_gemm_dgrad": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

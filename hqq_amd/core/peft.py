@@ -1,0 +1,212 @@
+"""LoRA adapters over quantised linears: the host mirror of hqq/core/peft.py.
+
+`HQQLinearLoRA` wraps a linear (an `HQQLinear`, or any module with `in_features` / `out_features` / `bias`) and adds the trainable low-rank
+pair lora_A [in, r], lora_B [r, out]: y = linear(x) + ((x @ A) @ B * scaling).to(x.dtype) (+ bias), in the reference's operation order.  The base layer
+stays frozen; its gradient with respect to the input runs through HQQLinear's autograd route (fused `hqq_hip_gemm_dgrad` where HQQLinear routes it there,
+dequantise + matmul elsewhere).  `PeftUtils` adds the adapters to a whole model, casts them, and saves / loads them in the reference's v0.2 file format
+({"peft_config": ..., "parameters": {module_name: state_dict}}), so that adapter files travel both ways.
+
+Linears are found by qualified-name suffix ("tag"), exactly as `hqq_amd.utils.model.quantize_model` finds them; there is no model zoo and no base class.
+
+Not covered (the reference's experimental or merge paths): HQQLinearLoRAWithFakeQuant, HQQLinearGroupedProj, merge_and_quantize / PeftUtils.merge_lora,
+and training through HQQLinearHIP (backends/hip.py), which stays inference-only.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional
+
+import torch
+from torch import Tensor, float16, float32, nn
+
+
+def _get_dense_param(in_features: int, out_features: int, device="cuda", trainable: bool = True, dtype: torch.dtype = float32) -> nn.Parameter:
+    """a trainable [in, out] matrix with nn.Linear's initialisation (peft.py:14-28)"""
+    W = nn.Linear(in_features, out_features, bias=False).weight.data.t().to(dtype).to(device).contiguous()
+    return nn.Parameter(W, requires_grad=trainable)
+
+
+class HQQLinearLoRA(nn.Module):
+    """peft.py:32-224.  peft_config: r, lora_alpha, and optionally dropout (0), train_dtype (fp32), train_bias (False),
+    lora_init ({"lora_A": [in, r], "lora_B": [r, out]})."""
+
+    def __init__(self, linear_layer: nn.Module, peft_config: dict):
+        super().__init__()
+        self.device = linear_layer.device if hasattr(linear_layer, "device") else next(linear_layer.parameters()).device
+        self.train_dtype = peft_config.get("train_dtype", torch.float)
+
+        self.linear_layer = linear_layer
+        self.in_features = linear_layer.in_features
+        self.out_features = linear_layer.out_features
+
+        # the bias moves from the wrapped layer into the wrapper
+        self.bias = None if linear_layer.bias is None else linear_layer.bias.clone()
+        self.linear_layer.bias = None
+        self.train_bias = peft_config.get("train_bias", False)
+        if self.bias is not None:
+            self.bias = nn.Parameter(self.bias, requires_grad=self.train_bias)
+            if self.train_bias:
+                self.bias.data = self.bias.data.to(self.train_dtype)
+        elif self.train_bias:
+            self.bias = nn.Parameter(torch.zeros((self.out_features,), device=self.device, dtype=self.train_dtype), requires_grad=True)
+
+        p_drop = peft_config.get("dropout", 0.0)
+        self.peft_drop = nn.Dropout(p=p_drop) if p_drop > 0.0 else nn.Identity()
+
+        self.peft_config = peft_config
+        self.lora_alpha = peft_config["lora_alpha"]
+        self.r = peft_config["r"]
+        self.scaling = self.lora_alpha / self.r
+        self.lora_A = _get_dense_param(self.in_features, self.r, device=self.device, trainable=True, dtype=self.train_dtype)
+        self.lora_B = _get_dense_param(self.r, self.out_features, device=self.device, trainable=True, dtype=self.train_dtype)
+        if "lora_init" in peft_config:
+            init = peft_config["lora_init"]
+            assert (init["lora_A"].shape[0], init["lora_B"].shape[1]) == (self.in_features, self.out_features), (
+                f"Invalid init LoRA weight shapes. Expected: lora_A: {self.in_features} x r , lora_B: r x {self.out_features})")
+            self.lora_A.data = init["lora_A"].to(device=self.device, dtype=self.train_dtype)
+            self.lora_B.data = init["lora_B"].to(device=self.device, dtype=self.train_dtype)
+        else:   # as the original LoRA implementation
+            nn.init.kaiming_uniform_(self.lora_A, a=math.sqrt(5))
+            nn.init.zeros_(self.lora_B)
+
+        # compute dtype: what load_state_dict casts to (inference)
+        if hasattr(self.linear_layer, "compute_dtype"):
+            self.compute_dtype = self.linear_layer.compute_dtype
+        else:
+            fp = [p for p in self.linear_layer.parameters() if p.is_floating_point()]
+            self.compute_dtype = fp[0].dtype if fp else self.train_dtype
+
+    def forward_lora(self, x: Tensor) -> Tensor:   # in lora_A's dtype
+        return torch.matmul(torch.matmul(self.peft_drop(x.to(self.lora_A.dtype)), self.lora_A), self.lora_B) * self.scaling
+
+    def forward(self, x: Tensor) -> Tensor:
+        x_dtype = x.dtype
+        # the reference's operations in its order, out of place: with a gradient flowing, HQQLinear's output is a view made inside its autograd
+        # function, which autograd does not allow to be modified in place
+        out = self.linear_layer(x)
+        if self.train_bias:
+            out = out + (self.forward_lora(x) + self.bias).to(x_dtype)
+        else:
+            out = out + self.forward_lora(x).to(x_dtype)
+            if self.bias is not None:
+                out = out + self.bias
+        return out
+
+    def merge_and_quantize(self, quant_config: dict):
+        raise NotImplementedError("hqq_amd: merging an adapter back into a quantised layer (peft.py:167-190) is not covered")
+
+    def cast(self, dtype: torch.dtype = float16):
+        self.lora_A.data = self.lora_A.data.to(dtype)
+        self.lora_B.data = self.lora_B.data.to(dtype)
+        if self.bias is not None:
+            self.bias.data = self.bias.data.to(dtype)
+        if isinstance(self.scaling, nn.Parameter):
+            self.scaling.data = self.scaling.data.to(dtype)
+        elif isinstance(self.scaling, Tensor):
+            self.scaling = self.scaling.to(dtype)
+        return self
+
+    def state_dict(self, *args, **kwargs):
+        return {"lora_A": self.lora_A.data, "lora_B": self.lora_B.data, "scaling": self.scaling, "bias": self.bias}
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        to = dict(device=self.device, dtype=self.compute_dtype)
+        self.lora_A.data = state_dict["lora_A"].data.to(**to)
+        self.lora_B.data = state_dict["lora_B"].data.to(**to)
+        if state_dict["bias"] is not None:
+            if self.bias is None:   # (the reference fails on None.data here; a file that carries a bias gets it)
+                self.bias = nn.Parameter(state_dict["bias"].data.to(**to), requires_grad=self.train_bias)
+            else:
+                self.bias.data = state_dict["bias"].data.to(**to)
+        scaling = state_dict["scaling"]
+        if isinstance(scaling, nn.Parameter):
+            self.scaling = nn.Parameter(scaling.data.to(**to), requires_grad=scaling.requires_grad)
+        elif isinstance(scaling, Tensor):
+            self.scaling = scaling.to(**to)
+        elif isinstance(scaling, (int, float)):
+            self.scaling = scaling
+
+
+_HQQ_LORA_CLASSES = [HQQLinearLoRA]
+_HQQ_LORA_MAPPING = {"default": HQQLinearLoRA}
+
+
+def is_hqq_lora_layer(layer) -> bool:
+    return type(layer) in _HQQ_LORA_CLASSES
+
+
+def autoname_modules(model: nn.Module) -> None:
+    for name, module in model.named_modules():
+        module.name = name
+
+
+def _is_linear(mod: nn.Module) -> bool:
+    from .quantize import HQQLinear   # (imported late: this module loads without the native library)
+    return isinstance(mod, (nn.Linear, HQQLinear))
+
+
+def patch_linear_add_peft(layer: nn.Module, patch_params: Optional[dict]) -> nn.Module:
+    if not patch_params:
+        return layer
+    lora_type = patch_params.get("lora_type", "default")
+    if lora_type not in _HQQ_LORA_MAPPING:
+        raise NotImplementedError(f"hqq_amd: lora_type {lora_type!r} is not covered (only 'default')")
+    return _HQQ_LORA_MAPPING[lora_type](layer, patch_params)
+
+
+def _lora_layers(model: nn.Module):
+    return [(name, mod) for name, mod in model.named_modules() if is_hqq_lora_layer(mod)]
+
+
+class PeftUtils:
+    """peft.py:414-555 without the model zoo: the linears are the modules whose qualified name ends with a key of peft_config."""
+
+    @classmethod
+    def add_lora(cls, model: nn.Module, peft_config: Dict[str, Optional[dict]], base_class=None, verbose: bool = False) -> None:
+        for param in model.parameters():
+            param.requires_grad = False
+        tags = list(peft_config)
+        todo = []
+        for name, mod in model.named_modules():
+            if _is_linear(mod):
+                tag = next((t for t in tags if name.endswith(t)), None)
+                if tag is not None and peft_config.get(tag):
+                    todo.append((name, tag))
+        for name, tag in todo:
+            parent_name, _, child = name.rpartition(".")
+            parent = model.get_submodule(parent_name) if parent_name else model
+            setattr(parent, child, patch_linear_add_peft(getattr(parent, child), peft_config[tag]))
+            if verbose:
+                print(f"lora {name}")
+        autoname_modules(model)
+        model.peft_config = peft_config
+
+    @classmethod
+    def merge_lora(cls, model, merge_lora_params, base_class=None, verbose: bool = False) -> None:
+        raise NotImplementedError("hqq_amd: merging adapters back into quantised layers (peft.py:452-461) is not covered")
+
+    @classmethod
+    def cast_lora_weights(cls, model: nn.Module, dtype: torch.dtype, base_class=None, verbose: bool = False) -> None:
+        for _, layer in _lora_layers(model):
+            layer.cast(dtype)
+
+    @classmethod
+    def save_lora_weights(cls, model: nn.Module, filename: str, base_class=None, verbose: bool = False) -> None:
+        autoname_modules(model)
+        params = {layer.name: layer.state_dict() for _, layer in _lora_layers(model)}
+        torch.save({"peft_config": model.peft_config, "parameters": params}, filename)
+
+    @classmethod
+    def load_lora_weights(cls, model: nn.Module, filename: str, base_class=None, verbose: bool = False) -> None:
+        lora_data = torch.load(filename, map_location="cpu", weights_only=True)
+        if ("peft_config" in lora_data) and ("parameters" in lora_data):   # v0.2: the adapters are created where the model has none
+            params = lora_data["parameters"]
+            if not hasattr(model, "peft_config"):
+                cls.add_lora(model=model, peft_config=lora_data["peft_config"])
+        else:                                                               # v0.1: the bare {module_name: state_dict}
+            if not hasattr(model, "peft_config"):
+                raise Exception("Using older version of lora weights. LoRa modules should be manually added in this case.")
+            params = lora_data
+        autoname_modules(model)
+        for _, layer in _lora_layers(model):
+            layer.load_state_dict(params[layer.name])

@@ -531,6 +531,23 @@ class HQQLinear(nn.Module):
             c = self._w3s = (key, Ws, o)
         return c[1], c[2]   # (in-place edits through W_q.data / meta[...].data bypass the version counters: call .cuda(device) again — it drops the copy — after such an edit)
 
+    # the backward with respect to the input, grad @ dequantize(W_q): one fused launch (csrc/gemm_dgrad.hip) instead of dequantise + torch.matmul, for up to
+    # ops.DGRAD_ROUTE_MAX_M rows of grad.  HQQLinear.fused_backward = False keeps dequantise + matmul at every size.
+    fused_backward = True
+
+    def _dgrad_kernel_ok(self, grad: Tensor) -> bool:
+        """a gradient [*, out_features] whose product with the dequantised weight hqq_hip_gemm_dgrad serves: what _fused_ok() admits, byte containers,
+        a shape ops.gemm_dgrad_covers() accepts, and no more rows than the measured cut-off"""
+        m = self.meta
+        if not self._fused_ok(grad) or m["packing"] not in ("8bit_u8", "4bit_u8", "2bit_u8") or m["zero"].dtype != grad.dtype:
+            return False
+        N, K = (int(v) for v in m["shape"])
+        gs = int(m["group_size"])
+        if grad.shape[-1] != N or m["scale"].numel() != N * K // gs or m["zero"].numel() != N * K // gs:
+            return False
+        rows = grad.numel() // N
+        return rows <= ops.DGRAD_ROUTE_MAX_M and ops.gemm_dgrad_covers(grad.dtype, rows, N, K, gs, Quantizer._packing_bits[m["packing"]])
+
     def _matmul_hip(self, x: Tensor, transpose: bool = True, bias=None) -> Tensor:
         if transpose and self._axis0_kernel_ok(x):
             m = self.meta
@@ -547,6 +564,11 @@ class HQQLinear(nn.Module):
                     return ops.forward(x, got[0], m["scale"], m["zero"], bias, N, K, m["group_size"], 3, opts=ops.layer_opts(got[1]))
             return ops.forward(x, W_q, m["scale"], m["zero"], bias, N, K, m["group_size"], Quantizer._packing_bits[m["packing"]],
                                opts=ops.layer_opts(getattr(self, "_hip_opts", 0)))
+        if not transpose and bias is None and HQQLinear.fused_backward and self._dgrad_kernel_ok(x):
+            m = self.meta
+            N, K = m["shape"]
+            W_q = self.W_q.view(m["unpack_view_dtype"]) if m["view_as_float"] else self.W_q
+            return ops.gemm_dgrad(x, W_q, m["scale"], m["zero"], int(N), int(K), int(m["group_size"]), Quantizer._packing_bits[m["packing"]])
         out = self.matmul(x, transpose=transpose)
         if bias is not None:
             out += bias

@@ -718,6 +718,54 @@ def gemm_axis0(x: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, bias, N: int
     return out.reshape(*x.shape[:-1], N)
 
 
+# The backward of an axis-1 layer with respect to its input, dx = g @ dequantize(W_q) (csrc/gemm_dgrad.hip), against what _MatmulNoCache.backward has always
+# run: the HIP dequantise kernel (2 N K bytes written, then read back) + torch.matmul.  HQQLinear._matmul_hip(transpose=False) takes the fused kernel up to
+# this many rows of g.  The rule is AXIS0_GEMM_ROUTE_MAX_M's: the largest measured row count at which the fused kernel is at least 10 % ahead on EVERY
+# measured shape (tools/dgrad_bench.py; profiles/dgrad_summary.md holds the table: 1.42x to 1.87x ahead at 16 rows on every shape; at 64 rows 1.04x on
+# 11008 x 4096, so the route ends at 16; from 1024 rows the composed route is 2x to 3x faster).  0 would mean "opt-in only".
+DGRAD_ROUTE_MAX_M = 16
+
+
+@functools.lru_cache(maxsize=4096)
+def gemm_dgrad_covers(dtype, M, N, K, group_size, nbits) -> bool:
+    """what hqq_hip_gemm_dgrad serves (the library's own answer, nothing launched): axis-1 byte containers (8 / 4 / 2 bit), fp16 / bf16,
+    group_size % 16 == 0 dividing K, K % 64 == 0, N % (8 * per) == 0, M >= 1, sizes within 32-bit offsets"""
+    if dtype not in _DT or group_size is None or isinstance(nbits, float) or int(nbits) != nbits:
+        return False
+    return bool(_C.lib().hqq_hip_gemm_dgrad_covers(int(nbits), int(M), int(N), int(K), int(group_size), _DT[dtype]))
+
+
+def gemm_dgrad(g: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, N: int, K: int, group_size, nbits: int, out: Tensor | None = None) -> Tensor:
+    """dx = g @ dequantize(W_q, axis=1) for g [*, N] -> [*, K] (hqq_hip_gemm_dgrad): the weights are the bits of dequantize(), accumulation in fp32,
+    one rounding; deterministic, on the current stream, no workspace.  `out`: a contiguous buffer of rows x K elements in g's dtype.
+    Raises NotImplementedError outside gemm_dgrad_covers()."""
+    _dev(g, W_q, scale, zero)
+    if g.dtype != scale.dtype or zero.dtype != scale.dtype:
+        raise TypeError("hqq_amd: g / scale / zero must share the compute dtype")
+    if g.shape[-1] != N:
+        raise ValueError(f"hqq_amd: g has {g.shape[-1]} features, layer produces {N}")
+    if group_size is None:
+        raise NotImplementedError("hqq_amd: gemm_dgrad needs a group size")
+    gs = int(group_size)
+    if scale.numel() != (N * K) // gs or zero.numel() != (N * K) // gs:
+        raise ValueError(f"hqq_amd: gemm_dgrad needs {(N * K) // gs} scale / zero values (N * K / group_size), got {scale.numel()} / {zero.numel()}")
+    if W_q.dtype != torch.uint8 or W_q.numel() != (N // PER.get(nbits, 1)) * K:
+        raise NotImplementedError(f"hqq_amd: gemm_dgrad reads the byte container [N / per, K] of an axis-1 layer (nbits={nbits})")
+    g2 = g.reshape(-1, N)
+    if not g2.is_contiguous():
+        g2 = g2.contiguous()
+    M = g2.shape[0]
+    if out is None:
+        out = torch.empty((M, K), dtype=g.dtype, device=g.device)
+    elif out.numel() != M * K or out.dtype != g.dtype or not out.is_contiguous() or out.device != g.device:
+        raise ValueError(f"hqq_amd: gemm_dgrad writes a dense output of {M} x {K} elements in g's dtype")
+    with torch.cuda.device(g.device):
+        rc = _C.lib().hqq_hip_gemm_dgrad(int(nbits), _p(g2), _p(W_q.contiguous()), _p(scale.contiguous()), _p(zero.contiguous()), _p(out),
+                                         M, int(N), int(K), gs, _dt(g.dtype), _stream())
+    _C.check(rc, "hqq_hip_gemm_dgrad")
+    return out.reshape(*g.shape[:-1], K)
+
+
 def _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts, library_gemm: bool = False) -> Tensor:
     """axis-0 layers: decode sizes through hqq_hip_gemv_axis0; GEMV_MAX_M + 1 .. AXIS0_GEMM_ROUTE_MAX_M rows through hqq_hip_gemm_axis0 (unless
     library_gemm); everything else as HQQLinear has always run them — the HIP dequantise kernel (axis 0) + torch.matmul, then `out += bias`

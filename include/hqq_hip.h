@@ -379,6 +379,23 @@ int hqq_hip_gemm_axis0(int nbits, const void* x, const void* Wq, const void* sca
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The backward of HQQLinear with respect to its input for layers quantised along AXIS 1: dx[M,K] = g[M,N] . dequantize(Wq)[N,K] in one launch
+ * (csrc/gemm_dgrad.hip).  What it replaces is the backward of the reference's autograd functions (hqq/core/quantize.py:477-479, 534-553):
+ * Quantizer.dequantize writes the whole fp16 / bf16 weight (2 N K bytes), torch.matmul(grad, W) reads it back.
+ * g [M,N] and dx [M,K] dense, row-major, in `dtype`; Wq the byte container [N / per, K]; scale / zero N K / group_size elements of `dtype` (the axis-1
+ * layout of hqq_hip_dequantize).  Weights are the bits of hqq_hip_dequantize (two roundings in `dtype`); fp32 accumulation over n, one rounding; no bias
+ * (it has no part in dx).  Deterministic: an output tile belongs to one workgroup that walks all of N — no atomics, no workspace —, and a row's output
+ * bits depend on that row of g only, not on M or on the rows it travels with.
+ * Covers: nbits 8 / 4 / 2 (byte containers), HQQ_F16 / HQQ_BF16, group_size % 16 == 0, K % group_size == 0, K % 64 == 0, N % (8 per) == 0 (a lane contracts 8 packed rows), M >= 1,
+ * sizes within 32-bit offsets.  Anything else valid (3-bit, 1-bit, fp32, other shapes): HQQ_ERR_UNSUPPORTED ("not covered"), message in
+ * hqq_hip_last_error(); hqq_hip_gemm_dgrad_covers answers the same question (1 / 0) without launching.  g, Wq, dx 16-byte aligned.
+ * The two symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_gemm_dgrad_covers(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype);
+int hqq_hip_gemm_dgrad(int nbits, const void* g, const void* Wq, const void* scale, const void* zero, void* dx, int64_t M, int64_t N, int64_t K,
+                       int64_t group_size, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
