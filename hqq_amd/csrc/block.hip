@@ -8,6 +8,8 @@
 //   rope_cache    apply_rotary_pos_emb: (q * cos) + (rotate_half(q) * sin) with three roundings to T, k likewise, and the StaticCache
 //                 update (k_rot / v written at cache_position, read from device memory: graph-replay safe)
 //   silu_mul      LlamaMLP: act_fn(gate) * up — silu in fp32 (x / (1 + exp(-x))), rounded to T, then the product in T
+//   qknorm_rope_cache  Qwen3Attention: q_norm / k_norm (Qwen3RMSNorm per head: LlamaRMSNorm's roundings over head_dim elements), then rope_cache — the one
+//                 op by which Qwen3's decoder block differs from Llama's (opt-in, FusedLlamaStep(qk_norm=True))
 // T = fp16: native half arithmetic.  T = bf16: float arithmetic + one round-to-nearest-even per op, which is how torch evaluates bf16 elementwise ops.
 // And one that does NOT restate a kernel bit for bit (opt-in, FusedLlamaStep(attention="hip")):
 //   attn_decode   softmax(q K^T * scaling) V for ONE query per head over the static KV cache's first pos + 1 positions, fp32 scores / softmax /
@@ -152,6 +154,70 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(const uint16_t* __restr
     const uint16_t* vs = v + static_cast<int64_t>(kh) * hd;
     vd[i] = vs[i];
     vd[i + half] = vs[i + half];
+  }
+}
+
+// ---- per-head RMSNorm of q and k (Qwen3Attention's q_norm / k_norm), then rope_cache_kernel's rotary embedding and KV-cache write, one launch.
+//      One WAVE per (sequence, head), four waves per workgroup; blockIdx.y: the sequence.  Lane l holds the rotary pairs i = l + 64 j < HD / 2:
+//      elements i and i + HD / 2 of its head (HD = 64: lanes 32..63 hold nothing and add zeros).  The fp32 sum of squares is each lane's own
+//      elements in index order, then a butterfly of shuffles: a fixed order, the same bits on every call.  No LDS, no workspace.
+//      Qwen3RMSNorm's roundings (add_rmsnorm_kernel's): fp32 x * rsqrt(mean(x^2) + eps) -> T -> weight * (a product in T); rope_pair on those values ----
+template <int HD, bool BF>
+__global__ __launch_bounds__(256) void qknorm_rope_cache_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
+                                                                const uint16_t* __restrict__ q_weight, const uint16_t* __restrict__ k_weight, float q_eps, float k_eps,
+                                                                const uint16_t* __restrict__ cosv, const uint16_t* __restrict__ sinv, const int64_t* __restrict__ pos,
+                                                                uint16_t* __restrict__ q_out, uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
+                                                                int n_heads, int n_kv, int cache_len) {
+  using E = El<BF>;
+  constexpr int half = HD / 2, NP = (half + 63) / 64;
+  const int lane = threadIdx.x & 63;
+  const int head = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (head >= n_heads + n_kv) return;   // (a whole wave leaves: the shuffles below never miss a lane)
+  const int64_t row = blockIdx.y;
+  const bool is_k = head >= n_heads;
+  const int kh = head - n_heads;
+  const uint16_t* src = is_k ? k + (row * n_kv + kh) * HD : q + (row * n_heads + head) * HD;
+  const uint16_t* w = is_k ? k_weight : q_weight;
+  cosv += row * HD;
+  sinv += row * HD;
+  uint16_t x1[NP], x2[NP];
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const int i = lane + 64 * j;
+    const bool live = i < half;
+    x1[j] = live ? src[i] : static_cast<uint16_t>(0);
+    x2[j] = live ? src[i + half] : static_cast<uint16_t>(0);
+    const float f1 = E::f(x1[j]), f2 = E::f(x2[j]);
+    sum += f1 * f1;
+    sum += f2 * f2;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  const float r = rsqrtf(sum / static_cast<float>(HD) + (is_k ? k_eps : q_eps));
+  uint16_t* dst;
+  if (!is_k) {
+    dst = q_out + (row * n_heads + head) * HD;
+  } else {
+    const int64_t p = pos[row];
+    if (p < 0 || p >= cache_len) return;   // rope_cache_kernel's rule: a position outside the cache writes nothing
+    const int64_t slot = ((row * n_kv + kh) * cache_len + p) * HD;
+    dst = k_cache + slot;
+    const uint16_t* vs = v + (row * n_kv + kh) * HD;
+    uint16_t* vd = v_cache + slot;
+    for (int e = lane; e < HD; e += 64) vd[e] = vs[e];
+  }
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const int i = lane + 64 * j;
+    if (i < half) {
+      const uint16_t n1 = E::mul(w[i], E::r_prod(E::f(x1[j]), r));
+      const uint16_t n2 = E::mul(w[i + half], E::r_prod(E::f(x2[j]), r));
+      uint16_t o1, o2;
+      rope_pair<BF>(n1, n2, cosv[i], cosv[i + half], sinv[i], sinv[i + half], o1, o2);
+      dst[i] = o1;
+      dst[i + half] = o2;
+    }
   }
 }
 
@@ -542,6 +608,35 @@ int hqq_hip_rope_cache(const void* q, const void* k, const void* v, const void* 
 int hqq_hip_rope_cache_batched(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out,
                                void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
   return rope_cache_run("hqq_hip_rope_cache_batched", q, k, v, cos, sin, pos_dev, batch, q_out, k_cache, v_cache, n_heads, n_kv_heads, head_dim, cache_len, dtype, stream);
+}
+
+int hqq_hip_qknorm_rope_cache_batched(const void* q, const void* k, const void* v, const void* q_weight, const void* k_weight, float q_eps, float k_eps, const void* cos,
+                                      const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out, void* k_cache, void* v_cache, int64_t n_heads,
+                                      int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
+  const char* who = "hqq_hip_qknorm_rope_cache_batched";
+  clear_stale_error();
+  if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
+  if (!batch_ok(batch, who)) return HQQ_ERR_SHAPE;
+  if (!q || !k || !v || !q_weight || !k_weight || !cos || !sin || !pos_dev || !q_out || !k_cache || !v_cache || n_heads < 1 || n_kv_heads < 1 || head_dim < 2 ||
+      head_dim % 2 || cache_len < 1 || !(q_eps >= 0.f) || !(k_eps >= 0.f) || n_heads > INT32_MAX || n_kv_heads > INT32_MAX || head_dim > INT32_MAX ||
+      (n_heads + n_kv_heads) * head_dim > INT32_MAX || cache_len > INT32_MAX) {
+    set_error("%s: bad arguments (head_dim even, eps >= 0)", who);
+    return HQQ_ERR_SHAPE;
+  }
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256) { set_error("%s: head_dim %lld not covered (64 / 128 / 256)", who, (long long)head_dim); return HQQ_ERR_UNSUPPORTED; }
+  // (2-byte loads and stores, a wave's lanes on consecutive elements: no alignment beyond the element's is asked for)
+  const dim3 grid(static_cast<unsigned>((n_heads + n_kv_heads + 3) / 4), static_cast<unsigned>(batch));
+#define HQQ_QKN_GO(HDV, BFV)                                                                                                                     \
+  hipLaunchKernelGGL((qknorm_rope_cache_kernel<HDV, BFV>), grid, dim3(256), 0, as_stream(stream), static_cast<cu16>(q), static_cast<cu16>(k), static_cast<cu16>(v), \
+                     static_cast<cu16>(q_weight), static_cast<cu16>(k_weight), q_eps, k_eps, static_cast<cu16>(cos), static_cast<cu16>(sin), pos_dev,    \
+                     static_cast<u16>(q_out), static_cast<u16>(k_cache), static_cast<u16>(v_cache), static_cast<int>(n_heads), static_cast<int>(n_kv_heads), \
+                     static_cast<int>(cache_len))
+  const bool bf = dtype == HQQ_BF16;
+  if (head_dim == 64) { if (bf) HQQ_QKN_GO(64, true); else HQQ_QKN_GO(64, false); }
+  else if (head_dim == 128) { if (bf) HQQ_QKN_GO(128, true); else HQQ_QKN_GO(128, false); }
+  else { if (bf) HQQ_QKN_GO(256, true); else HQQ_QKN_GO(256, false); }
+#undef HQQ_QKN_GO
+  return check_launch(who);
 }
 
 int hqq_hip_silu_mul(const void* gate, const void* up, void* out, int64_t n, int dtype, void* stream) {

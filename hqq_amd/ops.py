@@ -1051,6 +1051,36 @@ def rope_cache(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: T
     return rope_cache_batched(q, k, v, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), q_out)
 
 
+def qknorm_rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, q_weight: Tensor, k_weight: Tensor, q_eps: float, k_eps: float, cos: Tensor, sin: Tensor, pos: Tensor,
+                              k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
+    """rope_cache_batched with Qwen3Attention's per-head RMSNorms in front of the rotary embedding, one launch (hqq_hip_qknorm_rope_cache_batched): every head of
+    q is normalised with q_weight [hd] / q_eps, every head of k with k_weight [hd] / k_eps (Qwen3RMSNorm's roundings), then rotated; q_out, the caches, v and
+    the positions as in rope_cache_batched.  head_dim 64 / 128 / 256, fp16 / bf16."""
+    _dev(q, k, v, q_weight, k_weight, cos, sin, pos, k_cache, v_cache, q_out)
+    B = _batch_of(pos, "qknorm_rope_cache_batched")
+    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError("hqq_amd: qknorm_rope_cache_batched takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
+    hd = k_cache.shape[-1]
+    if cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
+            k.numel() != B * k_cache.shape[1] * hd or v.numel() != k.numel() or q_out.numel() != q.numel():
+        raise ValueError("hqq_amd: qknorm_rope_cache_batched takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd]")
+    if any(w.numel() != hd or not w.is_contiguous() for w in (q_weight, k_weight)) or \
+            any(t.dtype != q.dtype for t in (k, v, q_weight, k_weight, cos, sin, k_cache, v_cache, q_out)):
+        raise ValueError("hqq_amd: qknorm_rope_cache_batched takes dense norm weights of head_dim elements, and every tensor but the positions in q's dtype")
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_qknorm_rope_cache_batched(_p(q), _p(k), _p(v), _p(q_weight), _p(k_weight), float(q_eps), float(k_eps), _p(cos), _p(sin), _p(pos), B,
+                                                        _p(q_out), _p(k_cache), _p(v_cache), q.numel() // (B * hd), k_cache.shape[1], hd, k_cache.shape[2],
+                                                        _dt(q.dtype), _stream())
+    _C.check(rc, "hqq_hip_qknorm_rope_cache_batched")
+    return q_out
+
+
+def qknorm_rope_cache(q: Tensor, k: Tensor, v: Tensor, q_weight: Tensor, k_weight: Tensor, q_eps: float, k_eps: float, cos: Tensor, sin: Tensor, pos: Tensor,
+                      k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
+    """qknorm_rope_cache_batched for one sequence: cos / sin [hd], the static caches [n_kv_heads, cache_len, head_dim], position pos[0] (device int64)"""
+    return qknorm_rope_cache_batched(q, k, v, q_weight, k_weight, q_eps, k_eps, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), q_out)
+
+
 def _attn_batched_args(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, who: str):
     B = _batch_of(pos, who)
     if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():

@@ -60,20 +60,27 @@ class GraphedGreedyDecoder:
     axis0: what a model quantised along AXIS 0 decodes through.  "model" (default): the model's own forward, as before.  "fused" (opt-in): where
     llama_fused.supports_axis0 accepts the model, the fused step with q|k|v and gate|up (+ SiLU * up) as one grouped axis-0 launch each
     (`fused_axis0`; `fused` stays the axis-1 flag), and generate_batch's batched step where supports_axis0_batch accepts the batch.
+    qk_norm: what a Qwen3 model (per-head q_norm / k_norm in front of the rotary embedding) decodes through.  "model" (default): the model's own forward, as
+    before.  "fused" (opt-in): where llama_fused.supports_qk_norm accepts the model, the fused step with ops.qknorm_rope_cache_batched in rope_cache's place
+    (`fused_qk_norm`; `fused` stays the Llama flag), and generate_batch's batched step where supports_qk_norm_batch accepts the batch.
     generate() and generate_batch() prefill differently and keep different caches, but advance through the same routine (_advance) over a small state
     holder: the device tensors tok / next_tok / pos that the captured graphs read and write, the step (None: the model's own forward), the dictionary
     its graphs are kept in with the key of an attended length in it, and the rule for that length."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
-                 do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model"):
+                 do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model"):
         from transformers import StaticCache
         from . import llama_fused
         if axis0 not in ("model", "fused"):
             raise ValueError("axis0: 'model' or 'fused'")
+        if qk_norm not in ("model", "fused"):
+            raise ValueError("qk_norm: 'model' or 'fused'")
         self.model = model.eval()
         self.fused = bool(fused) and llama_fused.supports(model)
         self.axis0 = axis0
         self.fused_axis0 = bool(fused) and axis0 == "fused" and not self.fused and llama_fused.supports_axis0(model)
+        self.qk_norm = qk_norm
+        self.fused_qk_norm = bool(fused) and qk_norm == "fused" and not self.fused and not self.fused_axis0 and llama_fused.supports_qk_norm(model)
         self._fused_mod = llama_fused
         self.attention = attention   # "sdpa": HF's attention function (token-identical to model(...)); "hip": the decode-attention kernel (faster, within rounding)
         self.glue = glue             # "auto" / "folded": RMSNorm, residual adds and SiLU * up inside the GEMV launches (csrc/gemv_block.hip); "kernels": round 4's separate glue kernels
@@ -184,10 +191,10 @@ class GraphedGreedyDecoder:
             st["pos"].fill_(T)
         else:
             self.step = None
-            if self.fused or self.fused_axis0:
+            if self.fused or self.fused_axis0 or self.fused_qk_norm:
                 try:
                     self.step = self._fused_mod.FusedLlamaStep(self.model, self.cache, self.max_cache_len, attention=self.attention,
-                                                               glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0)
+                                                               glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0, qk_norm=self.fused_qk_norm)
                 except ValueError:   # a cache layout / attention configuration the fused step does not restate: the model's own forward serves
                     self.step = None
             self.graphs = {}
@@ -213,6 +220,20 @@ class GraphedGreedyDecoder:
             self.step.account_tokens(len(toks) - 1)
         return torch.cat([ids] + toks[:n], dim=1)
 
+    def _snapshot(self, st):
+        """what one _decode_once changes besides the cache slot it writes (and re-writes when repeated): the token and the positions — and, on the model's own
+        forward, each StaticLayer's cumulative_length, the device counter StaticLayer.update takes its slot from and advances itself (a fused step never calls
+        update: account_tokens keeps that counter, outside the captured step)"""
+        lens = [] if st["step"] is not None or self.cache is None else \
+            [lay.cumulative_length for lay in self.cache.layers if isinstance(getattr(lay, "cumulative_length", None), Tensor)]
+        return st["tok"].clone(), st["pos"].clone(), [(t, t.clone()) for t in lens]
+
+    @staticmethod
+    def _restore(st, snap) -> None:
+        st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
+        for t, was in snap[2]:
+            t.copy_(was)
+
     @torch.no_grad()
     def _advance(self, st, p: int, use_graph: bool) -> None:
         """one decode step of the state holder st at position p (the host's copy of its LARGEST row position): replay the graph of p's cache bucket, capturing it first if need be"""
@@ -223,9 +244,9 @@ class GraphedGreedyDecoder:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                snap = (st["tok"].clone(), st["pos"].clone())
+                snap = self._snapshot(st)
                 self._decode_once(st, kv)                # warm-up on the side stream (writes cache slot pos, re-written below)
-                st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
+                self._restore(st, snap)
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
@@ -246,9 +267,9 @@ class GraphedGreedyDecoder:
             p += 1
         for q in range(p, p + new_tokens):                    # buckets the timed steps will enter: captured before the clock starts
             if st["key"](st["kv_len"](q)) not in st["graphs"]:
-                snap = (st["tok"].clone(), st["pos"].clone())
+                snap = self._snapshot(st)
                 self._advance(st, q, True)
-                st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
+                self._restore(st, snap)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -332,7 +353,8 @@ class GraphedGreedyDecoder:
     def _batch_state(self, B: int):
         """the kept state holder of generate_batch at B rows, or None when the batched step does not serve the model there"""
         fm = self._fused_mod
-        if not ((self.fused and fm.supports_batch(self.model, B)) or (self.fused_axis0 and fm.supports_axis0_batch(self.model, B))):
+        if not ((self.fused and fm.supports_batch(self.model, B)) or (self.fused_axis0 and fm.supports_axis0_batch(self.model, B)) or
+                (self.fused_qk_norm and fm.supports_qk_norm_batch(self.model, B))):
             return None
         cfg = self.model.config
         n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
@@ -340,7 +362,7 @@ class GraphedGreedyDecoder:
         cache = self._StaticCache(config=cfg, max_cache_len=self.max_cache_len)
         cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
         try:   # (without the decoder's `glue`: the batched step has the one-launch front and back wherever they apply)
-            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0)
+            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0, qk_norm=self.fused_qk_norm)
         except ValueError:
             return None
         st = {"B": B, "cache": cache, "scratch": self._StaticCache(config=cfg, max_cache_len=self.max_cache_len), "step": step,
@@ -386,11 +408,13 @@ class HFGenerator:
     a prompt that leaves less than max_new_tokens of cache generates what fits."""
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
-                 compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model"):
+                 compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         if axis0 not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts an axis-0 model into the fused decode step)
             raise ValueError("axis0: 'model' or 'fused'")
+        if qk_norm not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts a Qwen3 model into the fused decode step)
+            raise ValueError("qk_norm: 'model' or 'fused'")
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -402,7 +426,7 @@ class HFGenerator:
         self.is_compiled = compile is not None
         self.use_graph = compile is not None
         self.compile_options = compile_options
-        self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0)
+        self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm)
         self.init()
 
     @staticmethod

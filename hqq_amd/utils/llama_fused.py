@@ -21,6 +21,12 @@ Models quantised along AXIS 0 (supports_axis0; opt-in through GraphedGreedyDecod
     SiLU * up in its reduce) -> down (ops.gemv_axis0)
 = 11 launches + the attention's (10 with attention="hip"), on the layers' own tensors.
 
+Qwen3 models (supports_qk_norm; opt-in through GraphedGreedyDecoder(qk_norm="fused")) differ from Llama's block in ONE op: Qwen3Attention normalises every
+head of q and k (q_norm / k_norm, an RMSNorm over head_dim) before the rotary embedding.  ops.qknorm_rope_cache_batched (csrc/block.hip) takes rope_cache's place:
+    add_rmsnorm -> q|k|v -> qknorm_rope_cache -> attention -> ...   (glue="kernels", and every batch > 1), otherwise unchanged; folded glue: q|k|v with the
+    RMSNorm in its prologue -> qknorm_rope_cache -> attention -> o / gate|up pair / down folded as above
+= 5 launches + the attention's.  The rotary-paired q / k copies are not built: the head norm must see a whole head before the rotation.
+
 Only what the step needs is taken from the model: module weights and the HF StaticCache's tensors are used in place (nothing is copied).
 """
 from __future__ import annotations
@@ -38,8 +44,10 @@ def _hip(layer):
 
 def arch_supported(model) -> bool:
     """The allow-list half of supports(): the step restates LlamaDecoderLayer's arithmetic (transformers models/llama, models/mistral) and nothing
-    else.  Models that merely LOOK like it (same attribute names) would decode wrong tokens without an error: Qwen3 (per-head q_norm / k_norm),
-    Granite (residual / embedding / logits / attention multipliers), Gemma (soft-capping, (1 + w) norms), Cohere, OLMo ..."""
+    else.  Models that merely LOOK like it (same attribute names) would decode wrong tokens through that sequence without an error: Granite (residual /
+    embedding / logits / attention multipliers), Gemma (soft-capping, (1 + w) norms), Cohere, OLMo ...  Qwen3 (per-head q_norm / k_norm in front of the
+    rotary embedding) is refused HERE too — this predicate and the defaults built on it stay Llama's — and is served by a predicate of its own,
+    qk_norm_arch_supported, whose step (FusedLlamaStep(qk_norm=True)) has a kernel for that op; nothing takes it without being asked."""
     try:
         cfg = model.config
         if getattr(cfg, "model_type", None) not in ("llama", "mistral"):
@@ -62,18 +70,57 @@ def arch_supported(model) -> bool:
         return False
 
 
+def _common_arch(cfg) -> bool:
+    """what both architecture predicates ask of a config: no biases, no soft-capping, no Granite-style multipliers"""
+    if getattr(cfg, "attn_logit_softcapping", None) or getattr(cfg, "final_logit_softcapping", None):
+        return False
+    if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False):
+        return False
+    return all(getattr(cfg, odd, None) in (None, 1, 1.0) for odd in ("residual_multiplier", "embedding_multiplier", "logits_scaling", "attention_multiplier"))
+
+
+def qk_norm_arch_supported(model) -> bool:
+    """arch_supported's counterpart for the step with qk_norm=True, which restates Qwen3DecoderLayer (transformers models/qwen3): Llama's block with
+    Qwen3Attention's q_norm / k_norm — an RMSNorm over head_dim on every head of q and k, before the rotary embedding.  model_type "qwen3" (not
+    qwen3_moe), no biases, full attention in every layer (no sliding window), SiLU, and on every block a q_norm and a k_norm with a 1-D weight of head_dim
+    elements in the compute dtype and a variance_epsilon."""
+    try:
+        cfg = model.config
+        if getattr(cfg, "model_type", None) != "qwen3" or not _common_arch(cfg):
+            return False
+        if getattr(cfg, "sliding_window", None) or getattr(cfg, "use_sliding_window", False):
+            return False
+        if any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
+            return False
+        hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+        dt = model.model.norm.weight.dtype
+        for blk in model.model.layers:
+            at = blk.self_attn
+            if any(hasattr(at, n) for n in ("qk_norm", "sinks")) or getattr(at, "sliding_window", None):
+                return False
+            for nrm in (at.q_norm, at.k_norm):
+                if nrm.weight.dim() != 1 or nrm.weight.shape[0] != hd or nrm.weight.dtype != dt or not isinstance(nrm.variance_epsilon, (int, float)):
+                    return False
+            if type(getattr(blk.mlp, "act_fn", None)).__name__ not in ("SiLUActivation", "SiLU"):
+                return False
+        return True
+    except AttributeError:
+        return False
+
+
 def _decoder_linears(model):
     """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers"""
     return [[_hip(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
             for b in model.model.layers]
 
 
-def _structure(model, axis: int):
-    """The structural half of supports() and supports_axis0*(): an allow-listed architecture (arch_supported), fp16 or bf16, the rotary / embedding /
+def _structure(model, axis: int, arch=arch_supported):
+    """The structural half of supports(), supports_axis0*() and supports_qk_norm*(): an allow-listed architecture (`arch`: arch_supported, or
+    qk_norm_arch_supported for the step with qk_norm=True), fp16 or bf16, the rotary / embedding /
     lm_head modules the step calls, every decoder linear an HQQLinearHIP of the compute dtype without bias, quantised along `axis`, on the GPU, and
     RMSNorm weights of that dtype with a multiple of 8 features.  Returns (dtype, _decoder_linears(model)), or None where the model is not of that shape;
     which kernels cover the layers is the callers' question."""
-    if not arch_supported(model):
+    if not arch(model):
         return None
     try:
         inner = model.model
@@ -98,7 +145,12 @@ def supports(model) -> bool:
     """a LlamaForCausalLM-shaped model of an allow-listed architecture (arch_supported) — model.model.layers[*].self_attn.{q,k,v,o}_proj,
     .mlp.{gate,up,down}_proj, RMSNorm without bias —, fp16 or bf16, every decoder linear an HQQLinearHIP without bias, quantised along axis 1 (the folded
     block kernels read axis-1 meta), whose group can share one launch"""
-    found = _structure(model, 1)
+    return _supports(model, arch_supported)
+
+
+def _supports(model, arch) -> bool:
+    """supports() / supports_qk_norm(): _structure along axis 1 under the architecture predicate `arch`, and the kernel coverage of the grouped launches"""
+    found = _structure(model, 1, arch)
     if found is None:
         return False
     dt, blocks = found
@@ -155,8 +207,24 @@ def batch_covers(dtype, B: int, layers, opts: int = 0) -> bool:
 
 def supports_batch(model, B: int) -> bool:
     """supports(model), and every decoder linear served by a fused decode kernel at B rows (batch_covers, with this module's default option bits)"""
-    if not supports(model):
+    return supports(model) and _batch_served(model, B)
+
+
+def supports_qk_norm(model) -> bool:
+    """supports() for a Qwen3 model (qk_norm_arch_supported in arch_supported's place: the same structural and kernel-coverage checks), whose head_dim
+    ops.qknorm_rope_cache_batched serves (64 / 128 / 256).  What FusedLlamaStep(qk_norm=True) takes; nothing takes it by default."""
+    if not _supports(model, qk_norm_arch_supported):
         return False
+    cfg = model.config
+    return (getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads) in (64, 128, 256)
+
+
+def supports_qk_norm_batch(model, B: int) -> bool:
+    """supports_batch() for a Qwen3 model: supports_qk_norm(model), and every decoder linear served by a fused decode kernel at B rows"""
+    return supports_qk_norm(model) and _batch_served(model, B)
+
+
+def _batch_served(model, B: int) -> bool:
     specs = [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lins in _decoder_linears(model) for L in lins]
     return batch_covers(model.model.norm.weight.dtype, B, specs, ops._default_opts)
 
@@ -171,7 +239,8 @@ class FusedLlamaStep:
     that a prefill has filled (layer.keys / .values [batch, n_kv, max_cache_len, hd], used in place).  Each sequence has its own position; row b of
     every glue kernel gives the bits of the batch-1 kernel for sequence b alone, and the linears run at M = batch."""
 
-    def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1):
+    def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
+                 qk_norm: bool = False):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -179,7 +248,10 @@ class FusedLlamaStep:
         paired gate|up layer (csrc/gemv_block.hip: 4 launches + rotary / attention per block; costs a second copy of gate / up's packed levels in the
         paired layout); "kernels" — round 4's separate glue kernels (9 launches per block); "auto": folded where hqq_hip_gemv_block covers the model.
         batch: the number of sequences.  Beyond 1 the model must be one supports_batch (supports_axis0_batch with axis0) accepts at that many rows;
-        the folded launches serve one activation row, so a batch takes the separate glue kernels whatever `glue` allows."""
+        the folded launches serve one activation row, so a batch takes the separate glue kernels whatever `glue` allows.
+        qk_norm: the model is a Qwen3 (supports_qk_norm; supports_qk_norm_batch beyond one sequence): ops.qknorm_rope_cache_batched — the per-head q_norm /
+        k_norm, then the rotary embedding and the cache write — takes rope_cache's place after q|k|v, and attention="hip" attends on its rotated q_out
+        (ops.attn_decode_batched).  The folded glue keeps q|k|v in the natural row order (the norm comes before the rotation): 5 launches + attention."""
         # axis0: the model's linears are quantised along axis 0 (supports_axis0).  The step is the glue="kernels" sequence with q|k|v and gate|up through
         # ops.gemv_axis0_grouped (gate|up's reduce applies SiLU * up: no silu_mul launch) and o / down through ops.gemv_axis0, on the layers' own tensors
         # (nothing re-laid out); the folded launches read axis-1 meta and are never taken.
@@ -207,8 +279,14 @@ class FusedLlamaStep:
         if glue not in ("auto", "folded", "kernels"):
             raise ValueError("glue: 'auto', 'folded' or 'kernels'")
         self.axis0 = bool(axis0)
+        self.qk_norm = bool(qk_norm)
+        if self.qk_norm and self.axis0:
+            raise ValueError("hqq_amd: qk_norm=True serves models quantised along axis 1 (an axis-0 Qwen3 decodes through the model's own forward)")
+        if self.qk_norm and not (supports_qk_norm(model) if B == 1 else supports_qk_norm_batch(model, B)):
+            raise ValueError(f"hqq_amd: qk_norm=True needs a Qwen3 model whose decoder linears the fused decode kernels serve at {B} rows "
+                             "(supports_qk_norm / supports_qk_norm_batch)")
         # (a single sequence of an axis-1 model is not asked: its callers ask supports(), and models construct here that it refuses)
-        if (B != 1 or self.axis0) and not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
+        if (B != 1 or self.axis0) and not self.qk_norm and not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
             raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows "
                              f"({'axis0=True: supports_axis0_batch' if self.axis0 else 'supports_batch'})")
         if self.axis0 and glue == "folded":
@@ -253,7 +331,7 @@ class FusedLlamaStep:
                 "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
                 "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
             })
-            if self.folded and attention != "hip" and self.hd % 2 == 0:
+            if self.folded and attention != "hip" and self.hd % 2 == 0 and not self.qk_norm:
                 # q and k in the rotary-paired row order (ops.rotary_pair_layout): the q|k|v launch's epilogue applies the rotary embedding and writes the cache
                 # (the kernel attention folds the rotary embedding into the attention launch instead: it keeps the natural order)
                 def _sub_ok(t, L_):
@@ -343,7 +421,15 @@ class FusedLlamaStep:
             else:
                 ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
                 self._grouped(b, "qkv", [b["q"], b["k"], b["v"]])
-            if self.attention == "hip":   # rotary + cache write + attention: one launch
+            if self.qk_norm:   # Qwen3: the heads of q and k normalised, rotated and cached in one launch; either attention then reads the rotated q_out
+                qn, kn = at.q_norm, at.k_norm
+                ops.qknorm_rope_cache_batched(b["q"], b["k"], b["v"], qn.weight, kn.weight, qn.variance_epsilon, kn.variance_epsilon, cos, sin, pos,
+                                              b["kc"], b["vc"], b["qr"])
+                if self.attention == "hip":
+                    att = ops.attn_decode_batched(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
+                else:
+                    att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :, :kvl], b["vc"][:, :, :kvl], mask, dropout=0.0, scaling=at.scaling)
+            elif self.attention == "hip":   # rotary + cache write + attention: one launch
                 att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
                                                    workspace=self.attn_ws.get(splits))
             else:
@@ -395,5 +481,5 @@ class FusedLlamaBatchStep(FusedLlamaStep):
     """FusedLlamaStep under the name and positional signature the batched callers construct it by: no `glue` argument ("auto": the one-launch front
     wherever the tables exist)"""
 
-    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False):
-        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch)
+    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False):
+        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm)

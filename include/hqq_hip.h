@@ -205,6 +205,18 @@ int hqq_hip_silu_mul(const void* gate, const void* up, void* out, int64_t n, int
  * int64[batch]; sequence b's key / value go to its own cache row at pos_dev[b]; a position outside [0, cache_len) writes nothing, as in the batch-1 call. */
 int hqq_hip_rope_cache_batched(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out,
                                void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream);
+/* hqq_hip_rope_cache_batched with a per-head RMSNorm of q and k in front of the rotary embedding: what Qwen3Attention.forward does between its
+ * projections and the cache update (transformers models/qwen3/modeling_qwen3.py: query_states = q_norm(q_proj(x).view(..., head_dim)), key_states =
+ * k_norm(...), then apply_rotary_pos_emb and past_key_values.update).  Qwen3RMSNorm.forward's roundings, per head of head_dim elements:
+ * n = weight * T(float(x) * rsqrt(mean(x^2) + eps)), the product in T — q_weight / k_weight [head_dim] in T, q_eps / k_eps the two modules' own
+ * variance_epsilon (>= 0) —; hqq_hip_rope_cache's arithmetic on n; v is copied unchanged.  Shapes, positions and the rule for a position outside
+ * [0, cache_len) (nothing is written to the caches, q_out still is) as hqq_hip_rope_cache_batched.  The fp32 sum of squares is taken in a fixed order:
+ * two calls on the same inputs give the same bits.  head_dim 64 / 128 / 256 (other even values: HQQ_ERR_UNSUPPORTED; odd: HQQ_ERR_SHAPE), fp16 / bf16
+ * (other dtypes: HQQ_ERR_UNSUPPORTED); element-aligned pointers suffice.  Every check is made before anything is launched.
+ * The symbol was added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits. */
+int hqq_hip_qknorm_rope_cache_batched(const void* q, const void* k, const void* v, const void* q_weight, const void* k_weight, float q_eps, float k_eps, const void* cos,
+                                      const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out, void* k_cache, void* v_cache, int64_t n_heads,
+                                      int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream);
 /* The per-token work either side of the decoder blocks (ABI 7; hqq/utils/generation_hf.py:405-540: embedding lookup, the rotary table's row, the causal mask of one query in
  * front; argmax, token hand-over, position increment behind) as ONE launch each — copies and compares only, bit-identical to the torch ops they replace:
  *   hqq_hip_token_prologue  h[H] = embed[*tok_dev]; cos / sin [head_dim] = cos_tab / sin_tab [L, head_dim] row *pos_dev (tables NULL: skipped);
