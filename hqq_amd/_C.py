@@ -40,6 +40,8 @@ SYMBOLS = {
     "hqq_hip_rope_cache_batched": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
     # Qwen3's per-head q_norm / k_norm in front of rope_cache_batched (added at ABI 9 without a bump: nothing that existed changed)
     "hqq_hip_qknorm_rope_cache_batched": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
+    # Qwen2's q / k / v biases in front of rope_cache_batched (added at ABI 9 without a bump: nothing that existed changed)
+    "hqq_hip_bias_rope_cache_batched": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
     "hqq_hip_token_prologue_batched": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
     "hqq_hip_argmax_advance_batched": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
     "hqq_hip_attn_decode_batched": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),

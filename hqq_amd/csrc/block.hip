@@ -10,6 +10,8 @@
 //   silu_mul      LlamaMLP: act_fn(gate) * up — silu in fp32 (x / (1 + exp(-x))), rounded to T, then the product in T
 //   qknorm_rope_cache  Qwen3Attention: q_norm / k_norm (Qwen3RMSNorm per head: LlamaRMSNorm's roundings over head_dim elements), then rope_cache — the one
 //                 op by which Qwen3's decoder block differs from Llama's (opt-in, FusedLlamaStep(qk_norm=True))
+//   bias_rope_cache  Qwen2Attention: q_proj / k_proj / v_proj carry a bias — `out += bias` on the rounded matmul result, one rounding in T —, then rope_cache:
+//                 the one op by which Qwen2's decoder block differs from Llama's (opt-in, FusedLlamaStep(qkv_bias=True); the q|k|v launch stays bias-free)
 // T = fp16: native half arithmetic.  T = bf16: float arithmetic + one round-to-nearest-even per op, which is how torch evaluates bf16 elementwise ops.
 // And one that does NOT restate a kernel bit for bit (opt-in, FusedLlamaStep(attention="hip")):
 //   attn_decode   softmax(q K^T * scaling) V for ONE query per head over the static KV cache's first pos + 1 positions, fp32 scores / softmax /
@@ -154,6 +156,55 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(const uint16_t* __restr
     const uint16_t* vs = v + static_cast<int64_t>(kh) * hd;
     vd[i] = vs[i];
     vd[i + half] = vs[i + half];
+  }
+}
+
+// ---- rope_cache_kernel with the three projection biases added in front (Qwen2Attention: q_proj / k_proj / v_proj have a bias, shared by every sequence):
+//      q' = q + q_bias, k' = k + k_bias, v' = v + v_bias, each ONE rounding to T — the decode kernels' `out += bias` on the rounded matmul result
+//      (gemv_kernel.inc, skinny.hip) —, then rope_pair on q' / k' and the cache write of k' / v'.  rope_cache_kernel's geometry: one thread per
+//      (head, i < hd / 2), blockIdx.y the sequence; no LDS, no workspace ----
+template <bool BF>
+__global__ __launch_bounds__(256) void bias_rope_cache_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
+                                                              const uint16_t* __restrict__ q_bias, const uint16_t* __restrict__ k_bias, const uint16_t* __restrict__ v_bias,
+                                                              const uint16_t* __restrict__ cosv, const uint16_t* __restrict__ sinv, const int64_t* __restrict__ pos,
+                                                              uint16_t* __restrict__ q_out, uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
+                                                              int n_heads, int n_kv, int hd, int cache_len) {
+  using E = El<BF>;
+  const int half = hd / 2;
+  const int id = blockIdx.x * blockDim.x + threadIdx.x;
+  const int total = (n_heads + n_kv) * half;
+  if (id >= total) return;
+  const int64_t row = blockIdx.y;
+  q += row * n_heads * hd;
+  q_out += row * n_heads * hd;
+  k += row * n_kv * hd;
+  v += row * n_kv * hd;
+  cosv += row * hd;
+  sinv += row * hd;
+  pos += row;
+  k_cache += row * n_kv * cache_len * hd;
+  v_cache += row * n_kv * cache_len * hd;
+  const int head = id / half, i = id - head * half;
+  const bool is_k = head >= n_heads;
+  const int64_t off = static_cast<int64_t>(is_k ? head - n_heads : head) * hd;   // the head's first element in a row of q (k / v): the bias index too
+  const uint16_t* src = (is_k ? k : q) + off;
+  const uint16_t* bias = (is_k ? k_bias : q_bias) + off;
+  const uint16_t x1 = E::add(src[i], bias[i]), x2 = E::add(src[i + half], bias[i + half]);
+  uint16_t o1, o2;
+  rope_pair<BF>(x1, x2, cosv[i], cosv[i + half], sinv[i], sinv[i + half], o1, o2);
+  if (!is_k) {
+    q_out[off + i] = o1;
+    q_out[off + i + half] = o2;
+  } else {
+    const int64_t p = pos[0];
+    if (p < 0 || p >= cache_len) return;   // rope_cache_kernel's rule: a position outside the cache writes nothing
+    const int kh = head - n_heads;
+    uint16_t* kd = k_cache + (static_cast<int64_t>(kh) * cache_len + p) * hd;
+    uint16_t* vd = v_cache + (static_cast<int64_t>(kh) * cache_len + p) * hd;
+    kd[i] = o1;
+    kd[i + half] = o2;
+    vd[i] = E::add(v[off + i], v_bias[off + i]);
+    vd[i + half] = E::add(v[off + i + half], v_bias[off + i + half]);
   }
 }
 
@@ -636,6 +687,31 @@ int hqq_hip_qknorm_rope_cache_batched(const void* q, const void* k, const void* 
   else if (head_dim == 128) { if (bf) HQQ_QKN_GO(128, true); else HQQ_QKN_GO(128, false); }
   else { if (bf) HQQ_QKN_GO(256, true); else HQQ_QKN_GO(256, false); }
 #undef HQQ_QKN_GO
+  return check_launch(who);
+}
+
+int hqq_hip_bias_rope_cache_batched(const void* q, const void* k, const void* v, const void* q_bias, const void* k_bias, const void* v_bias, const void* cos,
+                                    const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out, void* k_cache, void* v_cache, int64_t n_heads,
+                                    int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
+  const char* who = "hqq_hip_bias_rope_cache_batched";
+  clear_stale_error();
+  if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
+  if (!batch_ok(batch, who)) return HQQ_ERR_SHAPE;
+  if (!q || !k || !v || !q_bias || !k_bias || !v_bias || !cos || !sin || !pos_dev || !q_out || !k_cache || !v_cache || n_heads < 1 || n_kv_heads < 1 || head_dim < 2 ||
+      head_dim % 2 || cache_len < 1 || n_heads > INT32_MAX || n_kv_heads > INT32_MAX || head_dim > INT32_MAX || (n_heads + n_kv_heads) * head_dim > INT32_MAX ||
+      cache_len > INT32_MAX) {
+    set_error("%s: bad arguments (all three biases are required, head_dim even)", who);
+    return HQQ_ERR_SHAPE;
+  }
+  const int64_t total = (n_heads + n_kv_heads) * (head_dim / 2);
+#define HQQ_BROPE_GO(BFV)                                                                                                                         \
+  hipLaunchKernelGGL(bias_rope_cache_kernel<BFV>, dim3(static_cast<unsigned>((total + 255) / 256), static_cast<unsigned>(batch)), dim3(256), 0, as_stream(stream), \
+                     static_cast<cu16>(q), static_cast<cu16>(k), static_cast<cu16>(v), static_cast<cu16>(q_bias), static_cast<cu16>(k_bias),          \
+                     static_cast<cu16>(v_bias), static_cast<cu16>(cos), static_cast<cu16>(sin), pos_dev, static_cast<u16>(q_out), static_cast<u16>(k_cache), \
+                     static_cast<u16>(v_cache), static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(head_dim), static_cast<int>(cache_len))
+  if (dtype == HQQ_BF16) HQQ_BROPE_GO(true);
+  else HQQ_BROPE_GO(false);
+#undef HQQ_BROPE_GO
   return check_launch(who);
 }
 

@@ -1081,6 +1081,36 @@ def qknorm_rope_cache(q: Tensor, k: Tensor, v: Tensor, q_weight: Tensor, k_weigh
     return qknorm_rope_cache_batched(q, k, v, q_weight, k_weight, q_eps, k_eps, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), q_out)
 
 
+def bias_rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, q_bias: Tensor, k_bias: Tensor, v_bias: Tensor, cos: Tensor, sin: Tensor, pos: Tensor,
+                            k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
+    """rope_cache_batched with Qwen2Attention's projection biases added in front of the rotary embedding, one launch (hqq_hip_bias_rope_cache_batched):
+    q + q_bias, k + k_bias, v + v_bias — one rounding each in q's dtype, the `out += bias` of the linears; the biases [n_heads * hd] / [n_kv_heads * hd],
+    shared by every sequence —, then q and k rotated; q_out, the caches and the positions as in rope_cache_batched.  Bit for bit gemv_grouped with the biases
+    followed by rope_cache_batched.  Any even head_dim, fp16 / bf16."""
+    _dev(q, k, v, q_bias, k_bias, v_bias, cos, sin, pos, k_cache, v_cache, q_out)
+    B = _batch_of(pos, "bias_rope_cache_batched")
+    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError("hqq_amd: bias_rope_cache_batched takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
+    hd = k_cache.shape[-1]
+    if cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
+            k.numel() != B * k_cache.shape[1] * hd or v.numel() != k.numel() or q_out.numel() != q.numel():
+        raise ValueError("hqq_amd: bias_rope_cache_batched takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd]")
+    if any(bias.numel() * B != t.numel() or not bias.is_contiguous() for bias, t in ((q_bias, q), (k_bias, k), (v_bias, v))) or \
+            any(t.dtype != q.dtype for t in (k, v, q_bias, k_bias, v_bias, cos, sin, k_cache, v_cache, q_out)):
+        raise ValueError("hqq_amd: bias_rope_cache_batched takes dense biases of one row of q / k / v each, and every tensor but the positions in q's dtype")
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_bias_rope_cache_batched(_p(q), _p(k), _p(v), _p(q_bias), _p(k_bias), _p(v_bias), _p(cos), _p(sin), _p(pos), B, _p(q_out), _p(k_cache),
+                                                      _p(v_cache), q.numel() // (B * hd), k_cache.shape[1], hd, k_cache.shape[2], _dt(q.dtype), _stream())
+    _C.check(rc, "hqq_hip_bias_rope_cache_batched")
+    return q_out
+
+
+def bias_rope_cache(q: Tensor, k: Tensor, v: Tensor, q_bias: Tensor, k_bias: Tensor, v_bias: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor,
+                    v_cache: Tensor, q_out: Tensor) -> Tensor:
+    """bias_rope_cache_batched for one sequence: cos / sin [hd], the static caches [n_kv_heads, cache_len, head_dim], position pos[0] (device int64)"""
+    return bias_rope_cache_batched(q, k, v, q_bias, k_bias, v_bias, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), q_out)
+
+
 def _attn_batched_args(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, who: str):
     B = _batch_of(pos, who)
     if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():

@@ -6,6 +6,8 @@ step — all decoder layers, attention, sampling argmax — as one graph removes
 capturable by construction (no allocation, no host sync, stream passed in)."""
 from __future__ import annotations
 
+import gc
+
 import torch
 from torch import Tensor
 
@@ -63,24 +65,33 @@ class GraphedGreedyDecoder:
     qk_norm: what a Qwen3 model (per-head q_norm / k_norm in front of the rotary embedding) decodes through.  "model" (default): the model's own forward, as
     before.  "fused" (opt-in): where llama_fused.supports_qk_norm accepts the model, the fused step with ops.qknorm_rope_cache_batched in rope_cache's place
     (`fused_qk_norm`; `fused` stays the Llama flag), and generate_batch's batched step where supports_qk_norm_batch accepts the batch.
+    qkv_bias: what a Qwen2 / Qwen2.5 model (biases on q_proj / k_proj / v_proj) decodes through.  "model" (default): the model's own forward, as before.
+    "fused" (opt-in): where llama_fused.supports_qkv_bias accepts the model, the fused step with bias-free q|k|v launches and ops.bias_rope_cache_batched in
+    rope_cache's place (`fused_qkv_bias`; `fused` stays the Llama flag), and generate_batch's batched step where supports_qkv_bias_batch accepts the batch.
     generate() and generate_batch() prefill differently and keep different caches, but advance through the same routine (_advance) over a small state
     holder: the device tensors tok / next_tok / pos that the captured graphs read and write, the step (None: the model's own forward), the dictionary
     its graphs are kept in with the key of an attended length in it, and the rule for that length."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
-                 do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model"):
+                 do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
+                 qkv_bias: str = "model"):
         from transformers import StaticCache
         from . import llama_fused
         if axis0 not in ("model", "fused"):
             raise ValueError("axis0: 'model' or 'fused'")
         if qk_norm not in ("model", "fused"):
             raise ValueError("qk_norm: 'model' or 'fused'")
+        if qkv_bias not in ("model", "fused"):
+            raise ValueError("qkv_bias: 'model' or 'fused'")
         self.model = model.eval()
         self.fused = bool(fused) and llama_fused.supports(model)
         self.axis0 = axis0
         self.fused_axis0 = bool(fused) and axis0 == "fused" and not self.fused and llama_fused.supports_axis0(model)
         self.qk_norm = qk_norm
         self.fused_qk_norm = bool(fused) and qk_norm == "fused" and not self.fused and not self.fused_axis0 and llama_fused.supports_qk_norm(model)
+        self.qkv_bias = qkv_bias
+        self.fused_qkv_bias = bool(fused) and qkv_bias == "fused" and not self.fused and not self.fused_axis0 and not self.fused_qk_norm and \
+            llama_fused.supports_qkv_bias(model)
         self._fused_mod = llama_fused
         self.attention = attention   # "sdpa": HF's attention function (token-identical to model(...)); "hip": the decode-attention kernel (faster, within rounding)
         self.glue = glue             # "auto" / "folded": RMSNorm, residual adds and SiLU * up inside the GEMV launches (csrc/gemv_block.hip); "kernels": round 4's separate glue kernels
@@ -191,10 +202,11 @@ class GraphedGreedyDecoder:
             st["pos"].fill_(T)
         else:
             self.step = None
-            if self.fused or self.fused_axis0 or self.fused_qk_norm:
+            if self.fused or self.fused_axis0 or self.fused_qk_norm or self.fused_qkv_bias:
                 try:
                     self.step = self._fused_mod.FusedLlamaStep(self.model, self.cache, self.max_cache_len, attention=self.attention,
-                                                               glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0, qk_norm=self.fused_qk_norm)
+                                                               glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0, qk_norm=self.fused_qk_norm,
+                                                               qkv_bias=self.fused_qkv_bias)
                 except ValueError:   # a cache layout / attention configuration the fused step does not restate: the model's own forward serves
                     self.step = None
             self.graphs = {}
@@ -249,8 +261,17 @@ class GraphedGreedyDecoder:
                 self._restore(st, snap)
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._decode_once(st, kv)
+            # Python's cyclic collector is held off for the capture: a pass that starts inside it can free a dead decoder (a reference cycle: its state holder keeps
+            # bound methods of it) with its captured graphs and cache tensors, and releasing those during a capture aborts the process.  torch.cuda.graph
+            # collects before a capture only under torch.compiler.config.force_cudagraph_gc; the model's own forward allocates enough objects to start a pass.
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g):
+                    self._decode_once(st, kv)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             st["graphs"][key] = g                        # the capture itself does not execute: replay for this step
         if g is not None:
             g.replay()
@@ -354,7 +375,7 @@ class GraphedGreedyDecoder:
         """the kept state holder of generate_batch at B rows, or None when the batched step does not serve the model there"""
         fm = self._fused_mod
         if not ((self.fused and fm.supports_batch(self.model, B)) or (self.fused_axis0 and fm.supports_axis0_batch(self.model, B)) or
-                (self.fused_qk_norm and fm.supports_qk_norm_batch(self.model, B))):
+                (self.fused_qk_norm and fm.supports_qk_norm_batch(self.model, B)) or (self.fused_qkv_bias and fm.supports_qkv_bias_batch(self.model, B))):
             return None
         cfg = self.model.config
         n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
@@ -362,7 +383,8 @@ class GraphedGreedyDecoder:
         cache = self._StaticCache(config=cfg, max_cache_len=self.max_cache_len)
         cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
         try:   # (without the decoder's `glue`: the batched step has the one-launch front and back wherever they apply)
-            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0, qk_norm=self.fused_qk_norm)
+            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0, qk_norm=self.fused_qk_norm,
+                                          qkv_bias=self.fused_qkv_bias)
         except ValueError:
             return None
         st = {"B": B, "cache": cache, "scratch": self._StaticCache(config=cfg, max_cache_len=self.max_cache_len), "step": step,
@@ -408,13 +430,16 @@ class HFGenerator:
     a prompt that leaves less than max_new_tokens of cache generates what fits."""
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
-                 compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model"):
+                 compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
+                 qkv_bias: str = "model"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         if axis0 not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts an axis-0 model into the fused decode step)
             raise ValueError("axis0: 'model' or 'fused'")
         if qk_norm not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts a Qwen3 model into the fused decode step)
             raise ValueError("qk_norm: 'model' or 'fused'")
+        if qkv_bias not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts a Qwen2 model into the fused decode step)
+            raise ValueError("qkv_bias: 'model' or 'fused'")
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -426,7 +451,8 @@ class HFGenerator:
         self.is_compiled = compile is not None
         self.use_graph = compile is not None
         self.compile_options = compile_options
-        self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm)
+        self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
+                                            qkv_bias=qkv_bias)
         self.init()
 
     @staticmethod

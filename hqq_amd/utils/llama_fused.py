@@ -27,6 +27,13 @@ head of q and k (q_norm / k_norm, an RMSNorm over head_dim) before the rotary em
     RMSNorm in its prologue -> qknorm_rope_cache -> attention -> o / gate|up pair / down folded as above
 = 5 launches + the attention's.  The rotary-paired q / k copies are not built: the head norm must see a whole head before the rotation.
 
+Qwen2 / Qwen2.5 models (supports_qkv_bias; opt-in through GraphedGreedyDecoder(qkv_bias="fused")) differ from Llama's block in ONE thing too: q_proj, k_proj
+and v_proj carry a bias (o_proj and the MLP do not).  The q|k|v launch stays bias-free and ops.bias_rope_cache_batched (csrc/block.hip) takes rope_cache's
+place: it adds the three biases (one rounding each, the linears' own `out += bias`), then rotates and writes the cache:
+    add_rmsnorm -> q|k|v -> bias_rope_cache -> attention -> ...   (glue="kernels", and every batch > 1); folded glue: q|k|v with the RMSNorm in its
+    prologue -> bias_rope_cache -> attention -> o / gate|up pair / down folded as above
+= 5 launches + the attention's.  The rotary-paired q / k copies are not built here either: their epilogue rotates before a bias could be added.
+
 Only what the step needs is taken from the model: module weights and the HF StaticCache's tensors are used in place (nothing is copied).
 """
 from __future__ import annotations
@@ -47,7 +54,8 @@ def arch_supported(model) -> bool:
     else.  Models that merely LOOK like it (same attribute names) would decode wrong tokens through that sequence without an error: Granite (residual /
     embedding / logits / attention multipliers), Gemma (soft-capping, (1 + w) norms), Cohere, OLMo ...  Qwen3 (per-head q_norm / k_norm in front of the
     rotary embedding) is refused HERE too — this predicate and the defaults built on it stay Llama's — and is served by a predicate of its own,
-    qk_norm_arch_supported, whose step (FusedLlamaStep(qk_norm=True)) has a kernel for that op; nothing takes it without being asked."""
+    qk_norm_arch_supported, whose step (FusedLlamaStep(qk_norm=True)) has a kernel for that op; nothing takes it without being asked.  Qwen2 (biases on
+    q_proj / k_proj / v_proj) likewise: qkv_bias_arch_supported and FusedLlamaStep(qkv_bias=True)."""
     try:
         cfg = model.config
         if getattr(cfg, "model_type", None) not in ("llama", "mistral"):
@@ -108,18 +116,53 @@ def qk_norm_arch_supported(model) -> bool:
         return False
 
 
+def qkv_bias_arch_supported(model) -> bool:
+    """arch_supported's counterpart for the step with qkv_bias=True, which restates Qwen2DecoderLayer (transformers models/qwen2): Llama's block with a
+    bias on q_proj, k_proj and v_proj, and none on o_proj or the MLP.  model_type "qwen2", full attention in every layer (no sliding window), no head
+    norms or sinks, SiLU; the three attention projections of every block have a bias and the other four linears have none (what the biases must look
+    like on the quantised layers is _structure's question)."""
+    try:
+        cfg = model.config
+        if getattr(cfg, "model_type", None) != "qwen2" or not _common_arch(cfg):
+            return False
+        if any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
+            return False
+        for blk in model.model.layers:
+            at = blk.self_attn
+            if any(hasattr(at, n) for n in ("q_norm", "k_norm", "qk_norm", "sinks")) or getattr(at, "sliding_window", None):
+                return False
+            if any(getattr(at, n).bias is None for n in ("q_proj", "k_proj", "v_proj")):
+                return False
+            if at.o_proj.bias is not None or any(getattr(blk.mlp, n).bias is not None for n in ("gate_proj", "up_proj", "down_proj")):
+                return False
+            if type(getattr(blk.mlp, "act_fn", None)).__name__ not in ("SiLUActivation", "SiLU"):
+                return False
+        return True
+    except AttributeError:
+        return False
+
+
 def _decoder_linears(model):
     """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers"""
     return [[_hip(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
             for b in model.model.layers]
 
 
-def _structure(model, axis: int, arch=arch_supported):
-    """The structural half of supports(), supports_axis0*() and supports_qk_norm*(): an allow-listed architecture (`arch`: arch_supported, or
-    qk_norm_arch_supported for the step with qk_norm=True), fp16 or bf16, the rotary / embedding /
-    lm_head modules the step calls, every decoder linear an HQQLinearHIP of the compute dtype without bias, quantised along `axis`, on the GPU, and
-    RMSNorm weights of that dtype with a multiple of 8 features.  Returns (dtype, _decoder_linears(model)), or None where the model is not of that shape;
-    which kernels cover the layers is the callers' question."""
+def _bias_ok(L, dt, wanted: bool) -> bool:
+    """a decoder linear's bias as _structure asks for it: none, or (wanted) a dense 1-D tensor of out_features elements in the compute dtype on the layer's device"""
+    if not wanted:
+        return L.bias is None
+    b = L.bias
+    return isinstance(b, Tensor) and b.dim() == 1 and b.shape[0] == L.out_features and b.is_contiguous() and b.dtype == dt and b.device == L.W_q.device
+
+
+def _structure(model, axis: int, arch=arch_supported, qkv_bias: bool = False):
+    """The structural half of supports(), supports_axis0*(), supports_qk_norm*() and supports_qkv_bias*(): an allow-listed architecture (`arch`:
+    arch_supported, qk_norm_arch_supported for the step with qk_norm=True, qkv_bias_arch_supported for the step with qkv_bias=True), fp16 or bf16, the
+    rotary / embedding / lm_head modules the step calls, every decoder linear an HQQLinearHIP of the compute dtype, quantised along `axis`, on the GPU, and
+    RMSNorm weights of that dtype with a multiple of 8 features.  Biases: by default no decoder linear may have one; with qkv_bias, q_proj, k_proj and v_proj
+    must each HAVE one — 1-D, dense, out_features elements, the compute dtype, the layer's device — and o_proj and the MLP still have none.
+    Returns (dtype, _decoder_linears(model)), or None where the model is not of that shape; which kernels cover the layers is the callers' question."""
     if not arch(model):
         return None
     try:
@@ -131,7 +174,9 @@ def _structure(model, axis: int, arch=arch_supported):
             return None
         blocks = _decoder_linears(model)
         for blk, lin in zip(inner.layers, blocks):
-            if not all(isinstance(L, HQQLinearHIP) and L.bias is None and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == axis for L in lin):
+            if not all(isinstance(L, HQQLinearHIP) and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == axis for L in lin):
+                return None
+            if not all(_bias_ok(L, dt, qkv_bias and i < 3) for i, L in enumerate(lin)):
                 return None
             for nrm in (blk.input_layernorm, blk.post_attention_layernorm):
                 if nrm.weight.dtype != dt or nrm.weight.shape[0] % 8:
@@ -148,9 +193,10 @@ def supports(model) -> bool:
     return _supports(model, arch_supported)
 
 
-def _supports(model, arch) -> bool:
-    """supports() / supports_qk_norm(): _structure along axis 1 under the architecture predicate `arch`, and the kernel coverage of the grouped launches"""
-    found = _structure(model, 1, arch)
+def _supports(model, arch, qkv_bias: bool = False) -> bool:
+    """supports() / supports_qk_norm() / supports_qkv_bias(): _structure along axis 1 under the architecture predicate `arch`, and the kernel coverage of
+    the grouped launches"""
+    found = _structure(model, 1, arch, qkv_bias)
     if found is None:
         return False
     dt, blocks = found
@@ -224,6 +270,18 @@ def supports_qk_norm_batch(model, B: int) -> bool:
     return supports_qk_norm(model) and _batch_served(model, B)
 
 
+def supports_qkv_bias(model) -> bool:
+    """supports() for a Qwen2 model (qkv_bias_arch_supported in arch_supported's place, biases admitted on q_proj / k_proj / v_proj and only there: otherwise
+    the same structural and kernel-coverage checks).  ops.bias_rope_cache_batched serves any even head_dim, so none is asked for here (attention="hip" has
+    its own check).  What FusedLlamaStep(qkv_bias=True) takes; nothing takes it by default."""
+    return _supports(model, qkv_bias_arch_supported, True)
+
+
+def supports_qkv_bias_batch(model, B: int) -> bool:
+    """supports_batch() for a Qwen2 model: supports_qkv_bias(model), and every decoder linear served by a fused decode kernel at B rows"""
+    return supports_qkv_bias(model) and _batch_served(model, B)
+
+
 def _batch_served(model, B: int) -> bool:
     specs = [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lins in _decoder_linears(model) for L in lins]
     return batch_covers(model.model.norm.weight.dtype, B, specs, ops._default_opts)
@@ -240,7 +298,7 @@ class FusedLlamaStep:
     every glue kernel gives the bits of the batch-1 kernel for sequence b alone, and the linears run at M = batch."""
 
     def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
-                 qk_norm: bool = False):
+                 qk_norm: bool = False, qkv_bias: bool = False):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -251,7 +309,10 @@ class FusedLlamaStep:
         the folded launches serve one activation row, so a batch takes the separate glue kernels whatever `glue` allows.
         qk_norm: the model is a Qwen3 (supports_qk_norm; supports_qk_norm_batch beyond one sequence): ops.qknorm_rope_cache_batched — the per-head q_norm /
         k_norm, then the rotary embedding and the cache write — takes rope_cache's place after q|k|v, and attention="hip" attends on its rotated q_out
-        (ops.attn_decode_batched).  The folded glue keeps q|k|v in the natural row order (the norm comes before the rotation): 5 launches + attention."""
+        (ops.attn_decode_batched).  The folded glue keeps q|k|v in the natural row order (the norm comes before the rotation): 5 launches + attention.
+        qkv_bias: the model is a Qwen2 (supports_qkv_bias; supports_qkv_bias_batch beyond one sequence): the q|k|v launch stays bias-free and
+        ops.bias_rope_cache_batched — the three biases added, then the rotary embedding and the cache write — takes rope_cache's place, with either attention
+        on its rotated q_out as for qk_norm; folded glue: 5 launches + attention.  Not together with axis0 or qk_norm."""
         # axis0: the model's linears are quantised along axis 0 (supports_axis0).  The step is the glue="kernels" sequence with q|k|v and gate|up through
         # ops.gemv_axis0_grouped (gate|up's reduce applies SiLU * up: no silu_mul launch) and o / down through ops.gemv_axis0, on the layers' own tensors
         # (nothing re-laid out); the folded launches read axis-1 meta and are never taken.
@@ -280,13 +341,20 @@ class FusedLlamaStep:
             raise ValueError("glue: 'auto', 'folded' or 'kernels'")
         self.axis0 = bool(axis0)
         self.qk_norm = bool(qk_norm)
+        self.qkv_bias = bool(qkv_bias)
+        if self.qkv_bias and (self.axis0 or self.qk_norm):
+            raise ValueError("hqq_amd: qkv_bias=True goes with neither axis0 nor qk_norm (an axis-0 Qwen2 decodes through the model's own forward; no served "
+                             "architecture has both biases and head norms)")
         if self.qk_norm and self.axis0:
             raise ValueError("hqq_amd: qk_norm=True serves models quantised along axis 1 (an axis-0 Qwen3 decodes through the model's own forward)")
         if self.qk_norm and not (supports_qk_norm(model) if B == 1 else supports_qk_norm_batch(model, B)):
             raise ValueError(f"hqq_amd: qk_norm=True needs a Qwen3 model whose decoder linears the fused decode kernels serve at {B} rows "
                              "(supports_qk_norm / supports_qk_norm_batch)")
+        if self.qkv_bias and not (supports_qkv_bias(model) if B == 1 else supports_qkv_bias_batch(model, B)):
+            raise ValueError(f"hqq_amd: qkv_bias=True needs a Qwen2 model whose decoder linears the fused decode kernels serve at {B} rows "
+                             "(supports_qkv_bias / supports_qkv_bias_batch)")
         # (a single sequence of an axis-1 model is not asked: its callers ask supports(), and models construct here that it refuses)
-        if (B != 1 or self.axis0) and not self.qk_norm and not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
+        if (B != 1 or self.axis0) and not self.qk_norm and not self.qkv_bias and not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
             raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows "
                              f"({'axis0=True: supports_axis0_batch' if self.axis0 else 'supports_batch'})")
         if self.axis0 and glue == "folded":
@@ -331,7 +399,9 @@ class FusedLlamaStep:
                 "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
                 "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
             })
-            if self.folded and attention != "hip" and self.hd % 2 == 0 and not self.qk_norm:
+            if self.qkv_bias:   # the three layers' own bias tensors (static addresses under graph capture); the launch records above stay bias-free
+                self.blocks[-1]["qkv_bias"] = (q.bias, k.bias, v.bias)
+            if self.folded and attention != "hip" and self.hd % 2 == 0 and not self.qk_norm and not self.qkv_bias:
                 # q and k in the rotary-paired row order (ops.rotary_pair_layout): the q|k|v launch's epilogue applies the rotary embedding and writes the cache
                 # (the kernel attention folds the rotary embedding into the attention launch instead: it keeps the natural order)
                 def _sub_ok(t, L_):
@@ -421,10 +491,13 @@ class FusedLlamaStep:
             else:
                 ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
                 self._grouped(b, "qkv", [b["q"], b["k"], b["v"]])
-            if self.qk_norm:   # Qwen3: the heads of q and k normalised, rotated and cached in one launch; either attention then reads the rotated q_out
-                qn, kn = at.q_norm, at.k_norm
-                ops.qknorm_rope_cache_batched(b["q"], b["k"], b["v"], qn.weight, kn.weight, qn.variance_epsilon, kn.variance_epsilon, cos, sin, pos,
-                                              b["kc"], b["vc"], b["qr"])
+            if self.qk_norm or self.qkv_bias:
+                if self.qk_norm:   # Qwen3: the heads of q and k normalised, rotated and cached in one launch; either attention then reads the rotated q_out
+                    qn, kn = at.q_norm, at.k_norm
+                    ops.qknorm_rope_cache_batched(b["q"], b["k"], b["v"], qn.weight, kn.weight, qn.variance_epsilon, kn.variance_epsilon, cos, sin, pos,
+                                                  b["kc"], b["vc"], b["qr"])
+                else:   # Qwen2: the projections' biases added to the bias-free q|k|v, then rotated and cached, one launch
+                    ops.bias_rope_cache_batched(b["q"], b["k"], b["v"], *b["qkv_bias"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
                 if self.attention == "hip":
                     att = ops.attn_decode_batched(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
                 else:
@@ -481,5 +554,5 @@ class FusedLlamaBatchStep(FusedLlamaStep):
     """FusedLlamaStep under the name and positional signature the batched callers construct it by: no `glue` argument ("auto": the one-launch front
     wherever the tables exist)"""
 
-    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False):
-        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm)
+    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False):
+        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias)

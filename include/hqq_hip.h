@@ -217,6 +217,18 @@ int hqq_hip_rope_cache_batched(const void* q, const void* k, const void* v, cons
 int hqq_hip_qknorm_rope_cache_batched(const void* q, const void* k, const void* v, const void* q_weight, const void* k_weight, float q_eps, float k_eps, const void* cos,
                                       const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out, void* k_cache, void* v_cache, int64_t n_heads,
                                       int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream);
+/* hqq_hip_rope_cache_batched with the three projection biases added in front: what Qwen2Attention.forward's biased q_proj / k_proj / v_proj give on top
+ * of bias-free linear launches (transformers models/qwen2/modeling_qwen2.py).  q' = q + q_bias, k' = k + k_bias, v' = v + v_bias — q_bias
+ * [n_heads * head_dim], k_bias / v_bias [n_kv_heads * head_dim], dense, in T, shared by every sequence, all three required.  Rounding contract: each add
+ * is ONE rounding in T, the `out += bias` the decode kernels make on a rounded matmul result (a native half add for fp16; bf16: the fp32 sum of the two
+ * values rounded to nearest even); then hqq_hip_rope_cache's arithmetic on q' / k'; v' goes to the cache.  The result is bit for bit that of
+ * hqq_hip_gemv_grouped with the biases followed by hqq_hip_rope_cache_batched.  Shapes, positions and the rule for a position outside [0, cache_len)
+ * (nothing is written to the caches, q_out still is) as hqq_hip_rope_cache_batched.  Any even head_dim (odd or < 2: HQQ_ERR_SHAPE), fp16 / bf16 (other
+ * dtypes: HQQ_ERR_UNSUPPORTED); element-aligned pointers suffice; no workspace; deterministic.  Every check is made before anything is launched.
+ * The symbol was added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits. */
+int hqq_hip_bias_rope_cache_batched(const void* q, const void* k, const void* v, const void* q_bias, const void* k_bias, const void* v_bias, const void* cos,
+                                    const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out, void* k_cache, void* v_cache, int64_t n_heads,
+                                    int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream);
 /* The per-token work either side of the decoder blocks (ABI 7; hqq/utils/generation_hf.py:405-540: embedding lookup, the rotary table's row, the causal mask of one query in
  * front; argmax, token hand-over, position increment behind) as ONE launch each — copies and compares only, bit-identical to the torch ops they replace:
  *   hqq_hip_token_prologue  h[H] = embed[*tok_dev]; cos / sin [head_dim] = cos_tab / sin_tab [L, head_dim] row *pos_dev (tables NULL: skipped);
