@@ -74,6 +74,9 @@ SYMBOLS = {
     # dx = g . dequantize(W_q) for axis-1 layers (csrc/gemm_dgrad.hip)
     "hqq_hip_gemm_dgrad_covers": (_i32, [_i32, _i64, _i64, _i64, _i64, _i32]),
     "hqq_hip_gemm_dgrad": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
+    # out = dequantize(W_q) + ((A @ B) * scaling)^T, the merge of a LoRA adapter (csrc/lora_merge.hip)
+    "hqq_hip_lora_merge_covers": (_i32, [_i32, _i64, _i64, _i64, _i32, _i32, _i32, _i64]),
+    "hqq_hip_lora_merge": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -8,8 +8,13 @@ dequantise + matmul elsewhere).  `PeftUtils` adds the adapters to a whole model,
 
 Linears are found by qualified-name suffix ("tag"), exactly as `hqq_amd.utils.model.quantize_model` finds them; there is no model zoo and no base class.
 
-Not covered (the reference's experimental or merge paths): HQQLinearLoRAWithFakeQuant, HQQLinearGroupedProj, merge_and_quantize / PeftUtils.merge_lora,
-and training through HQQLinearHIP (backends/hip.py), which stays inference-only.
+`HQQLinearLoRA.merge_and_quantize` / `PeftUtils.merge_lora` fold a trained adapter back into a freshly quantised `HQQLinear` (peft.py:167-190, 396-404,
+452-461): base weight + ((A @ B) * scaling)^T in one launch (`ops.lora_merge`, csrc/lora_merge.hip) where the kernel covers the layer, the reference's
+torch statements elsewhere; the HIP quantiser takes it from there.  A merged model is an ordinary quantised model again: prepare_for_inference and the
+fused decode step apply.
+
+Not covered (the reference's experimental paths): HQQLinearLoRAWithFakeQuant, HQQLinearGroupedProj, and training through or merging from HQQLinearHIP
+(backends/hip.py), which stays inference-only.
 """
 from __future__ import annotations
 
@@ -92,8 +97,77 @@ class HQQLinearLoRA(nn.Module):
                 out = out + self.bias
         return out
 
+    # merge_and_quantize builds the merged weight in ONE launch (ops.lora_merge for a wrapped HQQLinear, ops.lora_merge_dense for a wrapped nn.Linear)
+    # wherever ops.lora_merge_covers says so.  HQQLinearLoRA.fused_merge = False keeps the torch composition everywhere (the counterpart of
+    # HQQLinear.fused_backward).
+    fused_merge = True
+
+    def _scaling_float(self) -> float:
+        """`scaling` as load_state_dict can leave it (a number, a tensor, a parameter), read once"""
+        s = self.scaling
+        return float(s.detach().float().item()) if isinstance(s, Tensor) else float(s)
+
+    def _base_weight(self) -> Tensor:
+        """the wrapped layer's [out, in] weight, a tensor of its own: what the reference obtains by pushing an identity through the forward (peft.py:169-176)
+        for whatever linear it wraps; here the two kinds of linear a model holds are read directly"""
+        from .quantize import HQQLinear
+        if isinstance(self.linear_layer, HQQLinear):
+            return self.linear_layer.dequantize()
+        if isinstance(self.linear_layer, nn.Linear):
+            return self.linear_layer.weight.data.clone()
+        raise NotImplementedError(f"hqq_amd: merging into a wrapped {type(self.linear_layer).__name__} is not covered (HQQLinear or nn.Linear)")
+
+    def _merged_weight_fused(self, scaling: float) -> Optional[Tensor]:
+        """base weight + adapter through hqq_hip_lora_merge, or None where the kernel does not cover the layer"""
+        from .. import ops
+        from .quantize import HQQLinear, Quantizer
+        ll, A, B = self.linear_layer, self.lora_A.data, self.lora_B.data
+        if not (A.is_cuda and B.is_cuda and A.dtype == B.dtype):
+            return None
+        if isinstance(ll, HQQLinear):
+            meta = ll.meta
+            if not (ll.ready and meta.get("packing")) or not ll.W_q.is_cuda:
+                return None
+            N, K = meta["shape"]
+            axis = meta["axis"]
+            gs = meta["group_size"] if meta["group_size"] else (K if axis == 1 else N)
+            nbits = Quantizer._packing_bits[meta["packing"]]
+            scale, zero = meta["scale"].reshape(-1), meta["zero"].reshape(-1)
+            if scale.numel() != (N * K) // gs or zero.numel() != scale.numel() or scale.dtype != zero.dtype:   # (channel_wise=False: one pair per tensor)
+                return None
+            if not ops.lora_merge_covers(scale.dtype, A.dtype, N, K, gs, nbits, axis, self.r):
+                return None
+            W_q = ll.W_q.view(meta["unpack_view_dtype"]) if meta["view_as_float"] else ll.W_q
+            return ops.lora_merge(W_q, scale, zero, N, K, gs, nbits, axis, A, B, scaling)
+        if isinstance(ll, nn.Linear):
+            W = ll.weight.data
+            if not W.is_cuda or not ops.lora_merge_covers(W.dtype, A.dtype, W.shape[0], W.shape[1], 0, 0, 0, self.r):
+                return None
+            return ops.lora_merge_dense(W, A, B, scaling)
+        return None
+
     def merge_and_quantize(self, quant_config: dict):
-        raise NotImplementedError("hqq_amd: merging an adapter back into a quantised layer (peft.py:167-190) is not covered")
+        """peft.py:167-190: the base weight, `W += (A @ B * scaling).t().to(W.dtype)`, `HQQLinear(None, quant_config).quantize(W, **quant_config)`; the new
+        layer's bias is a clone of the wrapper's (or None).  Deliberately different from the reference: the new layer takes the wrapped layer's compute
+        dtype and device (the reference's HQQLinear(None, quant_config) falls back to fp16 / "cuda" whatever the layer was), and the bias is cast to that
+        compute dtype (a trained bias is in train_dtype)."""
+        from ..backends.hip import HQQLinearHIP
+        from .quantize import HQQLinear
+        if isinstance(self.linear_layer, HQQLinearHIP):
+            raise NotImplementedError("hqq_amd: a wrapped HQQLinearHIP is inference-only (its container may be re-laid out): merge the adapters before "
+                                      "prepare_for_inference")
+        scaling = self._scaling_float()
+        W = self._merged_weight_fused(scaling) if HQQLinearLoRA.fused_merge else None
+        if W is None:   # outside the kernel's coverage (an fp32 compute dtype, r > 256, a CPU layer, ...) or switched off: the same torch statements
+            W = self._base_weight()
+            W += (torch.matmul(self.lora_A.data, self.lora_B.data) * scaling).t().to(W.dtype)
+        new_layer = HQQLinear(None, {"offload_meta": False, **quant_config}, compute_dtype=self.compute_dtype, device=self.device)
+        new_layer.bias = None if self.bias is None else self.bias.data.clone().to(device=self.device, dtype=self.compute_dtype)
+        wq = dict(quant_config["weight_quant_params"])
+        if wq.get("group_size") is None:   # one group per row / column, as HQQLinear.initialize resolves it
+            wq["group_size"] = self.in_features if wq.get("axis") == 1 else self.out_features
+        new_layer.quantize(W, wq, quant_config.get("scale_quant_params"), quant_config.get("zero_quant_params"))
+        return new_layer
 
     def cast(self, dtype: torch.dtype = float16):
         self.lora_A.data = self.lora_A.data.to(dtype)
@@ -154,6 +228,13 @@ def patch_linear_add_peft(layer: nn.Module, patch_params: Optional[dict]) -> nn.
     return _HQQ_LORA_MAPPING[lora_type](layer, patch_params)
 
 
+def patch_linear_merge_peft(layer: nn.Module, quant_config: Optional[dict]) -> nn.Module:
+    """peft.py:396-404: the merged, re-quantised layer, or the wrapper itself where no quant config is given"""
+    if not quant_config:
+        return layer
+    return layer.merge_and_quantize(quant_config)
+
+
 def _lora_layers(model: nn.Module):
     return [(name, mod) for name, mod in model.named_modules() if is_hqq_lora_layer(mod)]
 
@@ -182,8 +263,26 @@ class PeftUtils:
         model.peft_config = peft_config
 
     @classmethod
-    def merge_lora(cls, model, merge_lora_params, base_class=None, verbose: bool = False) -> None:
-        raise NotImplementedError("hqq_amd: merging adapters back into quantised layers (peft.py:452-461) is not covered")
+    def merge_lora(cls, model: nn.Module, merge_lora_params: Dict[str, Optional[dict]], base_class=None, verbose: bool = False) -> None:
+        """peft.py:452-461: every HQQLinearLoRA whose qualified name ends with a key of merge_lora_params that maps to a quant config is replaced in its
+        parent by the merged HQQLinear; a key mapped to None (or a wrapper no key matches) stays.  model.peft_config goes once no wrapper is left."""
+        tags = list(merge_lora_params)
+        todo = []
+        for name, mod in _lora_layers(model):
+            tag = next((t for t in tags if name.endswith(t)), None)
+            if tag is not None and merge_lora_params.get(tag):
+                todo.append((name, tag))
+        for name, tag in todo:
+            parent_name, _, child = name.rpartition(".")
+            parent = model.get_submodule(parent_name) if parent_name else model
+            setattr(parent, child, patch_linear_merge_peft(getattr(parent, child), merge_lora_params[tag]))
+            if verbose:
+                print(f"merged {name}")
+        autoname_modules(model)
+        if not _lora_layers(model) and hasattr(model, "peft_config"):
+            del model.peft_config
+        if torch.cuda.is_available():
+            torch.cuda.empty_cache()
 
     @classmethod
     def cast_lora_weights(cls, model: nn.Module, dtype: torch.dtype, base_class=None, verbose: bool = False) -> None:

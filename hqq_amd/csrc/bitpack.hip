@@ -11,16 +11,10 @@
 #include <type_traits>
 
 #include "hqq_common.h"
+#include "unpack_common.h"   // Pk<NBITS>: the container layout, shared with lora_merge.hip
 #include "w3s.h"
 
 namespace hqq {
-
-template <int NBITS> struct Pk {
-  static constexpr int per = (NBITS == 3) ? 10 : 8 / NBITS;
-  static constexpr uint32_t mask = (NBITS == 8) ? 0xFFu : ((1u << NBITS) - 1u);
-  // shift of slab s inside the container (slab 0 most significant)
-  static __device__ __forceinline__ int shift(int s) { return (NBITS == 3) ? (27 - 3 * s) : NBITS * (per - 1 - s); }
-};
 
 // ---- input element readers for pack (uint8 levels, or float32 holding integer levels) ------------
 __device__ __forceinline__ uint32_t level_of(uint8_t v) { return v; }

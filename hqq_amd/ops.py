@@ -766,6 +766,80 @@ def gemm_dgrad(g: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, N: int, K: i
     return out.reshape(*g.shape[:-1], K)
 
 
+LORA_MERGE_MAX_R = 256
+
+
+@functools.lru_cache(maxsize=4096)
+def lora_merge_covers(dtype, lora_dtype, N, K, group_size, nbits, axis, r) -> bool:
+    """what hqq_hip_lora_merge serves (the library's own answer, nothing launched): a compute dtype fp16 / bf16, an adapter in fp32 / fp16 / bf16 of
+    rank 1 .. 256, and a base weight that is either packed — every (nbits, axis, group_size, N, K) dequantize() accepts — or dense (nbits = 0;
+    group_size and axis are not looked at)"""
+    if dtype not in _DT or lora_dtype not in _DT or isinstance(nbits, float) or int(nbits) != nbits:
+        return False
+    if int(nbits) != 0 and (group_size is None or axis not in (0, 1)):
+        return False
+    return bool(_C.lib().hqq_hip_lora_merge_covers(int(nbits), int(N), int(K), int(group_size or 0), int(axis or 0), _DT[dtype], _DT[lora_dtype], int(r)))
+
+
+def _lora_merge(who: str, nbits: int, base: Tensor, scale, zero, N: int, K: int, group_size: int, axis: int, dtype, A: Tensor, B: Tensor, scaling,
+                out: Tensor | None) -> Tensor:
+    _dev(base, scale, zero, A, B, out)
+    if A.dtype != B.dtype:
+        raise TypeError(f"hqq_amd: {who}: lora_A and lora_B must share a dtype")
+    if A.dim() != 2 or B.dim() != 2 or A.shape[0] != K or B.shape[1] != N or A.shape[1] != B.shape[0]:
+        raise ValueError(f"hqq_amd: {who} needs A [K, r] and B [r, N] for a [{N}, {K}] weight, got {tuple(A.shape)} and {tuple(B.shape)}")
+    r = A.shape[1]
+    if any(t is not None and t.device != base.device for t in (scale, zero, A, B, out)):
+        raise ValueError(f"hqq_amd: {who}: every tensor must be on the base weight's device")
+    if not lora_merge_covers(dtype, A.dtype, N, K, group_size, nbits, axis, r):
+        raise NotImplementedError(f"hqq_amd: {who} is not covered for compute dtype {dtype}, adapter dtype {A.dtype}, rank {r}, nbits {nbits}, "
+                                  f"axis {axis}, group_size {group_size}, N {N}, K {K} (fp16 / bf16, rank 1 .. {LORA_MERGE_MAX_R}, what dequantize accepts)")
+    if out is None:
+        out = torch.empty((N, K), dtype=dtype, device=base.device)
+    elif out.numel() != N * K or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} writes a dense output of {N} x {K} elements in the compute dtype")
+    with torch.cuda.device(base.device):
+        rc = _C.lib().hqq_hip_lora_merge(int(nbits), _p(base.contiguous()), _p(None if scale is None else scale.contiguous()),
+                                         _p(None if zero is None else zero.contiguous()), _p(A.contiguous()), _p(B.contiguous()), float(scaling), _p(out),
+                                         int(N), int(K), int(group_size), int(axis), _dt(dtype), _dt(A.dtype), int(r), _stream())
+    _C.check(rc, "hqq_hip_lora_merge")
+    return out.reshape(N, K)
+
+
+def lora_merge(W_q: Tensor, scale: Tensor, zero: Tensor, N: int, K: int, group_size: int, nbits: int, axis: int, A: Tensor, B: Tensor, scaling: float,
+               out: Tensor | None = None) -> Tensor:
+    """dequantize(W_q, ...) + ((A @ B) * scaling).t().to(dtype) in one launch (hqq_hip_lora_merge), [N, K] in scale.dtype: the base weight is the bits
+    of dequantize(); the rank-r product is an fp32 sum over j = 0 .. r - 1 in that order of separately rounded products, then rounded as the torch
+    statements round (adapter dtype, * scaling, adapter dtype, compute dtype, the add).  A [K, r], B [r, N] in fp32 / fp16 / bf16.  Deterministic, on the
+    current stream, no workspace.  `out`: a contiguous buffer of N x K elements in scale.dtype.  Raises NotImplementedError outside lora_merge_covers()."""
+    _dev(W_q, scale, zero, A, B, out)
+    if scale.dtype != zero.dtype:
+        raise TypeError("hqq_amd: scale and zero must share the compute dtype")
+    if group_size is None:
+        raise NotImplementedError("hqq_amd: lora_merge needs a group size")
+    if not lora_merge_covers(scale.dtype, A.dtype, N, K, group_size, nbits, axis, A.shape[-1]) or int(nbits) == 0:
+        raise NotImplementedError(f"hqq_amd: lora_merge is not covered for compute dtype {scale.dtype}, adapter dtype {A.dtype}, rank {A.shape[-1]}, "
+                                  f"nbits {nbits}, axis {axis}, group_size {group_size}, N {N}, K {K}")
+    gs = int(group_size)
+    groups = (N * K) // gs
+    if scale.numel() != groups or zero.numel() != groups:   # the kernel reads N * K / group_size constants through raw pointers
+        raise ValueError(f"hqq_amd: lora_merge needs {groups} scale / zero values (N * K / group_size), got {scale.numel()} / {zero.numel()}")
+    urows, ucols = (groups, gs) if axis == 1 else (gs, groups)
+    want = (torch.int32, packed_rows(nbits, urows) * ucols) if nbits == 3 else (torch.uint8, packed_rows(nbits, urows) * ucols)
+    if (W_q.dtype, W_q.numel()) != want:
+        raise ValueError(f"hqq_amd: lora_merge reads the reference's container of {want[1]} {want[0]} elements, got {W_q.numel()} of {W_q.dtype}")
+    return _lora_merge("lora_merge", nbits, W_q, scale, zero, N, K, gs, axis, scale.dtype, A, B, scaling, out)
+
+
+def lora_merge_dense(W: Tensor, A: Tensor, B: Tensor, scaling: float, out: Tensor | None = None) -> Tensor:
+    """W + ((A @ B) * scaling).t().to(W.dtype) for a dense [N, K] weight in fp16 / bf16, with lora_merge's arithmetic (hqq_hip_lora_merge, dense form).
+    W is not modified.  Raises NotImplementedError outside lora_merge_covers(..., nbits=0, ...)."""
+    if W.dim() != 2:
+        raise ValueError("hqq_amd: lora_merge_dense needs a [N, K] weight")
+    N, K = W.shape
+    return _lora_merge("lora_merge_dense", 0, W, None, None, N, K, 0, 0, W.dtype, A, B, scaling, out)
+
+
 def _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts, library_gemm: bool = False) -> Tensor:
     """axis-0 layers: decode sizes through hqq_hip_gemv_axis0; GEMV_MAX_M + 1 .. AXIS0_GEMM_ROUTE_MAX_M rows through hqq_hip_gemm_axis0 (unless
     library_gemm); everything else as HQQLinear has always run them — the HIP dequantise kernel (axis 0) + torch.matmul, then `out += bias`

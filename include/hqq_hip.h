@@ -420,6 +420,33 @@ int hqq_hip_gemm_dgrad(int nbits, const void* g, const void* Wq, const void* sca
                        int64_t group_size, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Merge a LoRA adapter into a layer's weight in one launch (csrc/lora_merge.hip): out[N,K] = dequantize(Wq) + ((A @ B) * scaling)^T, ready for
+ * hqq_hip_quantize.  What it replaces is the torch composition of HQQLinearLoRA.merge_and_quantize (hqq/core/peft.py:167-190): an identity pushed
+ * through the forward for the base weight, a K x N fp32 matmul, scaled, transposed, cast, added in place.
+ * With T the compute dtype (`dtype`) and L the adapter's (`lora_dtype`), for every n < N, k < K:
+ *     w         = hqq_hip_dequantize's value at [n, k]                 (its bits: two roundings in T)
+ *     acc       = 0.f;  for j = 0 .. r-1 in this order:  acc = fadd_rn(acc, fmul_rn(float(A[k, j]), float(B[j, n])))
+ *     m         = round_L(acc)                                          (the matmul's result in L; the identity for fp32)
+ *     s         = round_L(float(m) * scaling)
+ *     d         = round_T(s)                                            (.to(W.dtype))
+ *     out[n, k] = round_T(float(w) + float(d))                          (W += ...: one rounding in T)
+ * The multiply and the add are separate IEEE fp32 operations: no FMA, no MFMA, no atomics, no split over j — the result can be restated exactly on
+ * the host and two calls on the same inputs give the same bits.
+ * A [K, r] and B [r, N] dense, row-major, in L (HQQ_F32 / HQQ_F16 / HQQ_BF16); out [N, K] dense in T (HQQ_F16 / HQQ_BF16).
+ * Base weight, packed form: Wq, scale, zero, N, K, group_size, axis exactly as hqq_hip_dequantize takes them, every (nbits, axis, group_size, N, K) it
+ * accepts (8 / 4 / 3 / 2 / 1 bits, both axes); what it refuses with HQQ_ERR_NBITS / HQQ_ERR_SHAPE is refused here with the same code.
+ * Base weight, dense form: nbits == 0 — Wq is a dense [N, K] weight in T and takes the place of w; scale, zero, group_size and axis are not read.
+ * 1 <= r <= 256 and T fp16 / bf16; an fp32 T or another rank: HQQ_ERR_UNSUPPORTED ("not covered"); hqq_hip_lora_merge_covers answers the same
+ * question (1 / 0) without launching.  Every check is made before anything is launched and needs no GPU.  No workspace; runs on `stream`; pointers
+ * need the alignment of their elements only (16-byte stores and vector loads are used where the addresses allow); partial tiles on either edge are
+ * handled, nothing outside out[N, K] is written.
+ * The two symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_lora_merge_covers(int nbits, int64_t N, int64_t K, int64_t group_size, int axis, int dtype, int lora_dtype, int64_t r);
+int hqq_hip_lora_merge(int nbits, const void* Wq, const void* scale, const void* zero, const void* A, const void* B, float scaling, void* out,
+                       int64_t N, int64_t K, int64_t group_size, int axis, int dtype, int lora_dtype, int64_t r, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
