@@ -74,6 +74,9 @@ SYMBOLS = {
     # dx = g . dequantize(W_q) for axis-1 layers (csrc/gemm_dgrad.hip)
     "hqq_hip_gemm_dgrad_covers": (_i32, [_i32, _i64, _i64, _i64, _i64, _i32]),
     "hqq_hip_gemm_dgrad": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
+    # dx = g . dequantize(W_q, axis=0) for axis-0 layers (csrc/gemm_dgrad_axis0.hip; added at ABI 9 without a bump: nothing that existed changed)
+    "hqq_hip_gemm_dgrad_axis0_covers": (_i32, [_i32, _i64, _i64, _i64, _i64, _i32]),
+    "hqq_hip_gemm_dgrad_axis0": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
     # out = dequantize(W_q) + ((A @ B) * scaling)^T, the merge of a LoRA adapter (csrc/lora_merge.hip)
     "hqq_hip_lora_merge_covers": (_i32, [_i32, _i64, _i64, _i64, _i32, _i32, _i32, _i64]),
     "hqq_hip_lora_merge": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _vp]),

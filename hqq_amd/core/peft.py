@@ -3,7 +3,8 @@
 `HQQLinearLoRA` wraps a linear (an `HQQLinear`, or any module with `in_features` / `out_features` / `bias`) and adds the trainable low-rank
 pair lora_A [in, r], lora_B [r, out]: y = linear(x) + ((x @ A) @ B * scaling).to(x.dtype) (+ bias), in the reference's operation order.  The base layer
 stays frozen; its gradient with respect to the input runs through HQQLinear's autograd route (fused `hqq_hip_gemm_dgrad` where HQQLinear routes it there,
-dequantise + matmul elsewhere).  `PeftUtils` adds the adapters to a whole model, casts them, and saves / loads them in the reference's v0.2 file format
+`hqq_hip_gemm_dgrad_axis0` for a layer quantised along axis 0, dequantise + matmul elsewhere): the wrapper inherits the route from the layer it wraps
+and holds no routing of its own.  `PeftUtils` adds the adapters to a whole model, casts them, and saves / loads them in the reference's v0.2 file format
 ({"peft_config": ..., "parameters": {module_name: state_dict}}), so that adapter files travel both ways.
 
 Linears are found by qualified-name suffix ("tag"), exactly as `hqq_amd.utils.model.quantize_model` finds them; there is no model zoo and no base class.

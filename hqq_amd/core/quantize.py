@@ -532,7 +532,8 @@ class HQQLinear(nn.Module):
         return c[1], c[2]   # (in-place edits through W_q.data / meta[...].data bypass the version counters: call .cuda(device) again — it drops the copy — after such an edit)
 
     # the backward with respect to the input, grad @ dequantize(W_q): one fused launch (csrc/gemm_dgrad.hip) instead of dequantise + torch.matmul, for up to
-    # ops.DGRAD_ROUTE_MAX_M rows of grad.  HQQLinear.fused_backward = False keeps dequantise + matmul at every size.
+    # ops.DGRAD_ROUTE_MAX_M rows of grad; layers quantised along axis 0: csrc/gemm_dgrad_axis0.hip, up to ops.DGRAD_AXIS0_ROUTE_MAX_M rows.
+    # HQQLinear.fused_backward = False keeps dequantise + matmul at every size.
     fused_backward = True
 
     def _dgrad_kernel_ok(self, grad: Tensor) -> bool:
@@ -547,6 +548,22 @@ class HQQLinear(nn.Module):
             return False
         rows = grad.numel() // N
         return rows <= ops.DGRAD_ROUTE_MAX_M and ops.gemm_dgrad_covers(grad.dtype, rows, N, K, gs, Quantizer._packing_bits[m["packing"]])
+
+    def _dgrad_axis0_kernel_ok(self, grad: Tensor) -> bool:
+        """a gradient [*, out_features] of a layer quantised along axis 0 whose product with the dequantised weight hqq_hip_gemm_dgrad_axis0 serves:
+        what _axis0_kernel_ok() asks of the layer (byte container, N K / group_size constants, one dtype, on the device), a shape
+        ops.gemm_dgrad_axis0_covers() accepts, and no more rows than the measured cut-off ops.DGRAD_AXIS0_ROUTE_MAX_M"""
+        m = self.meta
+        if m["axis"] != 0 or m["packing"] not in ("8bit_u8", "4bit_u8", "2bit_u8") or not (grad.is_cuda and self.W_q.is_cuda):
+            return False
+        N, K = (int(v) for v in m["shape"])
+        gs = int(m["group_size"]) if m["group_size"] else N
+        if gs <= 0 or N % gs or m["scale"].numel() != N * K // gs or m["zero"].numel() != N * K // gs:
+            return False   # (channel_wise=False stores one constant pair for the whole tensor)
+        if grad.shape[-1] != N or grad.dtype != m["scale"].dtype or m["zero"].dtype != grad.dtype:
+            return False
+        rows = grad.numel() // N
+        return rows <= ops.DGRAD_AXIS0_ROUTE_MAX_M and ops.gemm_dgrad_axis0_covers(grad.dtype, rows, N, K, gs, Quantizer._packing_bits[m["packing"]])
 
     def _matmul_hip(self, x: Tensor, transpose: bool = True, bias=None) -> Tensor:
         if transpose and self._axis0_kernel_ok(x):
@@ -569,6 +586,11 @@ class HQQLinear(nn.Module):
             N, K = m["shape"]
             W_q = self.W_q.view(m["unpack_view_dtype"]) if m["view_as_float"] else self.W_q
             return ops.gemm_dgrad(x, W_q, m["scale"], m["zero"], int(N), int(K), int(m["group_size"]), Quantizer._packing_bits[m["packing"]])
+        if not transpose and bias is None and HQQLinear.fused_backward and self._dgrad_axis0_kernel_ok(x):
+            m = self.meta
+            N, K = m["shape"]
+            W_q = self.W_q.view(m["unpack_view_dtype"]) if m["view_as_float"] else self.W_q
+            return ops.gemm_dgrad_axis0(x, W_q, m["scale"], m["zero"], int(N), int(K), m["group_size"] or None, Quantizer._packing_bits[m["packing"]])
         out = self.matmul(x, transpose=transpose)
         if bias is not None:
             out += bias

@@ -21,25 +21,9 @@
 // lane groups past the end read a valid address and contribute zeros through A.
 // Every k tile streams its own 64-byte column of the container and one meta element per row and slab; every further 64 rows of g stream them again (from L2 /
 // MALL), so the rebuild is repeated M / 64 times: a library GEMM on the dequantised weight overtakes this kernel as M grows (profiles/dgrad_summary.md).
-#include "axis0_common.h"
+#include "dgrad_common.h"
 
 namespace hqq {
-
-constexpr int DG_WAVES = 8;             // waves per workgroup: the N walk is dealt out over them
-constexpr int DG_KT = 64;               // k per output tile: 4 per lane of a 16-lane group
-constexpr int DG_BT = 4;                // 16-row tiles of g per workgroup
-constexpr int DG_PASS_M = 16 * DG_BT;
-constexpr int DG_STEP = 32;             // packed rows per step: 8 per lane group
-
-// 4 x 4 byte transpose: in[r] = bytes (k0..k3) of row r  ->  out[i] = byte i of rows (0, 1, 2, 3)
-static __device__ __forceinline__ u32x4 dg_transpose(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3) {
-  const uint32_t a = __builtin_amdgcn_perm(r1, r0, 0x05010400u);   // (r0b0, r1b0, r0b1, r1b1)
-  const uint32_t b = __builtin_amdgcn_perm(r1, r0, 0x07030602u);   // (r0b2, r1b2, r0b3, r1b3)
-  const uint32_t c = __builtin_amdgcn_perm(r3, r2, 0x05010400u);
-  const uint32_t d = __builtin_amdgcn_perm(r3, r2, 0x07030602u);
-  return u32x4{__builtin_amdgcn_perm(c, a, 0x05040100u), __builtin_amdgcn_perm(c, a, 0x07060302u),
-               __builtin_amdgcn_perm(d, b, 0x05040100u), __builtin_amdgcn_perm(d, b, 0x07060302u)};
-}
 
 // the meta of four rows as the pairs rebuild_* wants them: (row 0, row 2) against bytes (0, 2) of a transposed dword, (row 1, row 3) against bytes (1, 3)
 static __device__ __forceinline__ void dg_pair(const uint16_t (&v)[4], uint32_t& p02, uint32_t& p13) {
@@ -47,7 +31,7 @@ static __device__ __forceinline__ void dg_pair(const uint16_t (&v)[4], uint32_t&
   p13 = static_cast<uint32_t>(v[1]) | (static_cast<uint32_t>(v[3]) << 16);
 }
 
-// every slab of one step: rebuild the lane's 8 rows x 4 k of the slab, then 4 MFMAs (one per k of the lane) per live tile of g
+// every slab of one step: the slab's meta (one group per row: the same pair at each of the lane's four k), then dg_slab (dgrad_common.h)
 template <int NBITS, bool BF16, int SL, int NBT>
 struct DgSlabs {
   static constexpr int PER = 8 / NBITS;
@@ -61,42 +45,12 @@ struct DgSlabs {
       dg_pair(zq, zp[h][0], zp[h][1]);
       dg_pair(sq, sp[h][0], sp[h][1]);
     }
-    u32x4 lo0, lo1, hi0, hi1;   // lo0 = k 0, 1 of rows 0..3; lo1 = k 2, 3 of rows 0..3; hi*: rows 4..7
-    if constexpr (!BF16) {
-      half2_t zz[2][8], ss[2][8];
+    uint32_t zz[2][8], ss[2][8];
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { zz[h][i] = as_h2(zp[h][i & 1]); ss[h][i] = as_h2(sp[h][i & 1]); }
-      h8_t a0, a1;
-      rebuild_f16<NBITS, SL>(tlo, zz[0], ss[0], a0, a1, magic);
-      lo0 = __builtin_bit_cast(u32x4, a0); lo1 = __builtin_bit_cast(u32x4, a1);
-      rebuild_f16<NBITS, SL>(thi, zz[1], ss[1], a0, a1, magic);
-      hi0 = __builtin_bit_cast(u32x4, a0); hi1 = __builtin_bit_cast(u32x4, a1);
-    } else {
-      uint32_t zz[2][8], ss[2][8];
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { zz[h][i] = zp[h][i & 1]; ss[h][i] = sp[h][i & 1]; }
-      bf16x8_t a0, a1;
-      rebuild_bf16<NBITS, SL>(tlo, zz[0], ss[0], a0, a1);
-      lo0 = __builtin_bit_cast(u32x4, a0); lo1 = __builtin_bit_cast(u32x4, a1);
-      rebuild_bf16<NBITS, SL>(thi, zz[1], ss[1], a0, a1);
-      hi0 = __builtin_bit_cast(u32x4, a0); hi1 = __builtin_bit_cast(u32x4, a1);
-    }
-    // B operand of output column k0 + 4 c + i: rows (0, 2, 1, 3, 4, 6, 5, 7) of the lane's eight
-    const u32x4 bq[4] = {u32x4{lo0[0], lo0[1], hi0[0], hi0[1]}, u32x4{lo0[2], lo0[3], hi0[2], hi0[3]},
-                         u32x4{lo1[0], lo1[1], hi1[0], hi1[1]}, u32x4{lo1[2], lo1[3], hi1[2], hi1[3]}};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int bt = 0; bt < NBT; ++bt) {
-        if constexpr (!BF16)
-          acc[bt][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_t, ga[SL][bt]), __builtin_bit_cast(h8_t, bq[i]), acc[bt][i], 0, 0, 0);
-        else
-          acc[bt][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ga[SL][bt]), __builtin_bit_cast(bf16x8_t, bq[i]), acc[bt][i], 0, 0, 0);
-      }
+      for (int i = 0; i < 8; ++i) { zz[h][i] = zp[h][i & 1]; ss[h][i] = sp[h][i & 1]; }
+    dg_slab<NBITS, BF16, SL, NBT>(tlo, thi, zz, ss, ga, acc, magic);
     if constexpr (SL + 1 < PER) DgSlabs<NBITS, BF16, SL + 1, NBT>::run(tlo, thi, z, s, ga, acc, magic);
   }
 };
@@ -105,7 +59,7 @@ struct DgSlabs {
 template <int NBITS, bool BF16, int NBT>
 __device__ __forceinline__ void dg_tile(const uint16_t* __restrict__ g, const uint8_t* __restrict__ Wq, const uint16_t* __restrict__ scale,
                                         const uint16_t* __restrict__ zero, uint16_t* __restrict__ dx, int M, int N, int K, int Np, int G, int gs, int k0,
-                                        int m0, f32x4 (*red)[4 * DG_BT][64]) {
+                                        int m0, dg_red_t* red) {
   constexpr int PER = 8 / NBITS;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
@@ -145,62 +99,20 @@ __device__ __forceinline__ void dg_tile(const uint16_t* __restrict__ g, const ui
         s[j][r] = scale[mi];
       }
     u32x4 ga[PER][NBT];
-#pragma unroll
-    for (int j = 0; j < PER; ++j)
-#pragma unroll
-      for (int bt = 0; bt < NBT; ++bt) {
-        u32x4 v = ld16(grow[bt] + static_cast<int64_t>(j) * Np + pc);
-        if (!(live && mv[bt])) v = u32x4{0u, 0u, 0u, 0u};
-        ga[j][bt] = permute_x8(v);
-      }
+    dg_load_g<PER, NBT>(grow, mv, Np, pc, live, ga);
     const u32x4 tlo = dg_transpose(w[0], w[1], w[2], w[3]);
     const u32x4 thi = dg_transpose(w[4], w[5], w[6], w[7]);
     DgSlabs<NBITS, BF16, 0, NBT>::run(tlo, thi, z, s, ga, acc, magic);
   }
 
-  // the eight partial tiles, added in a fixed tree: wave w += wave w + 4, then + 2, then + 1
-#pragma unroll
-  for (int half = DG_WAVES / 2; half >= 1; half >>= 1) {
-    if (wave >= half && wave < 2 * half) {
-#pragma unroll
-      for (int bt = 0; bt < NBT; ++bt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) red[wave - half][4 * bt + i][lane] = acc[bt][i];
-    }
-    __syncthreads();
-    if (wave < half) {
-#pragma unroll
-      for (int bt = 0; bt < NBT; ++bt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[bt][i] += red[wave][4 * bt + i][lane];
-    }
-    __syncthreads();
-  }
-  if (wave != 0) return;
-  // D[m][c] of MFMA i: lane (c, o) holds rows m0 + 16 bt + 4 o + reg, column k0 + 4 c + i: 4 consecutive k per row
-#pragma unroll
-  for (int bt = 0; bt < NBT; ++bt)
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const int m = m0 + 16 * bt + 4 * o + rg;
-      if (m < M) {
-        uint16_t h[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if constexpr (BF16) h[i] = f32_to_bf16(acc[bt][i][rg]);
-          else h[i] = __builtin_bit_cast(uint16_t, static_cast<half_t>(acc[bt][i][rg]));
-        }
-        const u32x2 v = {static_cast<uint32_t>(h[0]) | (static_cast<uint32_t>(h[1]) << 16), static_cast<uint32_t>(h[2]) | (static_cast<uint32_t>(h[3]) << 16)};
-        *reinterpret_cast<u32x2*>(dx + static_cast<int64_t>(m) * K + kl) = v;
-      }
-    }
+  dg_reduce_store<BF16, NBT>(acc, red, dx, M, K, m0, kl, wave, lane);
 }
 
 template <int NBITS, bool BF16>
 __global__ __launch_bounds__(DG_WAVES * 64) void gemm_dgrad_kernel(const uint16_t* __restrict__ g, const uint8_t* __restrict__ Wq,
                                                                   const uint16_t* __restrict__ scale, const uint16_t* __restrict__ zero,
                                                                   uint16_t* __restrict__ dx, int M, int N, int K, int Np, int G, int gs, int ktiles) {
-  __shared__ f32x4 red[DG_WAVES / 2][4 * DG_BT][64];   // 64 KiB: the partial tiles of four waves
+  __shared__ dg_red_t red[DG_WAVES / 2];   // 64 KiB: the partial tiles of four waves
   // k tiles fastest: the workgroups in flight together share their rows of g and neighbouring 64-byte columns of the container
   const int k0 = static_cast<int>(blockIdx.x % ktiles) * DG_KT;
   const int m0 = static_cast<int>(blockIdx.x / ktiles) * DG_PASS_M;

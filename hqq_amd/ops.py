@@ -766,6 +766,53 @@ def gemm_dgrad(g: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, N: int, K: i
     return out.reshape(*g.shape[:-1], K)
 
 
+# The same product for a layer quantised along AXIS 0 (csrc/gemm_dgrad_axis0.hip), against ops.dequantize(axis=0) + torch.matmul.
+# HQQLinear._matmul_hip(transpose=False) takes the fused kernel up to this many rows of g; the rule is DGRAD_ROUTE_MAX_M's: the largest measured row
+# count at which the kernel is at least 10 % ahead on EVERY measured shape (tools/dgrad_axis0_bench.py; profiles/dgrad_axis0_summary.md holds the
+# table: ahead on every shape at every measured row count from 1 to 256; at 1024 rows it is within 10 % on 4096 x 11008, so the route ends at 256).
+# 0 would mean "opt-in only".  ops.gemm_dgrad_axis0 itself serves any row count.
+DGRAD_AXIS0_ROUTE_MAX_M = 256
+
+
+@functools.lru_cache(maxsize=4096)
+def gemm_dgrad_axis0_covers(dtype, M, N, K, group_size, nbits) -> bool:
+    """what hqq_hip_gemm_dgrad_axis0 serves (the library's own answer, nothing launched): axis-0 byte containers (8 / 4 / 2 bit), fp16 / bf16,
+    group_size % 16 == 0 dividing N (None: one group of N), K % 64 == 0, N % (8 * per) == 0, M >= 1, sizes within 32-bit offsets"""
+    if dtype not in _DT or isinstance(nbits, float) or int(nbits) != nbits:
+        return False
+    gs = int(N) if group_size is None else int(group_size)
+    return bool(_C.lib().hqq_hip_gemm_dgrad_axis0_covers(int(nbits), int(M), int(N), int(K), gs, _DT[dtype]))
+
+
+def gemm_dgrad_axis0(g: Tensor, W_q: Tensor, scale: Tensor, zero: Tensor, N: int, K: int, group_size, nbits: int, out: Tensor | None = None) -> Tensor:
+    """dx = g @ dequantize(W_q, axis=0) for g [*, N] -> [*, K] (hqq_hip_gemm_dgrad_axis0): the weights are the bits of dequantize(axis=0), accumulation
+    in fp32, one rounding; deterministic, on the current stream, no workspace.  group_size None: one group of N rows.  `out`: a contiguous buffer of
+    rows x K elements in g's dtype.  Raises NotImplementedError outside gemm_dgrad_axis0_covers()."""
+    _dev(g, W_q, scale, zero)
+    if g.dtype != scale.dtype or zero.dtype != scale.dtype:
+        raise TypeError("hqq_amd: g / scale / zero must share the compute dtype")
+    if g.shape[-1] != N:
+        raise ValueError(f"hqq_amd: g has {g.shape[-1]} features, layer produces {N}")
+    gs = int(N) if group_size is None else int(group_size)
+    if gs < 1 or scale.numel() != (N * K) // gs or zero.numel() != (N * K) // gs:
+        raise ValueError(f"hqq_amd: gemm_dgrad_axis0 needs {(N * K) // max(gs, 1)} scale / zero values (N * K / group_size), got {scale.numel()} / {zero.numel()}")
+    if W_q.dtype != torch.uint8 or W_q.numel() != (N // PER.get(nbits, 1)) * K:
+        raise NotImplementedError(f"hqq_amd: gemm_dgrad_axis0 reads the byte container [N / per, K] of an axis-0 layer (nbits={nbits})")
+    g2 = g.reshape(-1, N)
+    if not g2.is_contiguous():
+        g2 = g2.contiguous()
+    M = g2.shape[0]
+    if out is None:
+        out = torch.empty((M, K), dtype=g.dtype, device=g.device)
+    elif out.numel() != M * K or out.dtype != g.dtype or not out.is_contiguous() or out.device != g.device:
+        raise ValueError(f"hqq_amd: gemm_dgrad_axis0 writes a dense output of {M} x {K} elements in g's dtype")
+    with torch.cuda.device(g.device):
+        rc = _C.lib().hqq_hip_gemm_dgrad_axis0(int(nbits), _p(g2), _p(W_q.contiguous()), _p(scale.contiguous()), _p(zero.contiguous()), _p(out),
+                                               M, int(N), int(K), gs, _dt(g.dtype), _stream())
+    _C.check(rc, "hqq_hip_gemm_dgrad_axis0")
+    return out.reshape(*g.shape[:-1], K)
+
+
 LORA_MERGE_MAX_R = 256
 
 

@@ -420,6 +420,24 @@ int hqq_hip_gemm_dgrad(int nbits, const void* g, const void* Wq, const void* sca
                        int64_t group_size, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same product for layers quantised along AXIS 0: dx[M,K] = g[M,N] . dequantize(Wq, axis = 0)[N,K] in one launch (csrc/gemm_dgrad_axis0.hip) —
+ * the backward of the reference's only training backend (ATEN_BACKPROP, hqq/core/quantize.py:930), which serves axis 0 and nothing else.
+ * g [M,N] and dx [M,K] dense, row-major, in `dtype`; Wq the byte container [N / per, K] (the same bytes as on axis 1: byte [p, k] holds rows
+ * p + slab N / per); scale / zero N K / group_size elements of `dtype` in the axis-0 layout of hqq_hip_dequantize: with Nr = N / group_size, element
+ * (n, k) uses constant (n % Nr) K + k.  The contract is hqq_hip_gemm_dgrad's: weights are the bits of hqq_hip_dequantize(axis = 0) (two roundings in
+ * `dtype`); fp32 accumulation over n in the same fixed order, one rounding; no bias.  Deterministic: no atomics, no workspace; a row's output bits depend
+ * on (N, nbits) and that row of g only, not on M or on the rows it travels with; rows past M are never stored.  Runs on `stream`, graph-capturable.
+ * Covers: nbits 8 / 4 / 2 (byte containers), HQQ_F16 / HQQ_BF16, group_size % 16 == 0, N % group_size == 0 (group_size = N: one group per column),
+ * K % 64 == 0, N % (8 per) == 0, M >= 1, sizes within 32-bit offsets (HQQ_ERR_SHAPE, "size overflow", past them).  Anything else valid (3-bit, 1-bit,
+ * fp32, other shapes): HQQ_ERR_UNSUPPORTED ("not covered"), message in hqq_hip_last_error(); hqq_hip_gemm_dgrad_axis0_covers answers the same question
+ * (1 / 0) without launching.  Every check is made before anything is launched and needs no GPU.  g, Wq, scale, zero, dx 16-byte aligned.
+ * The two symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_gemm_dgrad_axis0_covers(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype);
+int hqq_hip_gemm_dgrad_axis0(int nbits, const void* g, const void* Wq, const void* scale, const void* zero, void* dx, int64_t M, int64_t N, int64_t K,
+                             int64_t group_size, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Merge a LoRA adapter into a layer's weight in one launch (csrc/lora_merge.hip): out[N,K] = dequantize(Wq) + ((A @ B) * scaling)^T, ready for
  * hqq_hip_quantize.  What it replaces is the torch composition of HQQLinearLoRA.merge_and_quantize (hqq/core/peft.py:167-190): an identity pushed
  * through the forward for the base weight, a K x N fp32 matmul, scaled, transposed, cast, added in place.
