@@ -80,6 +80,11 @@ SYMBOLS = {
     # out = dequantize(W_q) + ((A @ B) * scaling)^T, the merge of a LoRA adapter (csrc/lora_merge.hip)
     "hqq_hip_lora_merge_covers": (_i32, [_i32, _i64, _i64, _i64, _i32, _i32, _i32, _i64]),
     "hqq_hip_lora_merge": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _vp]),
+    # the adapter term of un-merged LoRA layers in the decode step (csrc/lora_decode.hip; added at ABI 9 without a bump: nothing that existed changed)
+    "hqq_hip_lora_decode_covers": (_i32, [_i32, _vp, _vp, _i64, _i64, _i32, _i32, _i32]),
+    "hqq_hip_lora_decode_workspace_bytes": (_sz, [_i32, _vp, _i64, _i64]),
+    "hqq_hip_lora_shrink": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _sz, _vp]),
+    "hqq_hip_lora_expand": (_i32, [_i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -887,6 +887,117 @@ def lora_merge_dense(W: Tensor, A: Tensor, B: Tensor, scaling: float, out: Tenso
     return _lora_merge("lora_merge_dense", 0, W, None, None, N, K, 0, 0, W.dtype, A, B, scaling, out)
 
 
+# ---- the adapter term of UN-MERGED LoRA layers in the decode step (csrc/lora_decode.hip) ------------------------------------------------------------
+LORA_DECODE_MAX_R = 256   # = LORA_MERGE_MAX_R: what can be merged can be decoded un-merged
+
+
+def _i64s(vals):
+    vals = [int(v) for v in vals]
+    return (ctypes.c_int64 * max(len(vals), 1))(*vals)
+
+
+def lora_decode_covers(dtype, lora_dtype, M, Ns, K, rs) -> bool:
+    """what hqq_hip_lora_shrink / hqq_hip_lora_expand serve (the library's own answer, nothing launched): a group of 1 .. GEMV_MAX_GROUP layers of ranks
+    `rs` (1 .. 256 each) and widths `Ns` on 1 .. GEMV_MAX_M rows of K features, K and every N a multiple of 8, activations in fp16 / bf16, adapters in
+    fp32 / fp16 / bf16 (A and B of one dtype: `lora_dtype`)"""
+    Ns, rs = tuple(Ns), tuple(rs)
+    if dtype not in _DT or lora_dtype not in _DT or len(Ns) != len(rs) or not rs:
+        return False
+    return bool(_C.lib().hqq_hip_lora_decode_covers(len(rs), _i64s(Ns), _i64s(rs), int(M), int(K), _DT[dtype], _DT[lora_dtype], _DT[lora_dtype]))
+
+
+def lora_decode_workspace_bytes(M: int, K: int, rs) -> int:
+    """bytes of workspace lora_shrink / lora_expand need for layers of ranks `rs` on M rows of K features (0: a group they refuse)"""
+    rs = tuple(rs)
+    return int(_C.lib().hqq_hip_lora_decode_workspace_bytes(len(rs), _i64s(rs), int(M), int(K))) if rs else 0
+
+
+def lora_decode_workspace(device, M: int, K: int, rs) -> Tensor:
+    """a workspace of lora_decode_workspace_bytes(M, K, rs) bytes on `device` for lora_shrink / lora_expand / lora_apply: the caller's own (a decode step
+    keeps one for its lifetime, so that a captured graph replays on a static address), not to be shared by calls that may run concurrently.  It needs
+    no clearing: every partial sum is written before it is read."""
+    need = lora_decode_workspace_bytes(M, K, rs)
+    if not need:
+        raise NotImplementedError(f"hqq_amd: lora_shrink / lora_expand do not cover ranks {tuple(rs)} on {M} rows of {K} features: {_C.last_error()}")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _lora_ws(ws: Tensor, who: str) -> None:
+    if not isinstance(ws, Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes the workspace lora_decode_workspace() returns (a dense uint8 tensor)")
+
+
+def lora_shrink(x: Tensor, As, workspace: Tensor) -> None:
+    """t_l = x @ A_l in fp32 for the 1 .. GEMV_MAX_GROUP adapters `As` ([K, r_l] each, one dtype, contiguous) that read the same x [*, K] of 1 .. GEMV_MAX_M
+    rows: ONE launch (hqq_hip_lora_shrink), the K slices' partial sums parked in `workspace` for lora_expand.  Deterministic; row m's bits do not
+    depend on the other rows.  Raises NotImplementedError outside lora_decode_covers()."""
+    As = list(As)
+    n = len(As)
+    _dev(x, workspace, *As)
+    _lora_ws(workspace, "lora_shrink")
+    if not 1 <= n <= GEMV_MAX_GROUP:
+        raise NotImplementedError(f"hqq_amd: lora_shrink takes 1 .. {GEMV_MAX_GROUP} adapters per call, got {n}")
+    K = x.shape[-1]
+    if any(A.dim() != 2 or A.shape[0] != K or not A.is_contiguous() for A in As):
+        raise ValueError(f"hqq_amd: lora_shrink needs dense A [K, r] matrices for x of {K} features, got {[tuple(A.shape) for A in As]}")
+    if len({A.dtype for A in As}) != 1 or any(A.device != x.device for A in As) or workspace.device != x.device:
+        raise TypeError("hqq_amd: lora_shrink needs adapters of ONE dtype, on x's device together with the workspace")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    VP = ctypes.c_void_p * n
+    with torch.cuda.device(x.device):
+        rc = _C.lib().hqq_hip_lora_shrink(n, _p(x2), VP(*[_p(A) for A in As]), _i64s(A.shape[1] for A in As), x2.shape[0], int(K), _dt(x.dtype),
+                                          _dt(As[0].dtype), _p(workspace), workspace.numel(), _stream())
+    _C.check(rc, "hqq_hip_lora_shrink")
+
+
+def lora_expand(workspace: Tensor, Bs, scalings, ys, K: int) -> None:
+    """y_l <- round(y_l + round(scaling_l * t_l @ B_l)) in place for the group lora_shrink just served: ONE launch (hqq_hip_lora_expand).  Bs: [r_l, N_l]
+    each (one dtype, contiguous); scalings: host floats; ys: dense [M, N_l] outputs in fp16 / bf16 that hold the base layers' results; K: the features
+    of the x the shrink read (it fixes the number of partial sums).  u is formed in fp32 over j = 0 .. r - 1 in ascending order from the partials summed in
+    slice order, rounded once to y's dtype, added with one more rounding: HQQLinearLoRA.forward's `out + forward_lora(x).to(x_dtype)`."""
+    Bs, ys, scalings = list(Bs), list(ys), [float(s) for s in scalings]
+    n = len(Bs)
+    _dev(workspace, *Bs, *ys)
+    _lora_ws(workspace, "lora_expand")
+    if not 1 <= n <= GEMV_MAX_GROUP:
+        raise NotImplementedError(f"hqq_amd: lora_expand takes 1 .. {GEMV_MAX_GROUP} adapters per call, got {n}")
+    if len(ys) != n or len(scalings) != n:
+        raise ValueError("hqq_amd: lora_expand needs one scaling and one output per adapter")
+    if any(B.dim() != 2 or not B.is_contiguous() for B in Bs):
+        raise ValueError("hqq_amd: lora_expand needs dense B [r, N] matrices")
+    M = ys[0].numel() // Bs[0].shape[1]
+    if any(y.numel() != M * B.shape[1] or y.shape[-1] != B.shape[1] or not y.is_contiguous() or y.dtype != ys[0].dtype for y, B in zip(ys, Bs)):
+        raise ValueError(f"hqq_amd: lora_expand updates dense [M, N] outputs of one dtype and {M} rows, N that of each B")
+    if len({B.dtype for B in Bs}) != 1 or any(t.device != workspace.device for t in Bs + ys):
+        raise TypeError("hqq_amd: lora_expand needs adapters of ONE dtype, on the workspace's device together with the outputs")
+    VP = ctypes.c_void_p * n
+    with torch.cuda.device(workspace.device):
+        rc = _C.lib().hqq_hip_lora_expand(n, _p(workspace), workspace.numel(), VP(*[_p(B) for B in Bs]), (ctypes.c_float * n)(*scalings),
+                                          VP(*[_p(y) for y in ys]), _i64s(B.shape[1] for B in Bs), _i64s(B.shape[0] for B in Bs), int(M), int(K),
+                                          _dt(ys[0].dtype), _dt(Bs[0].dtype), _stream())
+    _C.check(rc, "hqq_hip_lora_expand")
+
+
+def lora_apply(x: Tensor, adapters, ys, workspace: Tensor | None = None):
+    """ys[l] += (x @ A_l @ B_l * scaling_l).to(x.dtype) in place for `adapters` = [(A_l, B_l, scaling_l), ...] that share x: lora_shrink, then lora_expand
+    (two launches for the whole group).  ys hold the base layers' outputs on the same rows.  workspace: lora_decode_workspace(...) of at least this
+    group's size; None allocates one.  Returns ys."""
+    adapters = list(adapters)
+    As, Bs = [a[0] for a in adapters], [a[1] for a in adapters]
+    if any(A.dim() != 2 or B.dim() != 2 or A.shape[1] != B.shape[0] for A, B in zip(As, Bs)):
+        raise ValueError("hqq_amd: lora_apply needs A [K, r] and B [r, N] per adapter")
+    if any(A.dtype != B.dtype for A, B in zip(As, Bs)):
+        raise TypeError("hqq_amd: lora_apply: lora_A and lora_B must share a dtype")
+    K = x.shape[-1]
+    if workspace is None:
+        workspace = lora_decode_workspace(x.device, x.numel() // K, K, [A.shape[1] for A in As])
+    lora_shrink(x, As, workspace)
+    lora_expand(workspace, Bs, [a[2] for a in adapters], ys, K)
+    return ys
+
+
 def _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts, library_gemm: bool = False) -> Tensor:
     """axis-0 layers: decode sizes through hqq_hip_gemv_axis0; GEMV_MAX_M + 1 .. AXIS0_GEMM_ROUTE_MAX_M rows through hqq_hip_gemm_axis0 (unless
     library_gemm); everything else as HQQLinear has always run them — the HIP dequantise kernel (axis 0) + torch.matmul, then `out += bias`

@@ -68,13 +68,17 @@ class GraphedGreedyDecoder:
     qkv_bias: what a Qwen2 / Qwen2.5 model (biases on q_proj / k_proj / v_proj) decodes through.  "model" (default): the model's own forward, as before.
     "fused" (opt-in): where llama_fused.supports_qkv_bias accepts the model, the fused step with bias-free q|k|v launches and ops.bias_rope_cache_batched in
     rope_cache's place (`fused_qkv_bias`; `fused` stays the Llama flag), and generate_batch's batched step where supports_qkv_bias_batch accepts the batch.
+    lora: what a model whose decoder linears still carry LoRA adapters (HQQLinearLoRA wrappers around HQQLinearHIP layers) decodes through.  "model"
+    (default): the model's own forward, as before.  "fused" (opt-in): where llama_fused.supports_lora accepts the model, the fused step with one
+    ops.lora_shrink + one ops.lora_expand behind each base launch that has adapted layers (`fused_lora`; `fused` stays the Llama flag), and
+    generate_batch's batched step where supports_lora_batch accepts the batch.  An adapted model quantised along axis 0 needs axis0="fused" as well.
     generate() and generate_batch() prefill differently and keep different caches, but advance through the same routine (_advance) over a small state
     holder: the device tensors tok / next_tok / pos that the captured graphs read and write, the step (None: the model's own forward), the dictionary
     its graphs are kept in with the key of an attended length in it, and the rule for that length."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
-                 qkv_bias: str = "model"):
+                 qkv_bias: str = "model", lora: str = "model"):
         from transformers import StaticCache
         from . import llama_fused
         if axis0 not in ("model", "fused"):
@@ -83,6 +87,8 @@ class GraphedGreedyDecoder:
             raise ValueError("qk_norm: 'model' or 'fused'")
         if qkv_bias not in ("model", "fused"):
             raise ValueError("qkv_bias: 'model' or 'fused'")
+        if lora not in ("model", "fused"):
+            raise ValueError("lora: 'model' or 'fused'")
         self.model = model.eval()
         self.fused = bool(fused) and llama_fused.supports(model)
         self.axis0 = axis0
@@ -92,6 +98,13 @@ class GraphedGreedyDecoder:
         self.qkv_bias = qkv_bias
         self.fused_qkv_bias = bool(fused) and qkv_bias == "fused" and not self.fused and not self.fused_axis0 and not self.fused_qk_norm and \
             llama_fused.supports_qkv_bias(model)
+        self.lora = lora
+        self.fused_lora, self._lora_axis0 = False, False
+        if bool(fused) and lora == "fused" and not (self.fused or self.fused_axis0 or self.fused_qk_norm or self.fused_qkv_bias):
+            if llama_fused.supports_lora(model, axis0=False):
+                self.fused_lora = True
+            elif axis0 == "fused" and llama_fused.supports_lora(model, axis0=True):
+                self.fused_lora = self._lora_axis0 = True
         self._fused_mod = llama_fused
         self.attention = attention   # "sdpa": HF's attention function (token-identical to model(...)); "hip": the decode-attention kernel (faster, within rounding)
         self.glue = glue             # "auto" / "folded": RMSNorm, residual adds and SiLU * up inside the GEMV launches (csrc/gemv_block.hip); "kernels": round 4's separate glue kernels
@@ -163,6 +176,12 @@ class GraphedGreedyDecoder:
                 sc = meta.get("scale") if isinstance(meta, dict) else getattr(m, "scale", None)
                 ver = lambda t: None if (t is None or t.is_inference()) else t._version   # noqa: E731
                 fp.append((id(m), W.data_ptr(), ver(W), None if sc is None else sc.data_ptr(), ver(sc)))
+            A, B = getattr(m, "lora_A", None), getattr(m, "lora_B", None)
+            if isinstance(A, Tensor) and isinstance(B, Tensor) and hasattr(m, "linear_layer"):
+                # an adapter: load_lora_weights / cast replace .data (a kept step or graph would read freed tensors); `scaling` is baked into the step
+                ver = lambda t: None if t.is_inference() else t._version   # noqa: E731
+                sc = m._scaling_float() if hasattr(m, "_scaling_float") else getattr(m, "scaling", None)
+                fp.append((id(m), A.data_ptr(), ver(A), B.data_ptr(), ver(B), sc if isinstance(sc, (int, float)) else id(sc)))
         return tuple(fp)
 
     def reset(self) -> None:
@@ -202,11 +221,11 @@ class GraphedGreedyDecoder:
             st["pos"].fill_(T)
         else:
             self.step = None
-            if self.fused or self.fused_axis0 or self.fused_qk_norm or self.fused_qkv_bias:
+            if self.fused or self.fused_axis0 or self.fused_qk_norm or self.fused_qkv_bias or self.fused_lora:
                 try:
                     self.step = self._fused_mod.FusedLlamaStep(self.model, self.cache, self.max_cache_len, attention=self.attention,
-                                                               glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0, qk_norm=self.fused_qk_norm,
-                                                               qkv_bias=self.fused_qkv_bias)
+                                                               glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0 or self._lora_axis0,
+                                                               qk_norm=self.fused_qk_norm, qkv_bias=self.fused_qkv_bias, lora=self.fused_lora)
                 except ValueError:   # a cache layout / attention configuration the fused step does not restate: the model's own forward serves
                     self.step = None
             self.graphs = {}
@@ -375,7 +394,8 @@ class GraphedGreedyDecoder:
         """the kept state holder of generate_batch at B rows, or None when the batched step does not serve the model there"""
         fm = self._fused_mod
         if not ((self.fused and fm.supports_batch(self.model, B)) or (self.fused_axis0 and fm.supports_axis0_batch(self.model, B)) or
-                (self.fused_qk_norm and fm.supports_qk_norm_batch(self.model, B)) or (self.fused_qkv_bias and fm.supports_qkv_bias_batch(self.model, B))):
+                (self.fused_qk_norm and fm.supports_qk_norm_batch(self.model, B)) or (self.fused_qkv_bias and fm.supports_qkv_bias_batch(self.model, B)) or
+                (self.fused_lora and fm.supports_lora_batch(self.model, B, self._lora_axis0))):
             return None
         cfg = self.model.config
         n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
@@ -383,8 +403,8 @@ class GraphedGreedyDecoder:
         cache = self._StaticCache(config=cfg, max_cache_len=self.max_cache_len)
         cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
         try:   # (without the decoder's `glue`: the batched step has the one-launch front and back wherever they apply)
-            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0, qk_norm=self.fused_qk_norm,
-                                          qkv_bias=self.fused_qkv_bias)
+            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0 or self._lora_axis0,
+                                          qk_norm=self.fused_qk_norm, qkv_bias=self.fused_qkv_bias, lora=self.fused_lora)
         except ValueError:
             return None
         st = {"B": B, "cache": cache, "scratch": self._StaticCache(config=cfg, max_cache_len=self.max_cache_len), "step": step,
@@ -431,7 +451,7 @@ class HFGenerator:
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
                  compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
-                 qkv_bias: str = "model"):
+                 qkv_bias: str = "model", lora: str = "model"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         if axis0 not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts an axis-0 model into the fused decode step)
@@ -440,6 +460,8 @@ class HFGenerator:
             raise ValueError("qk_norm: 'model' or 'fused'")
         if qkv_bias not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts a Qwen2 model into the fused decode step)
             raise ValueError("qkv_bias: 'model' or 'fused'")
+        if lora not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts a model with un-merged LoRA adapters into the fused decode step)
+            raise ValueError("lora: 'model' or 'fused'")
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -452,7 +474,7 @@ class HFGenerator:
         self.use_graph = compile is not None
         self.compile_options = compile_options
         self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
-                                            qkv_bias=qkv_bias)
+                                            qkv_bias=qkv_bias, lora=lora)
         self.init()
 
     @staticmethod

@@ -49,6 +49,16 @@ def _hip(layer):
     return layer.layer if isinstance(layer, _GroupedMember) else layer
 
 
+def _is_lora(layer) -> bool:
+    from ..core.peft import is_hqq_lora_layer
+    return is_hqq_lora_layer(layer)
+
+
+def _unwrap(layer):
+    """the quantised layer behind an HQQLinearLoRA wrapper (prepare_for_inference keeps the wrapper and patches its linear_layer), or the layer itself"""
+    return _hip(layer.linear_layer) if _is_lora(layer) else _hip(layer)
+
+
 def arch_supported(model) -> bool:
     """The allow-list half of supports(): the step restates LlamaDecoderLayer's arithmetic (transformers models/llama, models/mistral) and nothing
     else.  Models that merely LOOK like it (same attribute names) would decode wrong tokens through that sequence without an error: Granite (residual /
@@ -142,10 +152,17 @@ def qkv_bias_arch_supported(model) -> bool:
         return False
 
 
-def _decoder_linears(model):
-    """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers"""
-    return [[_hip(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [_hip(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
+def _decoder_linears(model, lora: bool = False):
+    """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers (lora: the layer behind an HQQLinearLoRA wrapper where there is one)"""
+    get = _unwrap if lora else _hip
+    return [[get(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [get(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
             for b in model.model.layers]
+
+
+def _decoder_wrappers(model):
+    """beside _decoder_linears(model, lora=True): per block, the HQQLinearLoRA wrapper of each of the seven linears, or None where it is not adapted"""
+    return [[(w if _is_lora(w) else None) for w in [getattr(b.self_attn, n) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] +
+             [getattr(b.mlp, n) for n in ("gate_proj", "up_proj", "down_proj")]] for b in model.model.layers]
 
 
 def _bias_ok(L, dt, wanted: bool) -> bool:
@@ -156,12 +173,13 @@ def _bias_ok(L, dt, wanted: bool) -> bool:
     return isinstance(b, Tensor) and b.dim() == 1 and b.shape[0] == L.out_features and b.is_contiguous() and b.dtype == dt and b.device == L.W_q.device
 
 
-def _structure(model, axis: int, arch=arch_supported, qkv_bias: bool = False):
+def _structure(model, axis: int, arch=arch_supported, qkv_bias: bool = False, lora: bool = False):
     """The structural half of supports(), supports_axis0*(), supports_qk_norm*() and supports_qkv_bias*(): an allow-listed architecture (`arch`:
     arch_supported, qk_norm_arch_supported for the step with qk_norm=True, qkv_bias_arch_supported for the step with qkv_bias=True), fp16 or bf16, the
     rotary / embedding / lm_head modules the step calls, every decoder linear an HQQLinearHIP of the compute dtype, quantised along `axis`, on the GPU, and
     RMSNorm weights of that dtype with a multiple of 8 features.  Biases: by default no decoder linear may have one; with qkv_bias, q_proj, k_proj and v_proj
     must each HAVE one — 1-D, dense, out_features elements, the compute dtype, the layer's device — and o_proj and the MLP still have none.
+    lora: the checks apply to the layers behind HQQLinearLoRA wrappers (what the wrappers themselves must look like is supports_lora's question).
     Returns (dtype, _decoder_linears(model)), or None where the model is not of that shape; which kernels cover the layers is the callers' question."""
     if not arch(model):
         return None
@@ -172,7 +190,7 @@ def _structure(model, axis: int, arch=arch_supported, qkv_bias: bool = False):
             return None
         if not hasattr(inner, "rotary_emb") or not hasattr(inner, "embed_tokens") or not hasattr(model, "lm_head"):
             return None
-        blocks = _decoder_linears(model)
+        blocks = _decoder_linears(model, lora)
         for blk, lin in zip(inner.layers, blocks):
             if not all(isinstance(L, HQQLinearHIP) and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == axis for L in lin):
                 return None
@@ -193,10 +211,10 @@ def supports(model) -> bool:
     return _supports(model, arch_supported)
 
 
-def _supports(model, arch, qkv_bias: bool = False) -> bool:
+def _supports(model, arch, qkv_bias: bool = False, lora: bool = False) -> bool:
     """supports() / supports_qk_norm() / supports_qkv_bias(): _structure along axis 1 under the architecture predicate `arch`, and the kernel coverage of
     the grouped launches"""
-    found = _structure(model, 1, arch, qkv_bias)
+    found = _structure(model, 1, arch, qkv_bias, lora)
     if found is None:
         return False
     dt, blocks = found
@@ -210,8 +228,12 @@ def _supports(model, arch, qkv_bias: bool = False) -> bool:
 
 def supports_axis0_batch(model, B: int) -> bool:
     """supports_axis0(model) with every launch taking B activation rows (1 <= B <= ops.GEMV_MAX_M)"""
+    return _supports_axis0_batch(model, B)
+
+
+def _supports_axis0_batch(model, B: int, lora: bool = False) -> bool:
     M = int(B)
-    found = _structure(model, 0) if 1 <= M <= ops.GEMV_MAX_M else None
+    found = _structure(model, 0, lora=lora) if 1 <= M <= ops.GEMV_MAX_M else None
     if found is None:
         return False
     dt, blocks = found
@@ -282,9 +304,62 @@ def supports_qkv_bias_batch(model, B: int) -> bool:
     return supports_qkv_bias(model) and _batch_served(model, B)
 
 
-def _batch_served(model, B: int) -> bool:
-    specs = [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lins in _decoder_linears(model) for L in lins]
+def _batch_served(model, B: int, lora: bool = False) -> bool:
+    specs = [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lins in _decoder_linears(model, lora) for L in lins]
     return batch_covers(model.model.norm.weight.dtype, B, specs, ops._default_opts)
+
+
+# the four places of a decoder block where adapters are served, as slices of (q, k, v, o, gate, up, down): each is one base launch, followed by one
+# lora_shrink + one lora_expand over the adapted layers among its members
+LORA_GROUPS = (("qkv", 0, 3), ("o", 3, 4), ("gu", 4, 6), ("d", 6, 7))
+
+
+def _lora_wrappers_ok(model, B: int) -> bool:
+    """the wrapper half of supports_lora_batch: at least one decoder linear is an HQQLinearLoRA; every wrapper has no bias and does not train one, no
+    active dropout, and lora_A [K, r] / lora_B [r, N] dense, of ONE dtype the kernels cover, on the layer's device; ops.lora_decode_covers holds for the
+    adapted layers of each group at B rows"""
+    from torch import nn
+    try:
+        dt = model.model.norm.weight.dtype
+        found = False
+        for lin, wrs in zip(_decoder_linears(model, True), _decoder_wrappers(model)):
+            for L, w in zip(lin, wrs):
+                if w is None:
+                    continue
+                found = True
+                A, Bm = w.lora_A.data, w.lora_B.data
+                if w.bias is not None or w.train_bias or not (isinstance(w.peft_drop, nn.Identity) or not w.training):
+                    return False
+                if A.dtype != Bm.dtype or A.dim() != 2 or Bm.dim() != 2 or tuple(A.shape) != (L.in_features, w.r) or tuple(Bm.shape) != (w.r, L.out_features):
+                    return False
+                if not (A.is_contiguous() and Bm.is_contiguous() and A.device == L.W_q.device and Bm.device == L.W_q.device):
+                    return False
+                w._scaling_float()
+            for _, lo, hi in LORA_GROUPS:
+                ad = [(L, w) for L, w in zip(lin[lo:hi], wrs[lo:hi]) if w is not None]
+                if ad and (len({w.lora_A.dtype for _, w in ad}) != 1 or
+                           not ops.lora_decode_covers(dt, ad[0][1].lora_A.dtype, B, [L.out_features for L, _ in ad], ad[0][0].in_features, [w.r for _, w in ad])):
+                    return False
+        return found
+    except (AttributeError, TypeError, ValueError):
+        return False
+
+
+def supports_lora_batch(model, B: int, axis0: bool | None = None) -> bool:
+    """supports_batch (axis 1) or supports_axis0_batch (axis 0) asked of the layers BEHIND the HQQLinearLoRA wrappers — a decoder linear may be an
+    HQQLinearHIP or a wrapper whose linear_layer is one —, and the wrappers as _lora_wrappers_ok asks for them: any subset of the seven linears adapted,
+    with different ranks.  axis0: None — either axis; False / True — that one.  arch_supported architectures only (Llama, Mistral).  What
+    FusedLlamaStep(lora=True) takes; nothing takes it by default."""
+    B = int(B)
+    if B < 1 or not _lora_wrappers_ok(model, B):
+        return False
+    axis1 = axis0 in (None, False) and _supports(model, arch_supported, lora=True) and _batch_served(model, B, True)
+    return bool(axis1 or (axis0 in (None, True) and _supports_axis0_batch(model, B, True)))
+
+
+def supports_lora(model, axis0: bool | None = None) -> bool:
+    """supports() (axis 1) or supports_axis0() (axis 0) for a model whose decoder linears still carry their LoRA adapters: supports_lora_batch at one row"""
+    return supports_lora_batch(model, 1, axis0)
 
 
 def _gopts(Ls) -> int:
@@ -298,7 +373,7 @@ class FusedLlamaStep:
     every glue kernel gives the bits of the batch-1 kernel for sequence b alone, and the linears run at M = batch."""
 
     def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
-                 qk_norm: bool = False, qkv_bias: bool = False):
+                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -312,7 +387,13 @@ class FusedLlamaStep:
         (ops.attn_decode_batched).  The folded glue keeps q|k|v in the natural row order (the norm comes before the rotation): 5 launches + attention.
         qkv_bias: the model is a Qwen2 (supports_qkv_bias; supports_qkv_bias_batch beyond one sequence): the q|k|v launch stays bias-free and
         ops.bias_rope_cache_batched — the three biases added, then the rotary embedding and the cache write — takes rope_cache's place, with either attention
-        on its rotated q_out as for qk_norm; folded glue: 5 launches + attention.  Not together with axis0 or qk_norm."""
+        on its rotated q_out as for qk_norm; folded glue: 5 launches + attention.  Not together with axis0 or qk_norm.
+        lora: the model's decoder linears still carry LoRA adapters (supports_lora; supports_lora_batch beyond one sequence; with axis0 for a model
+        quantised along axis 0).  The step is the glue="kernels" sequence on the layers behind the wrappers, and after each of the four base launches —
+        q|k|v, o, gate|up, down — ONE ops.lora_shrink + ONE ops.lora_expand add the adapter terms of that group's adapted layers to the launch's
+        outputs, on the input the launch read: o's on self.delta before the residual add, gate|up's before SiLU (axis 0: the grouped launch then runs
+        without BLOCK_SILU and ops.silu_mul follows).  A group without an adapter launches nothing extra.  `scaling` is read once, here.  Not with
+        glue="folded", qk_norm or qkv_bias."""
         # axis0: the model's linears are quantised along axis 0 (supports_axis0).  The step is the glue="kernels" sequence with q|k|v and gate|up through
         # ops.gemv_axis0_grouped (gate|up's reduce applies SiLU * up: no silu_mul launch) and o / down through ops.gemv_axis0, on the layers' own tensors
         # (nothing re-laid out); the folded launches read axis-1 meta and are never taken.
@@ -342,6 +423,12 @@ class FusedLlamaStep:
         self.axis0 = bool(axis0)
         self.qk_norm = bool(qk_norm)
         self.qkv_bias = bool(qkv_bias)
+        self.lora = bool(lora)
+        if self.lora and (glue == "folded" or self.qk_norm or self.qkv_bias):
+            raise ValueError("hqq_amd: lora=True takes the separate glue kernels of a Llama / Mistral model: not with glue='folded', qk_norm or qkv_bias")
+        if self.lora and not supports_lora_batch(model, B, self.axis0):
+            raise ValueError(f"hqq_amd: lora=True needs a model with LoRA adapters on decoder linears the fused decode kernels serve at {B} rows "
+                             f"(supports_lora / supports_lora_batch{', axis 0' if self.axis0 else ''})")
         if self.qkv_bias and (self.axis0 or self.qk_norm):
             raise ValueError("hqq_amd: qkv_bias=True goes with neither axis0 nor qk_norm (an axis-0 Qwen2 decodes through the model's own forward; no served "
                              "architecture has both biases and head norms)")
@@ -354,13 +441,14 @@ class FusedLlamaStep:
             raise ValueError(f"hqq_amd: qkv_bias=True needs a Qwen2 model whose decoder linears the fused decode kernels serve at {B} rows "
                              "(supports_qkv_bias / supports_qkv_bias_batch)")
         # (a single sequence of an axis-1 model is not asked: its callers ask supports(), and models construct here that it refuses)
-        if (B != 1 or self.axis0) and not self.qk_norm and not self.qkv_bias and not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
+        if (B != 1 or self.axis0) and not self.qk_norm and not self.qkv_bias and not self.lora and not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
             raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows "
                              f"({'axis0=True: supports_axis0_batch' if self.axis0 else 'supports_batch'})")
         if self.axis0 and glue == "folded":
             raise ValueError("hqq_amd: glue='folded' reads axis-1 meta; an axis-0 model takes the separate glue kernels")
-        blocks = _decoder_linears(model)
-        can_fold = all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
+        blocks = _decoder_linears(model, self.lora)
+        wrappers = _decoder_wrappers(model) if self.lora else [[None] * 7 for _ in blocks]
+        can_fold = not self.lora and all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
                        for (q, _, _, o, g, _, d) in blocks for L, norm in ((q, True), (o, False), (g, True), (d, False))) and \
             all(g.out_features == u.out_features for (_, _, _, _, g, u, _) in blocks) and not (ops._default_opts & ops.OPT_FACTORED) and not self.axis0 and B == 1
         if glue == "folded" and not can_fold:
@@ -383,6 +471,7 @@ class FusedLlamaStep:
             else:
                 self.extra_weight_bytes = need
         self.blocks = []
+        lora_ws_bytes = 0
         for li, (blk, (q, k, v, o, g, u, d)) in enumerate(zip(inner.layers, blocks)):
             lay = cache.layers[li]
             if not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (B, self.n_kv, max_cache_len, self.hd) or \
@@ -399,6 +488,12 @@ class FusedLlamaStep:
                 "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
                 "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
             })
+            if self.lora:   # per group: the adapted members as (index within the group, A, B, scaling) — the tensors themselves (static addresses under graph capture)
+                for name, lo, hi in LORA_GROUPS:
+                    ad = [(i, w.lora_A.data, w.lora_B.data, w._scaling_float()) for i, w in enumerate(wrappers[li][lo:hi]) if w is not None]
+                    self.blocks[-1]["lora_" + name] = ad
+                    if ad:
+                        lora_ws_bytes = max(lora_ws_bytes, ops.lora_decode_workspace_bytes(B, ad[0][1].shape[0], [a[1].shape[1] for a in ad]))
             if self.qkv_bias:   # the three layers' own bias tensors (static addresses under graph capture); the launch records above stay bias-free
                 self.blocks[-1]["qkv_bias"] = (q.bias, k.bias, v.bias)
             if self.folded and attention != "hip" and self.hd % 2 == 0 and not self.qk_norm and not self.qkv_bias:
@@ -425,6 +520,8 @@ class FusedLlamaStep:
                     sub = ops.meta_scalable(pair[1], pair[2], pair[3], g.in_features, g.group_size, g.nbits)
                 self.blocks[-1]["gu_pair"] = [pair]
                 self.blocks[-1]["gu_pair_opts"] = ops.layer_opts((ops.OPT_META_SCALABLE if sub else 0) | (ops.OPT_W3S if g.w3s else 0))
+        # ONE adapter workspace for the whole step, sized for its largest group (the groups run one after the other on one stream)
+        self.lora_ws = torch.empty(lora_ws_bytes, dtype=torch.uint8, device=dev) if self.lora else None
         self.h = torch.empty(B, self.H, dtype=dt, device=dev)       # the residual stream
         self.xn = torch.empty(B, self.H, dtype=dt, device=dev)      # its normalised copy, input of the next linears
         self.delta = torch.empty(B, self.H, dtype=dt, device=dev)   # output of o / down, added by the next add_rmsnorm
@@ -491,6 +588,7 @@ class FusedLlamaStep:
             else:
                 ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
                 self._grouped(b, "qkv", [b["q"], b["k"], b["v"]])
+                self._adapters(b, "qkv", self.xn, [b["q"], b["k"], b["v"]])
             if self.qk_norm or self.qkv_bias:
                 if self.qk_norm:   # Qwen3: the heads of q and k normalised, rotated and cached in one launch; either attention then reads the rotated q_out
                     qn, kn = at.q_norm, at.k_norm
@@ -517,14 +615,18 @@ class FusedLlamaStep:
                 ops.gemv_block(h, b["n2"].weight, b["n2"].variance_epsilon, b["gu_pair"], K, b["gu_gs"], b["gu_nbits"], [b["a"]], ops.BLOCK_NORM | ops.BLOCK_SILU, opts=b["gu_pair_opts"])
                 ops.gemv_block(b["a"], None, 0.0, [(d.W_q, d.scale, d.zero, d.out_features)], d.in_features, d.group_size, d.nbits, [h], ops.BLOCK_RESID, opts=ops.layer_opts(d.opts))
                 continue
-            self._single(att.reshape(B, -1), o)
+            xo = att.reshape(B, -1)
+            self._single(xo, o)
+            self._adapters(b, "o", xo, [self.delta])     # before the residual add (the next add_rmsnorm)
             ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
-            if self.axis0:   # SiLU * up rides in the grouped launch's reduce: no silu_mul launch
+            if self.axis0 and not (self.lora and b["lora_gu"]):   # SiLU * up rides in the grouped launch's reduce: no silu_mul launch
                 self._grouped(b, "gu", [b["a"]], flags=ops.BLOCK_SILU)
-            else:
+            else:   # (an adapted gate | up of an axis-0 model too: the adapter terms come before SiLU)
                 self._grouped(b, "gu", [b["g"], b["u"]])
+                self._adapters(b, "gu", self.xn, [b["g"], b["u"]])
                 ops.silu_mul(b["g"], b["u"], out=b["a"])
             self._single(b["a"], d)
+            self._adapters(b, "d", b["a"], [self.delta])
             delta = self.delta
         ops.add_rmsnorm(h, delta, inner.norm.weight, inner.norm.variance_epsilon, out=self.xn)
         return self.model.lm_head(self.xn)
@@ -535,6 +637,15 @@ class FusedLlamaStep:
             ops.gemv_axis0_grouped(self.xn, b[which], self.H, b[which + "_gs"], b[which + "_nbits"], outs=outs, flags=flags)
         else:
             ops.gemv_grouped(self.xn, b[which], self.H, b[which + "_gs"], b[which + "_nbits"], outs=outs, opts=b[which + "_opts"])
+
+    def _adapters(self, b, which: str, x: Tensor, ys) -> None:
+        """the adapter terms of group `which` of block b added to the base launch's outputs ys, on the rows x that launch read: one lora_shrink + one
+        lora_expand over the adapted members; nothing where the group has none (or the step serves no adapters)"""
+        ad = b["lora_" + which] if self.lora else None
+        if not ad:
+            return
+        ops.lora_shrink(x, [a[1] for a in ad], self.lora_ws)
+        ops.lora_expand(self.lora_ws, [a[2] for a in ad], [a[3] for a in ad], [ys[a[0]] for a in ad], x.shape[-1])
 
     def _single(self, x: Tensor, L) -> None:
         """o or down: self.delta = L(x), added to the residual stream by the next add_rmsnorm"""
@@ -554,5 +665,6 @@ class FusedLlamaBatchStep(FusedLlamaStep):
     """FusedLlamaStep under the name and positional signature the batched callers construct it by: no `glue` argument ("auto": the one-launch front
     wherever the tables exist)"""
 
-    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False):
-        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias)
+    def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False,
+                 lora: bool = False):
+        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)

@@ -465,6 +465,40 @@ int hqq_hip_lora_merge(int nbits, const void* Wq, const void* scale, const void*
                        int64_t N, int64_t K, int64_t group_size, int axis, int dtype, int lora_dtype, int64_t r, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The adapter term of UN-MERGED LoRA layers in the decode step, two launches per group (csrc/lora_decode.hip).  For a group of
+ * 1 .. HQQ_GEMV_MAX_GROUP layers that read the same activation rows x[M, K] — each with A_l [K, r_l], B_l [r_l, N_l], a host float scaling[l] and an
+ * output y_l [M, N_l] that already holds the base layer's result (hqq_hip_gemv* / hqq_hip_gemv_grouped wrote it) — what HQQLinearLoRA.forward adds
+ * (hqq/core/peft.py:150-165, `out + forward_lora(x).to(x_dtype)`), with T the compute dtype (`dtype`):
+ *     t_l[m, j] = sum_k float(x[m, k]) * float(A_l[k, j])                  fp32     hqq_hip_lora_shrink  -> workspace
+ *     u_l[m, n] = scaling[l] * sum_j t_l[m, j] * float(B_l[j, n])          fp32     hqq_hip_lora_expand, which then does
+ *     y_l[m, n] = round_T(float(y_l[m, n]) + float(round_T(u_l[m, n])))             the read-modify-write of y
+ * t and u stay in fp32.  For fp32 adapters that is the reference's arithmetic up to summation order.  For fp16 / bf16 adapters the reference also
+ * rounds t, t @ B and the product with scaling to the adapter's dtype, and these kernels do NOT: the same value with fewer roundings (a deliberate
+ * deviation: results differ from HQQLinearLoRA.forward's in the last bits of T).
+ * Summation: K is cut into slices of 256 / 512 / 1024 k (r_l <= 64 / <= 128 / <= 256); slice i of layer l writes its partial t to
+ * workspace[layer][slice][M][r_l] (fp32, layers one after the other); the expand sums the partials in slice order and forms u over j = 0 .. r_l - 1 in
+ * ascending order.  The slice count, the order inside a slice and the order over j are functions of (K, r_l) alone — never of M, the row, a pointer
+ * or anything read from the device; fused multiply-adds for the products, plain fp32 adds for the partials; no atomics, no arrival counters.  Two calls give the same
+ * bits, and row m of an M-row call has the bits of a one-row call on that row.
+ * Covered: x / y fp16 or bf16 (an fp32 T: HQQ_ERR_UNSUPPORTED); A_l and B_l all HQQ_F32, all HQQ_F16 or all HQQ_BF16 (`lora_dtype`), dense, row-major;
+ * 1 <= M <= HQQ_GEMV_MAX_M; 1 <= r_l <= 256 (the ranks hqq_hip_lora_merge takes: what can be merged can be decoded un-merged); K % 8 == 0,
+ * N_l % 8 == 0 (both up to 2^24); r_l, N_l and scaling[l] may differ per layer.  Anything else: HQQ_ERR_UNSUPPORTED with a message, before anything
+ * is launched and without a GPU.  hqq_hip_lora_decode_covers answers the same question (1 / 0, A's and B's dtype given separately: they must agree).
+ * Workspace: hqq_hip_lora_decode_workspace_bytes(n_layers, r, M, K) bytes (pure host arithmetic; 0 where the call would be refused), caller-owned,
+ * 16-byte aligned, not shared by calls that may run concurrently; a larger one is fine.  It holds anything on entry: the shrink writes every partial
+ * the expand of the same (r, M, K) reads, so it needs no clearing; HQQ_ERR_WORKSPACE when it is missing or too small.
+ * The per-layer host arrays (A, B, y, N, r, scaling) are read during the call and not kept.  x must be 16-byte aligned; A, B, y to their element size.
+ * Nothing outside y_l[M, N_l] and the stated part of the workspace is written.
+ * The four symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_lora_decode_covers(int n_layers, const int64_t* N, const int64_t* r, int64_t M, int64_t K, int dtype, int a_dtype, int b_dtype);
+size_t hqq_hip_lora_decode_workspace_bytes(int n_layers, const int64_t* r, int64_t M, int64_t K);
+int hqq_hip_lora_shrink(int n_layers, const void* x, const void* const* A, const int64_t* r, int64_t M, int64_t K, int dtype, int lora_dtype,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int hqq_hip_lora_expand(int n_layers, const void* workspace, size_t workspace_bytes, const void* const* B, const float* scaling, void* const* y,
+                        const int64_t* N, const int64_t* r, int64_t M, int64_t K, int dtype, int lora_dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
