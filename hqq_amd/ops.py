@@ -1444,3 +1444,93 @@ def silu_mul(gate: Tensor, up: Tensor, out: Tensor | None = None) -> Tensor:
         rc = _C.lib().hqq_hip_silu_mul(_p(gate), _p(up), _p(out), gate.numel(), _dt(gate.dtype), _stream())
     _C.check(rc, "hqq_hip_silu_mul")
     return out
+
+
+# ---- the routed expert MLP of a mixture-of-experts block (csrc/moe.hip; include/hqq_hip.h hqq_hip_moe_*) ---------------------------------------------
+MOE_MAX_T = 16         # tokens one call takes (hqq_hip_moe_covers)
+# The largest token count at which HQQExperts takes the fused route on its own (fused=None).  The project's cut-off rule: the largest T <= MOE_MAX_T such that,
+# at it and at every smaller measured T, the two launches are at least 10 % ahead of the composed route on every shape, configuration and routing of
+# tools/moe_bench.py.  profiles/moe_summary.md: ahead everywhere up to T = 4; at T = 8 Mixtral's shape with every token on the same two experts is 1.10 (int4,
+# below the 10 %), at T = 16 the composed route wins there (0.57): the kernel rebuilds an expert's weights once per (token, slot), the composed route once per expert.
+# A graph capture cannot take the composed route (it reads the routing on the host): capture at most MOE_ROUTE_MAX_T tokens, or set HQQExperts.fused = True.
+MOE_ROUTE_MAX_T = 4
+
+
+def moe_covers(dtype, T: int, k: int, E: int, H: int, I: int, group_size, nbits, axis: int = 1) -> bool:
+    """what hqq_hip_moe_gate_up / hqq_hip_moe_down serve (pure host arithmetic): experts quantised along axis 1 at 4 or 2 bits, fp16 / bf16,
+    1..16 tokens, 1..8 experts per token, up to 256 experts, H and I multiples of 64, group_size a multiple of 16 that divides both"""
+    if axis != 1 or dtype not in (torch.float16, torch.bfloat16) or not group_size or nbits not in (8, 4, 3, 2, 1):
+        return False
+    return bool(_C.lib().hqq_hip_moe_covers(int(nbits), int(T), int(k), int(E), int(H), int(I), int(group_size), _DT[dtype]))
+
+
+def _moe_stack(who: str, layer, E: int, N: int, K: int, group_size: int, nbits: int, dtype):
+    """one role's stacks (W_q [E, ...] uint8, scale [E, ...], zero [E, ...]) checked against the sizes the kernel reads through raw pointers"""
+    W_q, scale, zero = layer
+    _dev(W_q, scale, zero)
+    groups = N * K // group_size
+    if W_q.dtype != torch.uint8 or W_q.numel() != E * N * K // PER[nbits] or scale.numel() != E * groups or zero.numel() != E * groups:
+        raise ValueError(f"hqq_amd: {who} takes stacks of {E} experts of a {N} x {K} layer: {E * N * K // PER[nbits]} packed bytes and {E * groups} scale / zero values")
+    if scale.dtype != dtype or zero.dtype != dtype:
+        raise TypeError("hqq_amd: x / scale / zero must share the compute dtype")
+    if not (W_q.is_contiguous() and scale.is_contiguous() and zero.is_contiguous()):
+        raise ValueError(f"hqq_amd: {who} takes dense (contiguous) expert stacks")
+    return W_q, scale, zero
+
+
+def _moe_routing(who: str, idx: Tensor, weights, T: int):
+    _dev(idx, weights)
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != T or not idx.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes top_k_index [T, k] int64, contiguous")
+    if weights is not None and (weights.dtype != torch.float32 or weights.shape != idx.shape or not weights.is_contiguous()):
+        raise ValueError(f"hqq_amd: {who} takes top_k_weights [T, k] float32, contiguous")
+    return int(idx.shape[1])
+
+
+def moe_gate_up(x: Tensor, idx: Tensor, gate, up, E: int, H: int, I: int, group_size: int, nbits: int, a: Tensor | None = None) -> Tensor:
+    """a[t, s] = act_fn(gate_e(x_t)) * up_e(x_t), e = idx[t, s] read on the device (hqq_hip_moe_gate_up).  gate / up: (W_q, scale, zero) stacks over the
+    E experts.  Returns a [T, k, I] (the caller's buffer when given).  The part of `a` that belongs to an id outside [0, E) is left unwritten."""
+    _dev(x)
+    if x.dim() != 2 or x.shape[1] != H or not x.is_contiguous():
+        raise ValueError(f"hqq_amd: moe_gate_up takes hidden_states [T, {H}], contiguous")
+    T = int(x.shape[0])
+    k = _moe_routing("moe_gate_up", idx, None, T)
+    g = _moe_stack("moe_gate_up", gate, E, I, H, group_size, nbits, x.dtype)
+    u = _moe_stack("moe_gate_up", up, E, I, H, group_size, nbits, x.dtype)
+    if a is None:
+        a = torch.empty((T, k, I), dtype=x.dtype, device=x.device)
+    elif a.dtype != x.dtype or a.numel() != T * k * I or not a.is_contiguous() or not a.is_cuda:
+        raise ValueError(f"hqq_amd: moe_gate_up's buffer must be [T, k, I] = [{T}, {k}, {I}] of the compute dtype, contiguous")
+    with torch.cuda.device(x.device):
+        rc = _C.lib().hqq_hip_moe_gate_up(int(nbits), _p(x), _p(idx), _p(g[0]), _p(g[1]), _p(g[2]), _p(u[0]), _p(u[1]), _p(u[2]), _p(a), T, k, int(E), int(H),
+                                          int(I), int(group_size), _dt(x.dtype), _stream())
+    _C.check(rc, "hqq_hip_moe_gate_up")
+    return a
+
+
+def moe_down(a: Tensor, idx: Tensor, weights: Tensor, down, E: int, H: int, I: int, group_size: int, nbits: int, out: Tensor | None = None) -> Tensor:
+    """out[t] = the token's slots s in ascending (expert, slot): out[t] += (down_e(a[t, s]) * weights[t, s]).to(dtype) (hqq_hip_moe_down): the combine in the
+    launch's epilogue, in the order of HF's loop over the experts hit.  Returns out [T, H]."""
+    _dev(a)
+    T = int(idx.shape[0]) if idx.dim() == 2 else -1
+    k = _moe_routing("moe_down", idx, weights, T)
+    if a.numel() != T * k * I or not a.is_contiguous():
+        raise ValueError(f"hqq_amd: moe_down takes a [T, k, I] = [{T}, {k}, {I}], contiguous")
+    d = _moe_stack("moe_down", down, E, H, I, group_size, nbits, a.dtype)
+    if out is None:
+        out = torch.empty((T, H), dtype=a.dtype, device=a.device)
+    elif out.dtype != a.dtype or out.numel() != T * H or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"hqq_amd: moe_down's output must be [T, H] = [{T}, {H}] of the compute dtype, contiguous")
+    with torch.cuda.device(a.device):
+        rc = _C.lib().hqq_hip_moe_down(int(nbits), _p(a), _p(idx), _p(weights), _p(d[0]), _p(d[1]), _p(d[2]), _p(out), T, k, int(E), int(H), int(I),
+                                       int(group_size), _dt(a.dtype), _stream())
+    _C.check(rc, "hqq_hip_moe_down")
+    return out
+
+
+def moe_forward(x: Tensor, idx: Tensor, weights: Tensor, gate, up, down, E: int, H: int, I: int, group_size: int, nbits: int,
+                a: Tensor | None = None, out: Tensor | None = None) -> Tensor:
+    """the experts module's forward in two launches (moe_gate_up, moe_down): no host read of the routing, nothing allocated but `out` and `a` when the
+    caller gives none — a step a graph can capture"""
+    a = moe_gate_up(x, idx, gate, up, E, H, I, group_size, nbits, a=a)
+    return moe_down(a, idx, weights, down, E, H, I, group_size, nbits, out=out)

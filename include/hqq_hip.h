@@ -499,6 +499,33 @@ int hqq_hip_lora_expand(int n_layers, const void* workspace, size_t workspace_by
                         const int64_t* N, const int64_t* r, int64_t M, int64_t K, int dtype, int lora_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The routed expert MLP of a mixture-of-experts block at decode sizes (csrc/moe.hip) — what transformers' fused experts modules compute
+ * (MixtralExperts.forward and its copies: gate_up_proj [E, 2I, H], down_proj [E, H, I], SiLU) over experts quantised along axis 1, in two launches
+ * without a host read of the routing.  With T the compute dtype (`dtype`), rnd = round to T, e = idx[t, s]:
+ *     hqq_hip_moe_gate_up   a[t, s, n] = rnd(rnd(silu32(rnd(x_t . Wg_e[n]))) * rnd(x_t . Wu_e[n]))                     a [T_, k, I], caller-owned
+ *     hqq_hip_moe_down      d[t, s, n] = rnd(a[t, s] . Wd_e[n]);  out[t, n]: acc = 0, then for the token's slots in ascending (e, s):
+ *                           acc = rnd(acc + rnd(fp32(d[t, s, n]) * w[t, s]))   (the product is an fp32 value first)      out [T_, H]
+ * — the order in which HF's loop over the experts hit and its index_add_ visit a token's slots.  Dot products accumulate in fp32 (fused multiply-adds
+ * in a fixed order that depends on K alone, then a fixed wave reduction): two calls give the same bits and a token's result does not depend on T_ or on
+ * the other tokens.  Weights are rebuilt exactly as hqq_hip_dequantize rebuilds them (the same two roundings in T), for any zero-points and scales.
+ *   x [T_, H] of T; idx [T_, k] int64 and weights [T_, k] float32 ON THE DEVICE; an id outside [0, E) contributes nothing and nothing is read for it
+ *   (its part of `a` is left unwritten).  Stacks, expert-major and dense: *_Wq [E, N K / per] bytes in the layout of hqq_hip_pack applied to each expert's
+ *   [N K / group_size, group_size] levels, *_scale / *_zero [E, N K / group_size] of T; gate and up: N = I, K = H; down: N = H, K = I.
+ * Covered: nbits 4 and 2; fp16 / bf16; 1 <= T_ <= 16, 1 <= k <= 8, 1 <= E <= 256; H % 64 == 0, I % 64 == 0 (both up to 65536); group_size % 16 == 0
+ * dividing H and I; per-expert strides that are 16-byte multiples.  Anything else (8 / 3 / 1 bits, fp32, other shapes): HQQ_ERR_UNSUPPORTED with a message,
+ * before anything is launched and without a GPU; axis 0, a bias and view_as_float have no argument here.  hqq_hip_moe_covers answers the same question (1 / 0).
+ * x, a, out and the stacks 16-byte aligned; idx and weights to their element size.  No workspace; nothing outside a[T_, k, I] / out[T_, H] is written.
+ * The three symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_moe_covers(int nbits, int64_t T_, int64_t k, int64_t E, int64_t H, int64_t I, int64_t group_size, int dtype);
+int hqq_hip_moe_gate_up(int nbits, const void* x, const void* idx, const void* gate_Wq, const void* gate_scale, const void* gate_zero,
+                        const void* up_Wq, const void* up_scale, const void* up_zero, void* a, int64_t T_, int64_t k, int64_t E, int64_t H,
+                        int64_t I, int64_t group_size, int dtype, void* stream);
+int hqq_hip_moe_down(int nbits, const void* a, const void* idx, const void* weights, const void* down_Wq, const void* down_scale,
+                     const void* down_zero, void* out, int64_t T_, int64_t k, int64_t E, int64_t H, int64_t I, int64_t group_size, int dtype,
+                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
