@@ -1260,20 +1260,27 @@ def token_prologue(tok: Tensor, pos: Tensor, embed: Tensor, h: Tensor, cos_tab=N
     token_prologue_batched(tok, _seq1(pos), embed, h, cos_tab, sin_tab, cos, sin, mask)
 
 
+def _rope_cache_args(who: str, q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor):
+    """what rope_cache_batched, qknorm_rope_cache_batched and bias_rope_cache_batched (`who`) all ask of their tensors: dense caches of the positions' batch and
+    q / k / v / q_out / cos / sin of matching extents.  Returns (B, head_dim, n_heads, n_kv_heads, cache_len), what the launches are given."""
+    B = _batch_of(pos, who)
+    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
+    _, n_kv, L, hd = k_cache.shape
+    if cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
+            k.numel() != B * n_kv * hd or v.numel() != k.numel() or q_out.numel() != q.numel():
+        raise ValueError(f"hqq_amd: {who} takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd]")
+    return B, hd, q.numel() // (B * hd), n_kv, L
+
+
 def rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
     """one token of B sequences in one launch: q_out [B, n_heads * hd] = rotary(q [B, n_heads * hd]) with cos / sin [B, hd]; rotary(k) and v ([B, n_kv * hd])
     go into row b of the caches [B, n_kv_heads, cache_len, head_dim] (HF's StaticCache tensors of batch B) at position pos[b]; a position outside the cache writes nothing"""
     _dev(q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
-    B = _batch_of(pos, "rope_cache_batched")
-    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
-        raise ValueError("hqq_amd: rope_cache_batched takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
-    hd = k_cache.shape[-1]
-    if cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
-            k.numel() != B * k_cache.shape[1] * hd or v.numel() != k.numel() or q_out.numel() != q.numel():
-        raise ValueError("hqq_amd: rope_cache_batched takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd]")
+    B, hd, n_heads, n_kv, L = _rope_cache_args("rope_cache_batched", q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
     with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_rope_cache_batched(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), B, _p(q_out), _p(k_cache), _p(v_cache), q.numel() // (B * hd),
-                                                 k_cache.shape[1], hd, k_cache.shape[2], _dt(q.dtype), _stream())
+        rc = _C.lib().hqq_hip_rope_cache_batched(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), B, _p(q_out), _p(k_cache), _p(v_cache), n_heads, n_kv, hd, L,
+                                                 _dt(q.dtype), _stream())
     _C.check(rc, "hqq_hip_rope_cache_batched")
     return q_out
 
@@ -1289,20 +1296,13 @@ def qknorm_rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, q_weight: Tensor,
     q is normalised with q_weight [hd] / q_eps, every head of k with k_weight [hd] / k_eps (Qwen3RMSNorm's roundings), then rotated; q_out, the caches, v and
     the positions as in rope_cache_batched.  head_dim 64 / 128 / 256, fp16 / bf16."""
     _dev(q, k, v, q_weight, k_weight, cos, sin, pos, k_cache, v_cache, q_out)
-    B = _batch_of(pos, "qknorm_rope_cache_batched")
-    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
-        raise ValueError("hqq_amd: qknorm_rope_cache_batched takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
-    hd = k_cache.shape[-1]
-    if cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
-            k.numel() != B * k_cache.shape[1] * hd or v.numel() != k.numel() or q_out.numel() != q.numel():
-        raise ValueError("hqq_amd: qknorm_rope_cache_batched takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd]")
+    B, hd, n_heads, n_kv, L = _rope_cache_args("qknorm_rope_cache_batched", q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
     if any(w.numel() != hd or not w.is_contiguous() for w in (q_weight, k_weight)) or \
             any(t.dtype != q.dtype for t in (k, v, q_weight, k_weight, cos, sin, k_cache, v_cache, q_out)):
         raise ValueError("hqq_amd: qknorm_rope_cache_batched takes dense norm weights of head_dim elements, and every tensor but the positions in q's dtype")
     with torch.cuda.device(q.device):
         rc = _C.lib().hqq_hip_qknorm_rope_cache_batched(_p(q), _p(k), _p(v), _p(q_weight), _p(k_weight), float(q_eps), float(k_eps), _p(cos), _p(sin), _p(pos), B,
-                                                        _p(q_out), _p(k_cache), _p(v_cache), q.numel() // (B * hd), k_cache.shape[1], hd, k_cache.shape[2],
-                                                        _dt(q.dtype), _stream())
+                                                        _p(q_out), _p(k_cache), _p(v_cache), n_heads, n_kv, hd, L, _dt(q.dtype), _stream())
     _C.check(rc, "hqq_hip_qknorm_rope_cache_batched")
     return q_out
 
@@ -1320,19 +1320,13 @@ def bias_rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, q_bias: Tensor, k_b
     shared by every sequence —, then q and k rotated; q_out, the caches and the positions as in rope_cache_batched.  Bit for bit gemv_grouped with the biases
     followed by rope_cache_batched.  Any even head_dim, fp16 / bf16."""
     _dev(q, k, v, q_bias, k_bias, v_bias, cos, sin, pos, k_cache, v_cache, q_out)
-    B = _batch_of(pos, "bias_rope_cache_batched")
-    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
-        raise ValueError("hqq_amd: bias_rope_cache_batched takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
-    hd = k_cache.shape[-1]
-    if cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
-            k.numel() != B * k_cache.shape[1] * hd or v.numel() != k.numel() or q_out.numel() != q.numel():
-        raise ValueError("hqq_amd: bias_rope_cache_batched takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd]")
+    B, hd, n_heads, n_kv, L = _rope_cache_args("bias_rope_cache_batched", q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
     if any(bias.numel() * B != t.numel() or not bias.is_contiguous() for bias, t in ((q_bias, q), (k_bias, k), (v_bias, v))) or \
             any(t.dtype != q.dtype for t in (k, v, q_bias, k_bias, v_bias, cos, sin, k_cache, v_cache, q_out)):
         raise ValueError("hqq_amd: bias_rope_cache_batched takes dense biases of one row of q / k / v each, and every tensor but the positions in q's dtype")
     with torch.cuda.device(q.device):
         rc = _C.lib().hqq_hip_bias_rope_cache_batched(_p(q), _p(k), _p(v), _p(q_bias), _p(k_bias), _p(v_bias), _p(cos), _p(sin), _p(pos), B, _p(q_out), _p(k_cache),
-                                                      _p(v_cache), q.numel() // (B * hd), k_cache.shape[1], hd, k_cache.shape[2], _dt(q.dtype), _stream())
+                                                      _p(v_cache), n_heads, n_kv, hd, L, _dt(q.dtype), _stream())
     _C.check(rc, "hqq_hip_bias_rope_cache_batched")
     return q_out
 

@@ -54,6 +54,15 @@ def eos_lengths(rows, eos_token_id, n: int) -> list:
     return out
 
 
+def opt_ins(**keywords) -> set:
+    """the decode-step opt-in keywords of GraphedGreedyDecoder and HFGenerator (axis0, qk_norm, qkv_bias, lora), each "model" or "fused": the names of those
+    set to "fused" (what llama_fused.resolve takes); ValueError naming the first keyword with another value"""
+    for name, value in keywords.items():
+        if value not in ("model", "fused"):
+            raise ValueError(f"{name}: 'model' or 'fused'")
+    return {name for name, value in keywords.items() if value == "fused"}
+
+
 class GraphedGreedyDecoder:
     """fused=True (default): a Llama-shaped model whose decoder linears are HQQLinearHIP layers decodes through hqq_amd.utils.llama_fused —
     RMSNorm (+ the residual adds), rotary + KV-cache write and SiLU * up as one HIP kernel each around the grouped GEMVs, HF's own attention
@@ -72,6 +81,7 @@ class GraphedGreedyDecoder:
     (default): the model's own forward, as before.  "fused" (opt-in): where llama_fused.supports_lora accepts the model, the fused step with one
     ops.lora_shrink + one ops.lora_expand behind each base launch that has adapted layers (`fused_lora`; `fused` stays the Llama flag), and
     generate_batch's batched step where supports_lora_batch accepts the batch.  An adapted model quantised along axis 0 needs axis0="fused" as well.
+    Which of these the model gets is decided once, by llama_fused.resolve, and kept as `variant` (None: the model's own forward); the fused_* flags read it.
     generate() and generate_batch() prefill differently and keep different caches, but advance through the same routine (_advance) over a small state
     holder: the device tensors tok / next_tok / pos that the captured graphs read and write, the step (None: the model's own forward), the dictionary
     its graphs are kept in with the key of an attended length in it, and the rule for that length."""
@@ -81,30 +91,11 @@ class GraphedGreedyDecoder:
                  qkv_bias: str = "model", lora: str = "model"):
         from transformers import StaticCache
         from . import llama_fused
-        if axis0 not in ("model", "fused"):
-            raise ValueError("axis0: 'model' or 'fused'")
-        if qk_norm not in ("model", "fused"):
-            raise ValueError("qk_norm: 'model' or 'fused'")
-        if qkv_bias not in ("model", "fused"):
-            raise ValueError("qkv_bias: 'model' or 'fused'")
-        if lora not in ("model", "fused"):
-            raise ValueError("lora: 'model' or 'fused'")
+        opted = opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)
         self.model = model.eval()
-        self.fused = bool(fused) and llama_fused.supports(model)
-        self.axis0 = axis0
-        self.fused_axis0 = bool(fused) and axis0 == "fused" and not self.fused and llama_fused.supports_axis0(model)
-        self.qk_norm = qk_norm
-        self.fused_qk_norm = bool(fused) and qk_norm == "fused" and not self.fused and not self.fused_axis0 and llama_fused.supports_qk_norm(model)
-        self.qkv_bias = qkv_bias
-        self.fused_qkv_bias = bool(fused) and qkv_bias == "fused" and not self.fused and not self.fused_axis0 and not self.fused_qk_norm and \
-            llama_fused.supports_qkv_bias(model)
-        self.lora = lora
-        self.fused_lora, self._lora_axis0 = False, False
-        if bool(fused) and lora == "fused" and not (self.fused or self.fused_axis0 or self.fused_qk_norm or self.fused_qkv_bias):
-            if llama_fused.supports_lora(model, axis0=False):
-                self.fused_lora = True
-            elif axis0 == "fused" and llama_fused.supports_lora(model, axis0=True):
-                self.fused_lora = self._lora_axis0 = True
+        self.axis0, self.qk_norm, self.qkv_bias, self.lora = axis0, qk_norm, qkv_bias, lora
+        # the llama_fused.StepVariant this model decodes through (resolve's precedence among the opt-ins), or None: the model's own forward
+        self.variant = llama_fused.resolve(model, opted) if fused else None
         self._fused_mod = llama_fused
         self.attention = attention   # "sdpa": HF's attention function (token-identical to model(...)); "hip": the decode-attention kernel (faster, within rounding)
         self.glue = glue             # "auto" / "folded": RMSNorm, residual adds and SiLU * up inside the GEMV launches (csrc/gemv_block.hip); "kernels": round 4's separate glue kernels
@@ -121,6 +112,13 @@ class GraphedGreedyDecoder:
         self._state = None     # the state holder of generate(): its tok / next_tok / pos are self.tok / .next_tok / .pos, its step self.step, its graphs self.graphs
         self._batch = {}       # B -> the state holder of generate_batch at B rows (with its B-row cache and its batch-1 prefill cache)
         self.batch_graphs = {} # (B, attended cache length) -> captured batched step
+
+    # `variant` as flags (what bench.py, the tools and the tests read): `fused` is plain Llama's, the others are the opt-in variants, one true at most
+    fused = property(lambda self: self.variant is not None and not any(self.variant.flags().values()))
+    fused_axis0 = property(lambda self: self.variant is not None and self.variant.axis0 and not self.variant.lora)   # (an adapted axis-0 model is fused_lora's)
+    fused_qk_norm = property(lambda self: self.variant is not None and self.variant.family == "qwen3")
+    fused_qkv_bias = property(lambda self: self.variant is not None and self.variant.family == "qwen2")
+    fused_lora = property(lambda self: self.variant is not None and self.variant.lora)
 
     @property
     def graph(self):
@@ -221,11 +219,10 @@ class GraphedGreedyDecoder:
             st["pos"].fill_(T)
         else:
             self.step = None
-            if self.fused or self.fused_axis0 or self.fused_qk_norm or self.fused_qkv_bias or self.fused_lora:
-                try:
+            if self.variant is not None:
+                try:   # (the plain axis-0 variant takes the separate glue kernels whatever `glue` says; with adapters `glue` goes through, and "folded" is refused)
                     self.step = self._fused_mod.FusedLlamaStep(self.model, self.cache, self.max_cache_len, attention=self.attention,
-                                                               glue="kernels" if self.fused_axis0 else self.glue, axis0=self.fused_axis0 or self._lora_axis0,
-                                                               qk_norm=self.fused_qk_norm, qkv_bias=self.fused_qkv_bias, lora=self.fused_lora)
+                                                               glue="kernels" if self.fused_axis0 else self.glue, **self.variant.flags())
                 except ValueError:   # a cache layout / attention configuration the fused step does not restate: the model's own forward serves
                     self.step = None
             self.graphs = {}
@@ -393,9 +390,7 @@ class GraphedGreedyDecoder:
     def _batch_state(self, B: int):
         """the kept state holder of generate_batch at B rows, or None when the batched step does not serve the model there"""
         fm = self._fused_mod
-        if not ((self.fused and fm.supports_batch(self.model, B)) or (self.fused_axis0 and fm.supports_axis0_batch(self.model, B)) or
-                (self.fused_qk_norm and fm.supports_qk_norm_batch(self.model, B)) or (self.fused_qkv_bias and fm.supports_qkv_bias_batch(self.model, B)) or
-                (self.fused_lora and fm.supports_lora_batch(self.model, B, self._lora_axis0))):
+        if self.variant is None or not fm.variant_supported(self.model, self.variant, B):
             return None
         cfg = self.model.config
         n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
@@ -403,8 +398,7 @@ class GraphedGreedyDecoder:
         cache = self._StaticCache(config=cfg, max_cache_len=self.max_cache_len)
         cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
         try:   # (without the decoder's `glue`: the batched step has the one-launch front and back wherever they apply)
-            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, axis0=self.fused_axis0 or self._lora_axis0,
-                                          qk_norm=self.fused_qk_norm, qkv_bias=self.fused_qkv_bias, lora=self.fused_lora)
+            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, **self.variant.flags())
         except ValueError:
             return None
         st = {"B": B, "cache": cache, "scratch": self._StaticCache(config=cfg, max_cache_len=self.max_cache_len), "step": step,
@@ -454,14 +448,7 @@ class HFGenerator:
                  qkv_bias: str = "model", lora: str = "model"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
-        if axis0 not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts an axis-0 model into the fused decode step)
-            raise ValueError("axis0: 'model' or 'fused'")
-        if qk_norm not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts a Qwen3 model into the fused decode step)
-            raise ValueError("qk_norm: 'model' or 'fused'")
-        if qkv_bias not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts a Qwen2 model into the fused decode step)
-            raise ValueError("qkv_bias: 'model' or 'fused'")
-        if lora not in ("model", "fused"):   # (GraphedGreedyDecoder's keyword: "fused" opts a model with un-merged LoRA adapters into the fused decode step)
-            raise ValueError("lora: 'model' or 'fused'")
+        opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)

@@ -5,38 +5,42 @@ buffer has B rows, every launch takes the B rows at once and the glue kernels ar
 the batch-1 kernel gives for sequence b alone).
 
 HF's decoder block around the seven linears is ~25 eager kernels per block at batch 1 (RMSNorm 5-6, rotary 8, cache update 2, SiLU * up 2,
-residual adds 2, ...): 79 % of a token once the linears are fused.  Here a block is
+residual adds 2, ...): 79 % of a token once the linears are fused.  Here a block is, with glue="kernels" (the only sequence at batch > 1, where the linears
+run at M = B),
     add_rmsnorm -> q|k|v (one grouped GEMV) -> rope_cache -> attention (HF's own attention function on the static cache) -> o ->
     add_rmsnorm (the residual add of o rides in it) -> gate|up (one grouped GEMV) -> silu_mul -> down (its residual add rides in the next block's add_rmsnorm)
-= 8 launches + the attention's (glue="kernels"; the only sequence at batch > 1, where the linears run at M = B, supports_batch).  Round 5 folds the glue
-into the launches either side of it (glue="folded", batch 1 only, the default where
-csrc/gemv_block.hip covers the model): q|k|v with the RMSNorm in its prologue -> rope_cache -> attention -> o with the residual add in its epilogue ->
-ONE paired gate|up layer (RMSNorm prologue, SiLU * up epilogue) -> down with the residual add in its epilogue; and with q / k in the rotary-paired row order
-(ops.rotary_pair_layout) the rotary embedding and the cache write ride in the q|k|v launch's epilogue too = 4 launches + the attention's.  The three glue kernels (csrc/block.hip) restate the HF modules rounding for rounding and the attention is
-HF's function on HF's cache tensors, so the step emits the same tokens as `model(...)` does on the same kernels — and as the same model
-under HQQBackend.PYTORCH_FORWARD does on the reference's arithmetic (tests/test_model_gpu.py).
+= 8 launches + the attention's; and with glue="folded" (one sequence, the default where csrc/gemv_block.hip covers the model)
+    q|k|v with the RMSNorm in its prologue -> rope_cache -> attention -> o with the residual add in its epilogue ->
+    ONE paired gate|up layer (RMSNorm prologue, SiLU * up epilogue) -> down with the residual add in its epilogue
+where, with q / k in the rotary-paired row order (ops.rotary_pair_layout), rope_cache rides in the q|k|v launch's epilogue too = 4 launches + the attention's.
+attention="hip" puts csrc/block.hip's decode-attention kernel in the attention function's place; in the Llama family it takes rope_cache into its launch.
+The glue kernels restate the HF modules rounding for rounding and the attention is HF's function on HF's cache tensors, so the step emits the same tokens
+as `model(...)` does on the same kernels — and as the same model under HQQBackend.PYTORCH_FORWARD does on the reference's arithmetic (tests/test_model_gpu.py).
 
-Models quantised along AXIS 0 (supports_axis0; opt-in through GraphedGreedyDecoder(axis0="fused")) take the glue="kernels" sequence with the axis-0 kernels:
-    add_rmsnorm -> q|k|v (ops.gemv_axis0_grouped) -> rope_cache -> attention -> o (ops.gemv_axis0) -> add_rmsnorm -> gate|up (ops.gemv_axis0_grouped with
-    SiLU * up in its reduce) -> down (ops.gemv_axis0)
-= 11 launches + the attention's (10 with attention="hip"), on the layers' own tensors.
+That is the base sequence.  WHICH model gets which sequence is one value, a StepVariant (family, axis0, lora); six exist, and each changes this much of it:
 
-Qwen3 models (supports_qk_norm; opt-in through GraphedGreedyDecoder(qk_norm="fused")) differ from Llama's block in ONE op: Qwen3Attention normalises every
-head of q and k (q_norm / k_norm, an RMSNorm over head_dim) before the rotary embedding.  ops.qknorm_rope_cache_batched (csrc/block.hip) takes rope_cache's place:
-    add_rmsnorm -> q|k|v -> qknorm_rope_cache -> attention -> ...   (glue="kernels", and every batch > 1), otherwise unchanged; folded glue: q|k|v with the
-    RMSNorm in its prologue -> qknorm_rope_cache -> attention -> o / gate|up pair / down folded as above
-= 5 launches + the attention's.  The rotary-paired q / k copies are not built: the head norm must see a whole head before the rotation.
+    variant               opt-in (decoder keyword)   what changes                                                                       per block, + attention
+    llama                 -                          nothing                                                                            8 kernels / 4 folded
+    llama + axis0         axis0                      q|k|v and gate|up through ops.gemv_axis0_grouped (SiLU * up in gate|up's reduce:   7, never folded
+                                                     no silu_mul), o / down through ops.gemv_axis0, on the layers' own tensors
+    qwen3                 qk_norm                    ops.qknorm_rope_cache_batched (per-head q_norm / k_norm, then rotary + cache) in   8 kernels / 5 folded
+                                                     rope_cache's place; no rotary-paired q / k (the norm must see a whole head first)
+    qwen2                 qkv_bias                   ops.bias_rope_cache_batched (q / k / v biases added, one rounding each, then       8 kernels / 5 folded
+                                                     rotary + cache) in rope_cache's place, behind a bias-free q|k|v launch; no
+                                                     rotary-paired q / k (their epilogue rotates before a bias could be added)
+    llama + lora          lora                       behind each of the four base launches that has adapted layers, one                 8 + 2 per adapted
+                                                     ops.lora_shrink + one ops.lora_expand; never folded                                group
+    llama + lora + axis0  lora and axis0             both of the above; an adapted gate|up runs without SiLU in its reduce, then        7 or 8, + 2 per
+                                                     silu_mul (the adapter terms come before SiLU)                                      adapted group
 
-Qwen2 / Qwen2.5 models (supports_qkv_bias; opt-in through GraphedGreedyDecoder(qkv_bias="fused")) differ from Llama's block in ONE thing too: q_proj, k_proj
-and v_proj carry a bias (o_proj and the MLP do not).  The q|k|v launch stays bias-free and ops.bias_rope_cache_batched (csrc/block.hip) takes rope_cache's
-place: it adds the three biases (one rounding each, the linears' own `out += bias`), then rotates and writes the cache:
-    add_rmsnorm -> q|k|v -> bias_rope_cache -> attention -> ...   (glue="kernels", and every batch > 1); folded glue: q|k|v with the RMSNorm in its
-    prologue -> bias_rope_cache -> attention -> o / gate|up pair / down folded as above
-= 5 launches + the attention's.  The rotary-paired q / k copies are not built here either: their epilogue rotates before a bias could be added.
+FAMILIES says what each family asks of an architecture, variant_supported(model, variant, batch) is the one coverage rule behind every supports_*
+function, and resolve() is the precedence by which the decoders pick a variant.  Nothing but plain llama is taken without being asked.
 
 Only what the step needs is taken from the model: module weights and the HF StaticCache's tensors are used in place (nothing is copied).
 """
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import torch
 from torch import Tensor
@@ -59,65 +63,69 @@ def _unwrap(layer):
     return _hip(layer.linear_layer) if _is_lora(layer) else _hip(layer)
 
 
-def arch_supported(model) -> bool:
-    """The allow-list half of supports(): the step restates LlamaDecoderLayer's arithmetic (transformers models/llama, models/mistral) and nothing
-    else.  Models that merely LOOK like it (same attribute names) would decode wrong tokens through that sequence without an error: Granite (residual /
-    embedding / logits / attention multipliers), Gemma (soft-capping, (1 + w) norms), Cohere, OLMo ...  Qwen3 (per-head q_norm / k_norm in front of the
-    rotary embedding) is refused HERE too — this predicate and the defaults built on it stay Llama's — and is served by a predicate of its own,
-    qk_norm_arch_supported, whose step (FusedLlamaStep(qk_norm=True)) has a kernel for that op; nothing takes it without being asked.  Qwen2 (biases on
-    q_proj / k_proj / v_proj) likewise: qkv_bias_arch_supported and FusedLlamaStep(qkv_bias=True)."""
+@dataclass(frozen=True)
+class Family:
+    """What one served model family asks of an architecture (_arch_ok walks a model once against it) and which step variants it admits."""
+    name: str
+    model_types: tuple    # config.model_type, an allow-list: models that merely LOOK like Llama (same attribute names) would decode wrong tokens without an error
+    qk_norm: bool         # per-head q_norm / k_norm on every attention module: required (1-D, head_dim elements, the compute dtype, an epsilon) / forbidden
+    qkv_bias: bool        # a bias on q_proj, k_proj and v_proj of every block and none on the other four linears: required / not looked at here (the config's
+                          # attention_bias / mlp_bias are refused in every family, and _structure refuses a bias on any quantised layer)
+    sliding: tuple        # which of the config's sliding-window signals refuse the model (a window on an attention MODULE refuses it in every family)
+    axis0: bool           # admits models quantised along axis 0 (the axis-0 kernels have no head-norm or bias sequence)
+    lora: bool            # admits un-merged LoRA adapters
+
+
+FAMILIES = {f.name: f for f in (
+    # LlamaDecoderLayer (transformers models/llama, models/mistral).  Their configs have neither use_sliding_window nor layer_types; a Mistral with a
+    # window says so in config.sliding_window, and that is the one signal looked at.
+    Family("llama", ("llama", "mistral"), qk_norm=False, qkv_bias=False, sliding=("sliding_window",), axis0=True, lora=True),
+    # Qwen3DecoderLayer (models/qwen3; not qwen3_moe): Llama's block with an RMSNorm over head_dim on every head of q and k before the rotary embedding.
+    # All three signals refuse (Qwen3Config clears sliding_window itself unless use_sliding_window is on).
+    Family("qwen3", ("qwen3",), qk_norm=True, qkv_bias=False, sliding=("sliding_window", "use_sliding_window", "layer_types"), axis0=False, lora=False),
+    # Qwen2DecoderLayer (models/qwen2): Llama's block with a bias on q_proj / k_proj / v_proj.  ONLY layer_types is looked at: Qwen2 / Qwen2.5 checkpoints
+    # carry a default config.sliding_window while use_sliding_window is off and every layer attends fully, so that field must not refuse them; and
+    # use_sliding_window alone changes nothing until max_window_layers makes some layer_types entry a sliding one.
+    Family("qwen2", ("qwen2",), qk_norm=False, qkv_bias=True, sliding=("layer_types",), axis0=False, lora=False),
+)}
+
+
+def _arch_ok(model, family: Family) -> bool:
+    """The allow-list half of variant_supported(): whether `model` is of `family`, i.e. its decoder block is the arithmetic the step restates and nothing
+    else.  Refused in every family: another model_type, soft-capping, config.attention_bias / mlp_bias, Granite-style multipliers (residual / embedding /
+    logits / attention) other than 1, attention sinks or a qk_norm module, a sliding window on an attention module, an activation other than SiLU.
+    What differs between the families is FAMILIES' fields."""
     try:
         cfg = model.config
-        if getattr(cfg, "model_type", None) not in ("llama", "mistral"):
+        if getattr(cfg, "model_type", None) not in family.model_types:
             return False
-        if getattr(cfg, "sliding_window", None) or getattr(cfg, "attn_logit_softcapping", None) or getattr(cfg, "final_logit_softcapping", None):
+        if getattr(cfg, "attn_logit_softcapping", None) or getattr(cfg, "final_logit_softcapping", None):
             return False
         if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False):
             return False
-        for odd in ("residual_multiplier", "embedding_multiplier", "logits_scaling", "attention_multiplier"):
-            if getattr(cfg, odd, None) not in (None, 1, 1.0):
-                return False
-        for blk in model.model.layers:
-            at = blk.self_attn
-            if any(hasattr(at, n) for n in ("q_norm", "k_norm", "qk_norm", "sinks")) or getattr(at, "sliding_window", None):
-                return False
-            if type(getattr(blk.mlp, "act_fn", None)).__name__ not in ("SiLUActivation", "SiLU"):
-                return False
-        return True
-    except AttributeError:
-        return False
-
-
-def _common_arch(cfg) -> bool:
-    """what both architecture predicates ask of a config: no biases, no soft-capping, no Granite-style multipliers"""
-    if getattr(cfg, "attn_logit_softcapping", None) or getattr(cfg, "final_logit_softcapping", None):
-        return False
-    if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False):
-        return False
-    return all(getattr(cfg, odd, None) in (None, 1, 1.0) for odd in ("residual_multiplier", "embedding_multiplier", "logits_scaling", "attention_multiplier"))
-
-
-def qk_norm_arch_supported(model) -> bool:
-    """arch_supported's counterpart for the step with qk_norm=True, which restates Qwen3DecoderLayer (transformers models/qwen3): Llama's block with
-    Qwen3Attention's q_norm / k_norm — an RMSNorm over head_dim on every head of q and k, before the rotary embedding.  model_type "qwen3" (not
-    qwen3_moe), no biases, full attention in every layer (no sliding window), SiLU, and on every block a q_norm and a k_norm with a 1-D weight of head_dim
-    elements in the compute dtype and a variance_epsilon."""
-    try:
-        cfg = model.config
-        if getattr(cfg, "model_type", None) != "qwen3" or not _common_arch(cfg):
+        if any(getattr(cfg, odd, None) not in (None, 1, 1.0) for odd in ("residual_multiplier", "embedding_multiplier", "logits_scaling", "attention_multiplier")):
             return False
-        if getattr(cfg, "sliding_window", None) or getattr(cfg, "use_sliding_window", False):
+        if any(getattr(cfg, sig, None) for sig in family.sliding if sig != "layer_types"):
             return False
-        if any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
+        if "layer_types" in family.sliding and any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
             return False
-        hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-        dt = model.model.norm.weight.dtype
+        if family.qk_norm:
+            hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+            dt = model.model.norm.weight.dtype
         for blk in model.model.layers:
             at = blk.self_attn
             if any(hasattr(at, n) for n in ("qk_norm", "sinks")) or getattr(at, "sliding_window", None):
                 return False
-            for nrm in (at.q_norm, at.k_norm):
-                if nrm.weight.dim() != 1 or nrm.weight.shape[0] != hd or nrm.weight.dtype != dt or not isinstance(nrm.variance_epsilon, (int, float)):
+            if family.qk_norm:
+                for nrm in (at.q_norm, at.k_norm):
+                    if nrm.weight.dim() != 1 or nrm.weight.shape[0] != hd or nrm.weight.dtype != dt or not isinstance(nrm.variance_epsilon, (int, float)):
+                        return False
+            elif hasattr(at, "q_norm") or hasattr(at, "k_norm"):
+                return False
+            if family.qkv_bias:
+                if any(getattr(at, n).bias is None for n in ("q_proj", "k_proj", "v_proj")):
+                    return False
+                if at.o_proj.bias is not None or any(getattr(blk.mlp, n).bias is not None for n in ("gate_proj", "up_proj", "down_proj")):
                     return False
             if type(getattr(blk.mlp, "act_fn", None)).__name__ not in ("SiLUActivation", "SiLU"):
                 return False
@@ -126,30 +134,58 @@ def qk_norm_arch_supported(model) -> bool:
         return False
 
 
+def arch_supported(model) -> bool:
+    """a Llama / Mistral architecture (FAMILIES["llama"]): what the plain step, its axis-0 and its LoRA variants restate.  Qwen3 and Qwen2 are refused HERE —
+    this predicate and the defaults built on it stay Llama's — and have predicates of their own"""
+    return _arch_ok(model, FAMILIES["llama"])
+
+
+def qk_norm_arch_supported(model) -> bool:
+    """a Qwen3 architecture (FAMILIES["qwen3"]): what the step with qk_norm=True restates"""
+    return _arch_ok(model, FAMILIES["qwen3"])
+
+
 def qkv_bias_arch_supported(model) -> bool:
-    """arch_supported's counterpart for the step with qkv_bias=True, which restates Qwen2DecoderLayer (transformers models/qwen2): Llama's block with a
-    bias on q_proj, k_proj and v_proj, and none on o_proj or the MLP.  model_type "qwen2", full attention in every layer (no sliding window), no head
-    norms or sinks, SiLU; the three attention projections of every block have a bias and the other four linears have none (what the biases must look
-    like on the quantised layers is _structure's question)."""
-    try:
-        cfg = model.config
-        if getattr(cfg, "model_type", None) != "qwen2" or not _common_arch(cfg):
-            return False
-        if any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
-            return False
-        for blk in model.model.layers:
-            at = blk.self_attn
-            if any(hasattr(at, n) for n in ("q_norm", "k_norm", "qk_norm", "sinks")) or getattr(at, "sliding_window", None):
-                return False
-            if any(getattr(at, n).bias is None for n in ("q_proj", "k_proj", "v_proj")):
-                return False
-            if at.o_proj.bias is not None or any(getattr(blk.mlp, n).bias is not None for n in ("gate_proj", "up_proj", "down_proj")):
-                return False
-            if type(getattr(blk.mlp, "act_fn", None)).__name__ not in ("SiLUActivation", "SiLU"):
-                return False
-        return True
-    except AttributeError:
-        return False
+    """a Qwen2 / Qwen2.5 architecture (FAMILIES["qwen2"]): what the step with qkv_bias=True restates (what the biases must look like on the quantised
+    layers is _structure's question)"""
+    return _arch_ok(model, FAMILIES["qwen2"])
+
+
+def _no_variant(**flags) -> ValueError:
+    return ValueError(f"hqq_amd: no fused decode step for {' with '.join(k + '=True' for k, on in flags.items() if on)}: axis0 and lora=True go with Llama / Mistral "
+                      "models only (an axis-0 or adapted Qwen decodes through the model's own forward), and no served architecture has both q/k/v biases and head norms")
+
+
+@dataclass(frozen=True)
+class StepVariant:
+    """Which sequence of launches a model decodes through: its family, whether its linears are quantised along axis 0, whether they still carry LoRA
+    adapters.  Six exist (VARIANTS): only the Llama family admits axis 0 or adapters.  The step and the decoders each hold one;
+    from_flags() / flags() translate from and to FusedLlamaStep's four boolean keywords."""
+    family: str = "llama"
+    axis0: bool = False
+    lora: bool = False
+
+    def __post_init__(self):
+        fam = FAMILIES.get(self.family)
+        if fam is None:
+            raise ValueError(f"hqq_amd: no family {self.family!r} ({', '.join(FAMILIES)})")
+        if (self.axis0 and not fam.axis0) or (self.lora and not fam.lora):
+            raise _no_variant(**self.flags())
+
+    @classmethod
+    def from_flags(cls, axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False) -> "StepVariant":
+        """the variant FusedLlamaStep's four keywords name; ValueError for the ten combinations that name none"""
+        if qk_norm and qkv_bias:
+            raise _no_variant(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)
+        return cls("qwen3" if qk_norm else "qwen2" if qkv_bias else "llama", bool(axis0), bool(lora))
+
+    def flags(self) -> dict:
+        """from_flags' inverse: the four booleans as FusedLlamaStep's keywords"""
+        return {"axis0": self.axis0, "qk_norm": self.family == "qwen3", "qkv_bias": self.family == "qwen2", "lora": self.lora}
+
+
+# every variant there is, in resolve()'s order of precedence
+VARIANTS = (StepVariant(), StepVariant(axis0=True), StepVariant("qwen3"), StepVariant("qwen2"), StepVariant(lora=True), StepVariant(axis0=True, lora=True))
 
 
 def _decoder_linears(model, lora: bool = False):
@@ -173,15 +209,15 @@ def _bias_ok(L, dt, wanted: bool) -> bool:
     return isinstance(b, Tensor) and b.dim() == 1 and b.shape[0] == L.out_features and b.is_contiguous() and b.dtype == dt and b.device == L.W_q.device
 
 
-def _structure(model, axis: int, arch=arch_supported, qkv_bias: bool = False, lora: bool = False):
-    """The structural half of supports(), supports_axis0*(), supports_qk_norm*() and supports_qkv_bias*(): an allow-listed architecture (`arch`:
-    arch_supported, qk_norm_arch_supported for the step with qk_norm=True, qkv_bias_arch_supported for the step with qkv_bias=True), fp16 or bf16, the
-    rotary / embedding / lm_head modules the step calls, every decoder linear an HQQLinearHIP of the compute dtype, quantised along `axis`, on the GPU, and
-    RMSNorm weights of that dtype with a multiple of 8 features.  Biases: by default no decoder linear may have one; with qkv_bias, q_proj, k_proj and v_proj
-    must each HAVE one — 1-D, dense, out_features elements, the compute dtype, the layer's device — and o_proj and the MLP still have none.
-    lora: the checks apply to the layers behind HQQLinearLoRA wrappers (what the wrappers themselves must look like is supports_lora's question).
-    Returns (dtype, _decoder_linears(model)), or None where the model is not of that shape; which kernels cover the layers is the callers' question."""
-    if not arch(model):
+def _structure(model, variant: StepVariant):
+    """The structural half of variant_supported(): an architecture of the variant's family (_arch_ok), fp16 or bf16, the rotary / embedding / lm_head modules
+    the step calls, every decoder linear an HQQLinearHIP of the compute dtype, quantised along the variant's axis, on the GPU, and RMSNorm weights of that
+    dtype with a multiple of 8 features.  Biases: no decoder linear may have one, except that in a family with qkv_bias q_proj, k_proj and v_proj must each
+    HAVE one — 1-D, dense, out_features elements, the compute dtype, the layer's device.  With lora the checks apply to the layers behind HQQLinearLoRA
+    wrappers (what the wrappers themselves must look like is _lora_wrappers_ok's question).
+    Returns (dtype, _decoder_linears(model)), or None where the model is not of that shape; which kernels cover the layers is the caller's question."""
+    family = FAMILIES[variant.family]
+    if not _arch_ok(model, family):
         return None
     try:
         inner = model.model
@@ -190,11 +226,11 @@ def _structure(model, axis: int, arch=arch_supported, qkv_bias: bool = False, lo
             return None
         if not hasattr(inner, "rotary_emb") or not hasattr(inner, "embed_tokens") or not hasattr(model, "lm_head"):
             return None
-        blocks = _decoder_linears(model, lora)
+        blocks = _decoder_linears(model, variant.lora)
         for blk, lin in zip(inner.layers, blocks):
-            if not all(isinstance(L, HQQLinearHIP) and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == axis for L in lin):
+            if not all(isinstance(L, HQQLinearHIP) and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == (0 if variant.axis0 else 1) for L in lin):
                 return None
-            if not all(_bias_ok(L, dt, qkv_bias and i < 3) for i, L in enumerate(lin)):
+            if not all(_bias_ok(L, dt, family.qkv_bias and i < 3) for i, L in enumerate(lin)):
                 return None
             for nrm in (blk.input_layernorm, blk.post_attention_layernorm):
                 if nrm.weight.dtype != dt or nrm.weight.shape[0] % 8:
@@ -202,57 +238,6 @@ def _structure(model, axis: int, arch=arch_supported, qkv_bias: bool = False, lo
         return dt, blocks
     except AttributeError:
         return None
-
-
-def supports(model) -> bool:
-    """a LlamaForCausalLM-shaped model of an allow-listed architecture (arch_supported) — model.model.layers[*].self_attn.{q,k,v,o}_proj,
-    .mlp.{gate,up,down}_proj, RMSNorm without bias —, fp16 or bf16, every decoder linear an HQQLinearHIP without bias, quantised along axis 1 (the folded
-    block kernels read axis-1 meta), whose group can share one launch"""
-    return _supports(model, arch_supported)
-
-
-def _supports(model, arch, qkv_bias: bool = False, lora: bool = False) -> bool:
-    """supports() / supports_qk_norm() / supports_qkv_bias(): _structure along axis 1 under the architecture predicate `arch`, and the kernel coverage of
-    the grouped launches"""
-    found = _structure(model, 1, arch, qkv_bias, lora)
-    if found is None:
-        return False
-    dt, blocks = found
-    for lin in blocks:
-        if len({(L.nbits, L.group_size, L.w3s) for L in lin[:3]}) != 1 or len({(L.nbits, L.group_size, L.w3s) for L in lin[4:6]}) != 1:
-            return False
-        if not ops.decode_covers(dt, 1, lin[0].out_features, lin[0].in_features, lin[0].group_size, lin[0].nbits) and not lin[0].w3s:
-            return False
-    return True
-
-
-def supports_axis0_batch(model, B: int) -> bool:
-    """supports_axis0(model) with every launch taking B activation rows (1 <= B <= ops.GEMV_MAX_M)"""
-    return _supports_axis0_batch(model, B)
-
-
-def _supports_axis0_batch(model, B: int, lora: bool = False) -> bool:
-    M = int(B)
-    found = _structure(model, 0, lora=lora) if 1 <= M <= ops.GEMV_MAX_M else None
-    if found is None:
-        return False
-    dt, blocks = found
-    for (q, k, v, o, g, u, d) in blocks:
-        if len({(L.nbits, L.group_size, L.in_features) for L in (q, k, v)}) != 1 or len({(L.nbits, L.group_size, L.in_features, L.out_features) for L in (g, u)}) != 1:
-            return False
-        if not ops.axis0_grouped_covers(dt, M, [L.out_features for L in (q, k, v)], q.in_features, q.group_size, q.nbits) or \
-                not ops.axis0_grouped_covers(dt, M, [g.out_features, u.out_features], g.in_features, g.group_size, g.nbits, ops.BLOCK_SILU):
-            return False
-        if not all(ops.decode_axis0_covers(dt, M, L.out_features, L.in_features, L.group_size, L.nbits) for L in (o, d)):
-            return False
-    return True
-
-
-def supports_axis0(model) -> bool:
-    """supports() for a model quantised along AXIS 0: an allow-listed architecture (arch_supported), fp16 or bf16, every decoder linear an HQQLinearHIP
-    with axis == 0 and no bias; q|k|v share (nbits, group_size) and gate|up share them with equal N, so that each group is ONE grouped launch
-    (ops.axis0_grouped_covers, gate|up with BLOCK_SILU); o and down on the single-layer kernel (ops.decode_axis0_covers)"""
-    return supports_axis0_batch(model, 1)
 
 
 def batch_covers(dtype, B: int, layers, opts: int = 0) -> bool:
@@ -273,51 +258,15 @@ def batch_covers(dtype, B: int, layers, opts: int = 0) -> bool:
     return True
 
 
-def supports_batch(model, B: int) -> bool:
-    """supports(model), and every decoder linear served by a fused decode kernel at B rows (batch_covers, with this module's default option bits)"""
-    return supports(model) and _batch_served(model, B)
-
-
-def supports_qk_norm(model) -> bool:
-    """supports() for a Qwen3 model (qk_norm_arch_supported in arch_supported's place: the same structural and kernel-coverage checks), whose head_dim
-    ops.qknorm_rope_cache_batched serves (64 / 128 / 256).  What FusedLlamaStep(qk_norm=True) takes; nothing takes it by default."""
-    if not _supports(model, qk_norm_arch_supported):
-        return False
-    cfg = model.config
-    return (getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads) in (64, 128, 256)
-
-
-def supports_qk_norm_batch(model, B: int) -> bool:
-    """supports_batch() for a Qwen3 model: supports_qk_norm(model), and every decoder linear served by a fused decode kernel at B rows"""
-    return supports_qk_norm(model) and _batch_served(model, B)
-
-
-def supports_qkv_bias(model) -> bool:
-    """supports() for a Qwen2 model (qkv_bias_arch_supported in arch_supported's place, biases admitted on q_proj / k_proj / v_proj and only there: otherwise
-    the same structural and kernel-coverage checks).  ops.bias_rope_cache_batched serves any even head_dim, so none is asked for here (attention="hip" has
-    its own check).  What FusedLlamaStep(qkv_bias=True) takes; nothing takes it by default."""
-    return _supports(model, qkv_bias_arch_supported, True)
-
-
-def supports_qkv_bias_batch(model, B: int) -> bool:
-    """supports_batch() for a Qwen2 model: supports_qkv_bias(model), and every decoder linear served by a fused decode kernel at B rows"""
-    return supports_qkv_bias(model) and _batch_served(model, B)
-
-
-def _batch_served(model, B: int, lora: bool = False) -> bool:
-    specs = [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lins in _decoder_linears(model, lora) for L in lins]
-    return batch_covers(model.model.norm.weight.dtype, B, specs, ops._default_opts)
-
-
 # the four places of a decoder block where adapters are served, as slices of (q, k, v, o, gate, up, down): each is one base launch, followed by one
 # lora_shrink + one lora_expand over the adapted layers among its members
 LORA_GROUPS = (("qkv", 0, 3), ("o", 3, 4), ("gu", 4, 6), ("d", 6, 7))
 
 
 def _lora_wrappers_ok(model, B: int) -> bool:
-    """the wrapper half of supports_lora_batch: at least one decoder linear is an HQQLinearLoRA; every wrapper has no bias and does not train one, no
-    active dropout, and lora_A [K, r] / lora_B [r, N] dense, of ONE dtype the kernels cover, on the layer's device; ops.lora_decode_covers holds for the
-    adapted layers of each group at B rows"""
+    """the wrapper half of variant_supported() for the lora variants: at least one decoder linear is an HQQLinearLoRA; every wrapper has no bias and does not
+    train one, no active dropout, and lora_A [K, r] / lora_B [r, N] dense, of ONE dtype the kernels cover, on the layer's device; ops.lora_decode_covers
+    holds for the adapted layers of each group at B rows"""
     from torch import nn
     try:
         dt = model.model.norm.weight.dtype
@@ -345,21 +294,102 @@ def _lora_wrappers_ok(model, B: int) -> bool:
         return False
 
 
-def supports_lora_batch(model, B: int, axis0: bool | None = None) -> bool:
-    """supports_batch (axis 1) or supports_axis0_batch (axis 0) asked of the layers BEHIND the HQQLinearLoRA wrappers — a decoder linear may be an
-    HQQLinearHIP or a wrapper whose linear_layer is one —, and the wrappers as _lora_wrappers_ok asks for them: any subset of the seven linears adapted,
-    with different ranks.  axis0: None — either axis; False / True — that one.  arch_supported architectures only (Llama, Mistral).  What
-    FusedLlamaStep(lora=True) takes; nothing takes it by default."""
-    B = int(B)
-    if B < 1 or not _lora_wrappers_ok(model, B):
+def variant_supported(model, variant: StepVariant, batch: int | None = None) -> bool:
+    """Whether the fused step of `variant` serves `model` — the one rule behind every supports_* function below.  batch=None asks about one sequence, an
+    integer about that many rows, and the two are NOT the same question at 1: on axis 1 without adapters, one sequence asks only that q|k|v and gate|up can
+    each share a grouped launch (the folded or grouped kernels then take the layers as they are), while B rows — 1 included — ask in addition for a decode
+    route of every linear at M = B (batch_covers); the axis-0 and the lora variants have no other sequence than the B-row one, so for them None means 1.
+    Everything else is common: _structure, then
+      axis 1: q|k|v share (nbits, group_size, layout) and so do gate|up; q is one the decode kernels cover, or 3-bit stream; qwen3: a head_dim
+      ops.qknorm_rope_cache_batched serves (64 / 128 / 256; ops.bias_rope_cache_batched serves any even one, so qwen2 asks for none);
+      axis 0: 1 <= B <= ops.GEMV_MAX_M; q|k|v share (nbits, group_size) and gate|up share them with equal N, so that each group is ONE grouped launch
+      (ops.axis0_grouped_covers, gate|up with BLOCK_SILU); o and down on the single-layer kernel (ops.decode_axis0_covers);
+      lora: the wrappers as _lora_wrappers_ok asks for them, any subset of the seven linears adapted, with different ranks."""
+    B = 1 if batch is None else int(batch)
+    if B < 1 or (variant.axis0 and B > ops.GEMV_MAX_M) or (variant.lora and not _lora_wrappers_ok(model, B)):
         return False
-    axis1 = axis0 in (None, False) and _supports(model, arch_supported, lora=True) and _batch_served(model, B, True)
-    return bool(axis1 or (axis0 in (None, True) and _supports_axis0_batch(model, B, True)))
+    found = _structure(model, variant)
+    if found is None:
+        return False
+    dt, blocks = found
+    if variant.axis0:
+        for (q, k, v, o, g, u, d) in blocks:
+            if len({(L.nbits, L.group_size, L.in_features) for L in (q, k, v)}) != 1 or len({(L.nbits, L.group_size, L.in_features, L.out_features) for L in (g, u)}) != 1:
+                return False
+            if not ops.axis0_grouped_covers(dt, B, [L.out_features for L in (q, k, v)], q.in_features, q.group_size, q.nbits) or \
+                    not ops.axis0_grouped_covers(dt, B, [g.out_features, u.out_features], g.in_features, g.group_size, g.nbits, ops.BLOCK_SILU):
+                return False
+            if not all(ops.decode_axis0_covers(dt, B, L.out_features, L.in_features, L.group_size, L.nbits) for L in (o, d)):
+                return False
+        return True
+    for lin in blocks:
+        if len({(L.nbits, L.group_size, L.w3s) for L in lin[:3]}) != 1 or len({(L.nbits, L.group_size, L.w3s) for L in lin[4:6]}) != 1:
+            return False
+        if not ops.decode_covers(dt, 1, lin[0].out_features, lin[0].in_features, lin[0].group_size, lin[0].nbits) and not lin[0].w3s:
+            return False
+    if variant.family == "qwen3":
+        cfg = model.config
+        if (getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads) not in (64, 128, 256):
+            return False
+    if batch is None and not variant.lora:
+        return True
+    return batch_covers(dt, B, [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lin in blocks for L in lin], ops._default_opts)
+
+
+def resolve(model, opted, batch: int | None = None) -> StepVariant | None:
+    """The variant a decoder gives `model`: the first of VARIANTS — llama, then axis 0, then qwen3, then qwen2, then lora on axis 1, then lora on axis 0 — that
+    is opted into and that variant_supported accepts (at `batch`), or None: the model's own forward.  `opted` holds the opt-ins among "axis0", "qk_norm",
+    "qkv_bias", "lora"; a variant is opted into when every flag it sets is (plain llama sets none: always; lora on axis 0 needs both)."""
+    opted = set(opted)
+    for variant in VARIANTS:
+        if all(k in opted for k, on in variant.flags().items() if on) and variant_supported(model, variant, batch):
+            return variant
+    return None
+
+
+def supports(model) -> bool:
+    """one sequence of a Llama / Mistral model quantised along axis 1: what the decoders take by default"""
+    return variant_supported(model, StepVariant())
+
+
+def supports_batch(model, B: int) -> bool:
+    return variant_supported(model, StepVariant(), B)
+
+
+def supports_axis0(model) -> bool:
+    """supports() for a model quantised along AXIS 0"""
+    return variant_supported(model, StepVariant(axis0=True))
+
+
+def supports_axis0_batch(model, B: int) -> bool:
+    return variant_supported(model, StepVariant(axis0=True), B)
+
+
+def supports_qk_norm(model) -> bool:
+    """supports() for a Qwen3 model: what FusedLlamaStep(qk_norm=True) takes"""
+    return variant_supported(model, StepVariant("qwen3"))
+
+
+def supports_qk_norm_batch(model, B: int) -> bool:
+    return variant_supported(model, StepVariant("qwen3"), B)
+
+
+def supports_qkv_bias(model) -> bool:
+    """supports() for a Qwen2 / Qwen2.5 model: what FusedLlamaStep(qkv_bias=True) takes"""
+    return variant_supported(model, StepVariant("qwen2"))
+
+
+def supports_qkv_bias_batch(model, B: int) -> bool:
+    return variant_supported(model, StepVariant("qwen2"), B)
 
 
 def supports_lora(model, axis0: bool | None = None) -> bool:
-    """supports() (axis 1) or supports_axis0() (axis 0) for a model whose decoder linears still carry their LoRA adapters: supports_lora_batch at one row"""
+    """supports() / supports_axis0() for a model whose decoder linears still carry their LoRA adapters.  axis0: None — either axis; False / True — that one"""
     return supports_lora_batch(model, 1, axis0)
+
+
+def supports_lora_batch(model, B: int, axis0: bool | None = None) -> bool:
+    return any(variant_supported(model, StepVariant(axis0=a, lora=True), B) for a in (False, True) if axis0 in (None, a))
 
 
 def _gopts(Ls) -> int:
@@ -382,23 +412,15 @@ class FusedLlamaStep:
         paired layout); "kernels" — round 4's separate glue kernels (9 launches per block); "auto": folded where hqq_hip_gemv_block covers the model.
         batch: the number of sequences.  Beyond 1 the model must be one supports_batch (supports_axis0_batch with axis0) accepts at that many rows;
         the folded launches serve one activation row, so a batch takes the separate glue kernels whatever `glue` allows.
-        qk_norm: the model is a Qwen3 (supports_qk_norm; supports_qk_norm_batch beyond one sequence): ops.qknorm_rope_cache_batched — the per-head q_norm /
-        k_norm, then the rotary embedding and the cache write — takes rope_cache's place after q|k|v, and attention="hip" attends on its rotated q_out
-        (ops.attn_decode_batched).  The folded glue keeps q|k|v in the natural row order (the norm comes before the rotation): 5 launches + attention.
-        qkv_bias: the model is a Qwen2 (supports_qkv_bias; supports_qkv_bias_batch beyond one sequence): the q|k|v launch stays bias-free and
-        ops.bias_rope_cache_batched — the three biases added, then the rotary embedding and the cache write — takes rope_cache's place, with either attention
-        on its rotated q_out as for qk_norm; folded glue: 5 launches + attention.  Not together with axis0 or qk_norm.
-        lora: the model's decoder linears still carry LoRA adapters (supports_lora; supports_lora_batch beyond one sequence; with axis0 for a model
-        quantised along axis 0).  The step is the glue="kernels" sequence on the layers behind the wrappers, and after each of the four base launches —
-        q|k|v, o, gate|up, down — ONE ops.lora_shrink + ONE ops.lora_expand add the adapter terms of that group's adapted layers to the launch's
-        outputs, on the input the launch read: o's on self.delta before the residual add, gate|up's before SiLU (axis 0: the grouped launch then runs
-        without BLOCK_SILU and ops.silu_mul follows).  A group without an adapter launches nothing extra.  `scaling` is read once, here.  Not with
-        glue="folded", qk_norm or qkv_bias."""
-        # axis0: the model's linears are quantised along axis 0 (supports_axis0).  The step is the glue="kernels" sequence with q|k|v and gate|up through
-        # ops.gemv_axis0_grouped (gate|up's reduce applies SiLU * up: no silu_mul launch) and o / down through ops.gemv_axis0, on the layers' own tensors
-        # (nothing re-laid out); the folded launches read axis-1 meta and are never taken.
+        axis0, qk_norm, qkv_bias, lora: together they name the StepVariant (self.variant) whose sequence the step runs — the table in the module's docstring;
+        a combination that names none is a ValueError, and so is a model that variant_supported refuses for it at `batch` rows.  axis0 and lora take the
+        separate glue kernels (the folded launches read axis-1 meta and serve no adapters: glue="folded" is refused); qk_norm and qkv_bias fold all but their
+        rotary-and-cache launch, and with attention="hip" the kernel attends on that launch's rotated q_out (ops.attn_decode_batched).  lora: the adapter
+        terms are added on the input the base launch read — o's on self.delta before the residual add, gate|up's before SiLU — and `scaling` is read once, here."""
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
+        self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)
+        self.axis0, self.qk_norm, self.qkv_bias, self.lora = (variant.flags()[k] for k in ("axis0", "qk_norm", "qkv_bias", "lora"))
         self.model = model
         inner = model.model
         self.inner = inner
@@ -420,32 +442,22 @@ class FusedLlamaStep:
         self.attention = attention
         if glue not in ("auto", "folded", "kernels"):
             raise ValueError("glue: 'auto', 'folded' or 'kernels'")
-        self.axis0 = bool(axis0)
-        self.qk_norm = bool(qk_norm)
-        self.qkv_bias = bool(qkv_bias)
-        self.lora = bool(lora)
-        if self.lora and (glue == "folded" or self.qk_norm or self.qkv_bias):
-            raise ValueError("hqq_amd: lora=True takes the separate glue kernels of a Llama / Mistral model: not with glue='folded', qk_norm or qkv_bias")
-        if self.lora and not supports_lora_batch(model, B, self.axis0):
-            raise ValueError(f"hqq_amd: lora=True needs a model with LoRA adapters on decoder linears the fused decode kernels serve at {B} rows "
-                             f"(supports_lora / supports_lora_batch{', axis 0' if self.axis0 else ''})")
-        if self.qkv_bias and (self.axis0 or self.qk_norm):
-            raise ValueError("hqq_amd: qkv_bias=True goes with neither axis0 nor qk_norm (an axis-0 Qwen2 decodes through the model's own forward; no served "
-                             "architecture has both biases and head norms)")
-        if self.qk_norm and self.axis0:
-            raise ValueError("hqq_amd: qk_norm=True serves models quantised along axis 1 (an axis-0 Qwen3 decodes through the model's own forward)")
-        if self.qk_norm and not (supports_qk_norm(model) if B == 1 else supports_qk_norm_batch(model, B)):
-            raise ValueError(f"hqq_amd: qk_norm=True needs a Qwen3 model whose decoder linears the fused decode kernels serve at {B} rows "
-                             "(supports_qk_norm / supports_qk_norm_batch)")
-        if self.qkv_bias and not (supports_qkv_bias(model) if B == 1 else supports_qkv_bias_batch(model, B)):
-            raise ValueError(f"hqq_amd: qkv_bias=True needs a Qwen2 model whose decoder linears the fused decode kernels serve at {B} rows "
-                             "(supports_qkv_bias / supports_qkv_bias_batch)")
-        # (a single sequence of an axis-1 model is not asked: its callers ask supports(), and models construct here that it refuses)
-        if (B != 1 or self.axis0) and not self.qk_norm and not self.qkv_bias and not self.lora and not (supports_axis0_batch(model, B) if self.axis0 else supports_batch(model, B)):
-            raise ValueError(f"hqq_amd: the fused decode kernels do not serve every decoder linear of this model at {B} rows "
-                             f"({'axis0=True: supports_axis0_batch' if self.axis0 else 'supports_batch'})")
-        if self.axis0 and glue == "folded":
-            raise ValueError("hqq_amd: glue='folded' reads axis-1 meta; an axis-0 model takes the separate glue kernels")
+        if glue == "folded" and (self.lora or self.axis0):
+            raise ValueError(f"hqq_amd: glue='folded' reads axis-1 meta and serves no adapters: {'lora=True' if self.lora else 'axis0=True'} takes the separate glue kernels")
+        # (a single sequence of an axis-1 Llama is not asked: its callers ask supports(), and models construct here that it refuses)
+        if (variant != StepVariant() or B != 1) and not variant_supported(model, variant, None if B == 1 else B):
+            on = [k for k, v in variant.flags().items() if v]
+            fn = "supports" + ("_lora" if self.lora else "_" + on[0] if on else "")
+            raise ValueError(f"hqq_amd: {', '.join(k + '=True' for k in on) or 'a batch'} needs a model of the {variant.family} family whose decoder linears "
+                             f"the fused decode kernels serve at {B} rows ({fn} / {fn}_batch)")
+        # the rotary-and-cache launch of the family, by name (looked up in ops at every call), and what it takes of block b between v and cos
+        self._rope_cache, self._rope_extra = {
+            "llama": ("rope_cache_batched", lambda b: ()),
+            # Qwen3: the heads of q and k normalised, rotated and cached in one launch
+            "qwen3": ("qknorm_rope_cache_batched", lambda b: (b["attn"].q_norm.weight, b["attn"].k_norm.weight, b["attn"].q_norm.variance_epsilon, b["attn"].k_norm.variance_epsilon)),
+            # Qwen2: the projections' biases added to the bias-free q|k|v, then rotated and cached, one launch
+            "qwen2": ("bias_rope_cache_batched", lambda b: b["qkv_bias"]),
+        }[variant.family]
         blocks = _decoder_linears(model, self.lora)
         wrappers = _decoder_wrappers(model) if self.lora else [[None] * 7 for _ in blocks]
         can_fold = not self.lora and all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
@@ -496,7 +508,7 @@ class FusedLlamaStep:
                         lora_ws_bytes = max(lora_ws_bytes, ops.lora_decode_workspace_bytes(B, ad[0][1].shape[0], [a[1].shape[1] for a in ad]))
             if self.qkv_bias:   # the three layers' own bias tensors (static addresses under graph capture); the launch records above stay bias-free
                 self.blocks[-1]["qkv_bias"] = (q.bias, k.bias, v.bias)
-            if self.folded and attention != "hip" and self.hd % 2 == 0 and not self.qk_norm and not self.qkv_bias:
+            if self.folded and attention != "hip" and self.hd % 2 == 0 and variant.family == "llama":
                 # q and k in the rotary-paired row order (ops.rotary_pair_layout): the q|k|v launch's epilogue applies the rotary embedding and writes the cache
                 # (the kernel attention folds the rotary embedding into the attention launch instead: it keeps the natural order)
                 def _sub_ok(t, L_):
@@ -555,7 +567,7 @@ class FusedLlamaStep:
         kv_len (host integer > the LARGEST position, default the whole cache): HF's attention function attends over the first kv_len cache positions only
         (each row masked beyond its own position) — its cost follows the length it is given, so a caller that knows the positions passes a bucket just
         above them; the kernel attention takes its split count from it"""
-        inner, B, h = self.inner, self.B, self.h
+        inner, B, h, variant = self.inner, self.B, self.h, self.variant
         # (the positions themselves are device memory — the step is graph-replayed —: the kernels that index the cache with them skip their
         #  writes beyond the cache's last slot, csrc/block.hip; callers that know the positions on the host check them there, generation.py)
         if self.one_launch_front:   # embedding rows, rotary table rows and the causal masks in ONE launch (csrc/block.hip: copies and compares, the same bits as the ops below)
@@ -589,24 +601,16 @@ class FusedLlamaStep:
                 ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
                 self._grouped(b, "qkv", [b["q"], b["k"], b["v"]])
                 self._adapters(b, "qkv", self.xn, [b["q"], b["k"], b["v"]])
-            if self.qk_norm or self.qkv_bias:
-                if self.qk_norm:   # Qwen3: the heads of q and k normalised, rotated and cached in one launch; either attention then reads the rotated q_out
-                    qn, kn = at.q_norm, at.k_norm
-                    ops.qknorm_rope_cache_batched(b["q"], b["k"], b["v"], qn.weight, kn.weight, qn.variance_epsilon, kn.variance_epsilon, cos, sin, pos,
-                                                  b["kc"], b["vc"], b["qr"])
-                else:   # Qwen2: the projections' biases added to the bias-free q|k|v, then rotated and cached, one launch
-                    ops.bias_rope_cache_batched(b["q"], b["k"], b["v"], *b["qkv_bias"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
+            if self.attention == "hip" and variant.family == "llama":   # rotary + cache write + attention: one launch
+                att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
+                                                   workspace=self.attn_ws.get(splits))
+            else:
+                if not (self.folded and "qkv_rope" in b):   # (the q|k|v epilogue has not rotated and cached already); either attention then reads the rotated qr
+                    getattr(ops, self._rope_cache)(b["q"], b["k"], b["v"], *self._rope_extra(b), cos, sin, pos, b["kc"], b["vc"], b["qr"])
                 if self.attention == "hip":
                     att = ops.attn_decode_batched(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
                 else:
                     att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :, :kvl], b["vc"][:, :, :kvl], mask, dropout=0.0, scaling=at.scaling)
-            elif self.attention == "hip":   # rotary + cache write + attention: one launch
-                att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
-                                                   workspace=self.attn_ws.get(splits))
-            else:
-                if not (self.folded and "qkv_rope" in b):
-                    ops.rope_cache_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
-                att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :, :kvl], b["vc"][:, :, :kvl], mask, dropout=0.0, scaling=at.scaling)
             o, d = b["o"], b["d"]
             if self.folded:
                 # o: h += o(att) in the epilogue; gate|up: RMSNorm prologue + silu(gate) * up epilogue on the paired layer; down: h += down(a) in the epilogue
