@@ -89,6 +89,9 @@ SYMBOLS = {
     "hqq_hip_moe_covers": (_i32, [_i32, _i64, _i64, _i64, _i64, _i64, _i64, _i32]),
     "hqq_hip_moe_gate_up": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
     "hqq_hip_moe_down": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
+    # the router in front of them, one launch (csrc/moe_router.hip; added at ABI 9 without a bump: nothing that existed changed)
+    "hqq_hip_moe_router_covers": (_i32, [_i64, _i64, _i64, _i64, _i32]),
+    "hqq_hip_moe_router": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1522,6 +1522,42 @@ def moe_down(a: Tensor, idx: Tensor, weights: Tensor, down, E: int, H: int, I: i
     return out
 
 
+def moe_router_covers(dtype, T: int, k: int, E: int, H: int) -> bool:
+    """what hqq_hip_moe_router serves (pure host arithmetic): fp16 / bf16, 1..16 rows, 1..8 experts per token, k..256 experts, H a multiple of 8 up to 65536"""
+    if dtype not in (torch.float16, torch.bfloat16):
+        return False
+    return bool(_C.lib().hqq_hip_moe_router_covers(int(T), int(k), int(E), int(H), _DT[dtype]))
+
+
+def moe_router(x: Tensor, weight: Tensor, k: int, renorm: bool = True, round_weights: bool = False, idx: Tensor | None = None, weights: Tensor | None = None,
+               logits: Tensor | None = None):
+    """a router's whole forward in one launch (hqq_hip_moe_router): logits = x @ weight.T rounded to the compute dtype, softmax in fp32, the k largest LOGITS
+    in descending order with equal logits by ascending expert id (this library's own rule: torch.topk leaves the order among equal values open), their
+    probabilities, divided by their sum with `renorm` (Mixtral always; Qwen3-MoE's norm_topk_prob) and rounded to the compute dtype with `round_weights`
+    (Qwen3-MoE).  x [T, H] and weight [E, H] dense, of one dtype.  Returns (idx [T, k] int64, weights [T, k] float32) — what moe_gate_up / moe_down read —
+    in the caller's buffers when given; `logits` [T, E] of the compute dtype is filled when given."""
+    _dev(x, weight, idx, weights, logits)
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1] or not x.is_contiguous() or not weight.is_contiguous():
+        raise ValueError("hqq_amd: moe_router takes hidden_states [T, H] and a router weight [E, H], contiguous")
+    if weight.dtype != x.dtype:
+        raise TypeError("hqq_amd: x and the router weight must share the compute dtype")
+    T, H, E, k = int(x.shape[0]), int(x.shape[1]), int(weight.shape[0]), int(k)
+    if idx is None:
+        idx = torch.empty((T, k), dtype=torch.int64, device=x.device)
+    if weights is None:
+        weights = torch.empty((T, k), dtype=torch.float32, device=x.device)
+    if tuple(idx.shape) != (T, k) or tuple(weights.shape) != (T, k):
+        raise ValueError(f"hqq_amd: moe_router's idx and weights must be [T, k] = [{T}, {k}]")
+    _moe_routing("moe_router", idx, weights, T)
+    if logits is not None and (logits.dtype != x.dtype or tuple(logits.shape) != (T, E) or not logits.is_contiguous()):
+        raise ValueError(f"hqq_amd: moe_router's logits must be [T, E] = [{T}, {E}] of the compute dtype, contiguous")
+    with torch.cuda.device(x.device):
+        rc = _C.lib().hqq_hip_moe_router(_p(x), _p(weight), _p(idx), _p(weights), _p(logits), T, k, E, H, int(bool(renorm)), int(bool(round_weights)),
+                                         _dt(x.dtype), _stream())
+    _C.check(rc, "hqq_hip_moe_router")
+    return idx, weights
+
+
 def moe_forward(x: Tensor, idx: Tensor, weights: Tensor, gate, up, down, E: int, H: int, I: int, group_size: int, nbits: int,
                 a: Tensor | None = None, out: Tensor | None = None) -> Tensor:
     """the experts module's forward in two launches (moe_gate_up, moe_down): no host read of the routing, nothing allocated but `out` and `a` when the

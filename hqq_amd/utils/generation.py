@@ -55,7 +55,7 @@ def eos_lengths(rows, eos_token_id, n: int) -> list:
 
 
 def opt_ins(**keywords) -> set:
-    """the decode-step opt-in keywords of GraphedGreedyDecoder and HFGenerator (axis0, qk_norm, qkv_bias, lora), each "model" or "fused": the names of those
+    """the decode-step opt-in keywords of GraphedGreedyDecoder and HFGenerator (axis0, qk_norm, qkv_bias, lora, moe), each "model" or "fused": the names of those
     set to "fused" (what llama_fused.resolve takes); ValueError naming the first keyword with another value"""
     for name, value in keywords.items():
         if value not in ("model", "fused"):
@@ -81,6 +81,10 @@ class GraphedGreedyDecoder:
     (default): the model's own forward, as before.  "fused" (opt-in): where llama_fused.supports_lora accepts the model, the fused step with one
     ops.lora_shrink + one ops.lora_expand behind each base launch that has adapted layers (`fused_lora`; `fused` stays the Llama flag), and
     generate_batch's batched step where supports_lora_batch accepts the batch.  An adapted model quantised along axis 0 needs axis0="fused" as well.
+    moe: what a Mixtral or Qwen3-MoE model whose experts are HQQExperts decodes through.  "model" (default): the model's own forward, as before.  "fused"
+    (opt-in): where llama_fused.supports_moe accepts the model, the fused step with ops.moe_router, ops.moe_gate_up and ops.moe_down in the MLP's place
+    (`fused_moe`; `fused` stays the Llama flag), and generate_batch's batched step where supports_moe_batch accepts the batch (otherwise the prompts decode one
+    after another).  A Qwen3-MoE model needs qk_norm="fused" as well.
     Which of these the model gets is decided once, by llama_fused.resolve, and kept as `variant` (None: the model's own forward); the fused_* flags read it.
     generate() and generate_batch() prefill differently and keep different caches, but advance through the same routine (_advance) over a small state
     holder: the device tensors tok / next_tok / pos that the captured graphs read and write, the step (None: the model's own forward), the dictionary
@@ -88,12 +92,12 @@ class GraphedGreedyDecoder:
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
-                 qkv_bias: str = "model", lora: str = "model"):
+                 qkv_bias: str = "model", lora: str = "model", moe: str = "model"):
         from transformers import StaticCache
         from . import llama_fused
-        opted = opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)
+        opted = opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
         self.model = model.eval()
-        self.axis0, self.qk_norm, self.qkv_bias, self.lora = axis0, qk_norm, qkv_bias, lora
+        self.axis0, self.qk_norm, self.qkv_bias, self.lora, self.moe = axis0, qk_norm, qkv_bias, lora, moe
         # the llama_fused.StepVariant this model decodes through (resolve's precedence among the opt-ins), or None: the model's own forward
         self.variant = llama_fused.resolve(model, opted) if fused else None
         self._fused_mod = llama_fused
@@ -116,9 +120,10 @@ class GraphedGreedyDecoder:
     # `variant` as flags (what bench.py, the tools and the tests read): `fused` is plain Llama's, the others are the opt-in variants, one true at most
     fused = property(lambda self: self.variant is not None and not any(self.variant.flags().values()))
     fused_axis0 = property(lambda self: self.variant is not None and self.variant.axis0 and not self.variant.lora)   # (an adapted axis-0 model is fused_lora's)
-    fused_qk_norm = property(lambda self: self.variant is not None and self.variant.family == "qwen3")
+    fused_qk_norm = property(lambda self: self.variant is not None and self.variant.family == "qwen3")   # (a Qwen3-MoE model is fused_moe's)
     fused_qkv_bias = property(lambda self: self.variant is not None and self.variant.family == "qwen2")
     fused_lora = property(lambda self: self.variant is not None and self.variant.lora)
+    fused_moe = property(lambda self: self.variant is not None and self.variant.flags().get("moe", False))
 
     @property
     def graph(self):
@@ -445,10 +450,10 @@ class HFGenerator:
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
                  compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
-                 qkv_bias: str = "model", lora: str = "model"):
+                 qkv_bias: str = "model", lora: str = "model", moe: str = "model"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
-        opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
+        opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -461,7 +466,7 @@ class HFGenerator:
         self.use_graph = compile is not None
         self.compile_options = compile_options
         self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
-                                            qkv_bias=qkv_bias, lora=lora)
+                                            qkv_bias=qkv_bias, lora=lora, moe=moe)
         self.init()
 
     @staticmethod

@@ -17,7 +17,7 @@ attention="hip" puts csrc/block.hip's decode-attention kernel in the attention f
 The glue kernels restate the HF modules rounding for rounding and the attention is HF's function on HF's cache tensors, so the step emits the same tokens
 as `model(...)` does on the same kernels — and as the same model under HQQBackend.PYTORCH_FORWARD does on the reference's arithmetic (tests/test_model_gpu.py).
 
-That is the base sequence.  WHICH model gets which sequence is one value, a StepVariant (family, axis0, lora); six exist, and each changes this much of it:
+That is the base sequence.  WHICH model gets which sequence is one value, a StepVariant (family, axis0, lora); eight exist, and each changes this much of it:
 
     variant               opt-in (decoder keyword)   what changes                                                                       per block, + attention
     llama                 -                          nothing                                                                            8 kernels / 4 folded
@@ -32,6 +32,10 @@ That is the base sequence.  WHICH model gets which sequence is one value, a Step
                                                      ops.lora_shrink + one ops.lora_expand; never folded                                group
     llama + lora + axis0  lora and axis0             both of the above; an adapted gate|up runs without SiLU in its reduce, then        7 or 8, + 2 per
                                                      silu_mul (the adapter terms come before SiLU)                                      adapted group
+    mixtral               moe                        ops.moe_router (logits, softmax, top-k and renormalisation in one launch, into     8, never folded
+                                                     per-block idx / weights), ops.moe_gate_up and ops.moe_down on the HQQExperts
+                                                     stacks in the place of gate|up, silu_mul and down
+    qwen3_moe             moe and qk_norm            mixtral's MLP half behind qwen3's attention half                                   8, never folded
 
 FAMILIES says what each family asks of an architecture, variant_supported(model, variant, batch) is the one coverage rule behind every supports_*
 function, and resolve() is the precedence by which the decoders pick a variant.  Nothing but plain llama is taken without being asked.
@@ -74,6 +78,7 @@ class Family:
     sliding: tuple        # which of the config's sliding-window signals refuse the model (a window on an attention MODULE refuses it in every family)
     axis0: bool           # admits models quantised along axis 0 (the axis-0 kernels have no head-norm or bias sequence)
     lora: bool            # admits un-merged LoRA adapters
+    moe: bool = False     # the block's MLP is a routed mixture of experts: `mlp.gate` a dense top-k router, `mlp.experts` an HQQExperts, and nothing else
 
 
 FAMILIES = {f.name: f for f in (
@@ -87,14 +92,42 @@ FAMILIES = {f.name: f for f in (
     # carry a default config.sliding_window while use_sliding_window is off and every layer attends fully, so that field must not refuse them; and
     # use_sliding_window alone changes nothing until max_window_layers makes some layer_types entry a sliding one.
     Family("qwen2", ("qwen2",), qk_norm=False, qkv_bias=True, sliding=("layer_types",), axis0=False, lora=False),
+    # MixtralDecoderLayer (models/mixtral): Mistral's block with MixtralSparseMoeBlock (a MixtralTopKRouter and fused experts) in the MLP's place.
+    Family("mixtral", ("mixtral",), qk_norm=False, qkv_bias=False, sliding=("sliding_window",), axis0=False, lora=False, moe=True),
+    # Qwen3MoeDecoderLayer (models/qwen3_moe) where every block is sparse: Qwen3's block with Qwen3MoeSparseMoeBlock in the MLP's place.  Dense blocks
+    # (mlp_only_layers, decoder_sparse_step != 1) have no `experts` and refuse the model; so do shared experts (Qwen2-MoE, DeepSeek: other model types anyway).
+    Family("qwen3_moe", ("qwen3_moe",), qk_norm=True, qkv_bias=False, sliding=("sliding_window", "use_sliding_window", "layer_types"), axis0=False, lora=False, moe=True),
 )}
+
+# the router class each MoE family's blocks carry (ops.moe_router restates exactly these two forwards)
+_ROUTERS = {"mixtral": "MixtralTopKRouter", "qwen3_moe": "Qwen3MoeTopKRouter"}
+
+
+def _moe_mlp_ok(mlp, family: Family, cfg, dt) -> bool:
+    """an MoE family's question about a block's `mlp` (in the place of the dense families' SiLU check): its children are `gate` and `experts` and nothing
+    else (no shared expert, no dense MLP); experts is a ready HQQExperts (SiLU by construction); gate is the family's router class with ONE parameter, a
+    dense weight [E, H] of the compute dtype on the experts' device (no bias), an integer top_k in 1 .. 8 and, for Qwen3-MoE, a boolean norm_topk_prob"""
+    from ..core.moe import HQQExperts
+    if set(dict(mlp.named_children())) != {"gate", "experts"}:
+        return False
+    gate, ex = mlp.gate, mlp.experts
+    if not isinstance(ex, HQQExperts) or not ex.ready or type(gate).__name__ != _ROUTERS[family.name]:
+        return False
+    if [n for n, _ in gate.named_parameters()] != ["weight"] or getattr(gate, "bias", None) is not None:
+        return False
+    w = gate.weight
+    if w.dim() != 2 or tuple(w.shape) != (ex.num_experts, cfg.hidden_size) or w.dtype != dt or not w.is_contiguous() or w.device != ex.gate_W_q.device:
+        return False
+    if isinstance(gate.top_k, bool) or not isinstance(gate.top_k, int) or not 1 <= gate.top_k <= min(8, ex.num_experts):
+        return False
+    return family.name != "qwen3_moe" or isinstance(gate.norm_topk_prob, bool)
 
 
 def _arch_ok(model, family: Family) -> bool:
     """The allow-list half of variant_supported(): whether `model` is of `family`, i.e. its decoder block is the arithmetic the step restates and nothing
     else.  Refused in every family: another model_type, soft-capping, config.attention_bias / mlp_bias, Granite-style multipliers (residual / embedding /
     logits / attention) other than 1, attention sinks or a qk_norm module, a sliding window on an attention module, an activation other than SiLU.
-    What differs between the families is FAMILIES' fields."""
+    What differs between the families is FAMILIES' fields; an MoE family asks _moe_mlp_ok of every block's mlp where the others ask for SiLU."""
     try:
         cfg = model.config
         if getattr(cfg, "model_type", None) not in family.model_types:
@@ -109,9 +142,9 @@ def _arch_ok(model, family: Family) -> bool:
             return False
         if "layer_types" in family.sliding and any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
             return False
+        dt = model.model.norm.weight.dtype
         if family.qk_norm:
             hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-            dt = model.model.norm.weight.dtype
         for blk in model.model.layers:
             at = blk.self_attn
             if any(hasattr(at, n) for n in ("qk_norm", "sinks")) or getattr(at, "sliding_window", None):
@@ -127,10 +160,13 @@ def _arch_ok(model, family: Family) -> bool:
                     return False
                 if at.o_proj.bias is not None or any(getattr(blk.mlp, n).bias is not None for n in ("gate_proj", "up_proj", "down_proj")):
                     return False
-            if type(getattr(blk.mlp, "act_fn", None)).__name__ not in ("SiLUActivation", "SiLU"):
+            if family.moe:
+                if not _moe_mlp_ok(blk.mlp, family, cfg, dt):
+                    return False
+            elif type(getattr(blk.mlp, "act_fn", None)).__name__ not in ("SiLUActivation", "SiLU"):
                 return False
         return True
-    except AttributeError:
+    except (AttributeError, TypeError):
         return False
 
 
@@ -151,16 +187,22 @@ def qkv_bias_arch_supported(model) -> bool:
     return _arch_ok(model, FAMILIES["qwen2"])
 
 
+def moe_arch_supported(model) -> bool:
+    """a Mixtral or an all-sparse Qwen3-MoE architecture (FAMILIES["mixtral"] / ["qwen3_moe"]) whose experts are HQQExperts: what the step with moe=True restates"""
+    return _arch_ok(model, FAMILIES["mixtral"]) or _arch_ok(model, FAMILIES["qwen3_moe"])
+
+
 def _no_variant(**flags) -> ValueError:
     return ValueError(f"hqq_amd: no fused decode step for {' with '.join(k + '=True' for k, on in flags.items() if on)}: axis0 and lora=True go with Llama / Mistral "
-                      "models only (an axis-0 or adapted Qwen decodes through the model's own forward), and no served architecture has both q/k/v biases and head norms")
+                      "models only (an axis-0 or adapted Qwen decodes through the model's own forward), no served architecture has both q/k/v biases and head norms, "
+                      "and moe=True goes alone (Mixtral) or with qk_norm=True (Qwen3-MoE)")
 
 
 @dataclass(frozen=True)
 class StepVariant:
     """Which sequence of launches a model decodes through: its family, whether its linears are quantised along axis 0, whether they still carry LoRA
-    adapters.  Six exist (VARIANTS): only the Llama family admits axis 0 or adapters.  The step and the decoders each hold one;
-    from_flags() / flags() translate from and to FusedLlamaStep's four boolean keywords."""
+    adapters.  Eight exist (VARIANTS): only the Llama family admits axis 0 or adapters, and the two MoE families are variants by their family alone.  The step
+    and the decoders each hold one; from_flags() / flags() translate from and to FusedLlamaStep's boolean keywords."""
     family: str = "llama"
     axis0: bool = False
     lora: bool = False
@@ -173,26 +215,35 @@ class StepVariant:
             raise _no_variant(**self.flags())
 
     @classmethod
-    def from_flags(cls, axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False) -> "StepVariant":
-        """the variant FusedLlamaStep's four keywords name; ValueError for the ten combinations that name none"""
-        if qk_norm and qkv_bias:
-            raise _no_variant(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)
+    def from_flags(cls, axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False) -> "StepVariant":
+        """the variant FusedLlamaStep's keywords name; ValueError for the combinations that name none (ten without moe; with moe, everything but moe alone —
+        Mixtral — and moe with qk_norm — Qwen3-MoE)"""
+        if (qk_norm and qkv_bias) or (moe and (axis0 or qkv_bias or lora)):
+            raise _no_variant(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
+        if moe:
+            return cls("qwen3_moe" if qk_norm else "mixtral")
         return cls("qwen3" if qk_norm else "qwen2" if qkv_bias else "llama", bool(axis0), bool(lora))
 
     def flags(self) -> dict:
-        """from_flags' inverse: the four booleans as FusedLlamaStep's keywords"""
-        return {"axis0": self.axis0, "qk_norm": self.family == "qwen3", "qkv_bias": self.family == "qwen2", "lora": self.lora}
+        """from_flags' inverse: the booleans as FusedLlamaStep's keywords — the four of the dense variants, and "moe": True in addition for the two MoE ones"""
+        fam = FAMILIES[self.family]
+        flags = {"axis0": self.axis0, "qk_norm": fam.qk_norm, "qkv_bias": fam.qkv_bias, "lora": self.lora}
+        if fam.moe:
+            flags["moe"] = True
+        return flags
 
 
 # every variant there is, in resolve()'s order of precedence
-VARIANTS = (StepVariant(), StepVariant(axis0=True), StepVariant("qwen3"), StepVariant("qwen2"), StepVariant(lora=True), StepVariant(axis0=True, lora=True))
+VARIANTS = (StepVariant(), StepVariant(axis0=True), StepVariant("qwen3"), StepVariant("qwen2"), StepVariant(lora=True), StepVariant(axis0=True, lora=True),
+            StepVariant("mixtral"), StepVariant("qwen3_moe"))
 
 
-def _decoder_linears(model, lora: bool = False):
-    """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers (lora: the layer behind an HQQLinearLoRA wrapper where there is one)"""
+def _decoder_linears(model, lora: bool = False, moe: bool = False):
+    """the seven linears of every decoder block, q k v o gate up down, as HQQLinearHIP layers (lora: the layer behind an HQQLinearLoRA wrapper where there is one);
+    moe: the four attention linears only (the MLP's place is taken by a router and an HQQExperts)"""
     get = _unwrap if lora else _hip
-    return [[get(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [get(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]
-            for b in model.model.layers]
+    return [[get(getattr(b.self_attn, n)) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] +
+            ([] if moe else [get(getattr(b.mlp, n)) for n in ("gate_proj", "up_proj", "down_proj")]) for b in model.model.layers]
 
 
 def _decoder_wrappers(model):
@@ -215,6 +266,7 @@ def _structure(model, variant: StepVariant):
     dtype with a multiple of 8 features.  Biases: no decoder linear may have one, except that in a family with qkv_bias q_proj, k_proj and v_proj must each
     HAVE one — 1-D, dense, out_features elements, the compute dtype, the layer's device.  With lora the checks apply to the layers behind HQQLinearLoRA
     wrappers (what the wrappers themselves must look like is _lora_wrappers_ok's question).
+    An MoE family: the four attention linears only (what the router and the experts must look like is _arch_ok's question, which kernels cover them _moe_covers').
     Returns (dtype, _decoder_linears(model)), or None where the model is not of that shape; which kernels cover the layers is the caller's question."""
     family = FAMILIES[variant.family]
     if not _arch_ok(model, family):
@@ -226,7 +278,7 @@ def _structure(model, variant: StepVariant):
             return None
         if not hasattr(inner, "rotary_emb") or not hasattr(inner, "embed_tokens") or not hasattr(model, "lm_head"):
             return None
-        blocks = _decoder_linears(model, variant.lora)
+        blocks = _decoder_linears(model, variant.lora, family.moe)
         for blk, lin in zip(inner.layers, blocks):
             if not all(isinstance(L, HQQLinearHIP) and L.compute_dtype == dt and L.W_q.is_cuda and L.axis == (0 if variant.axis0 else 1) for L in lin):
                 return None
@@ -294,6 +346,27 @@ def _lora_wrappers_ok(model, B: int) -> bool:
         return False
 
 
+def _moe_covers(model, dt, B: int) -> bool:
+    """the expert half of variant_supported() for the MoE families, at B rows: every block's HQQExperts in a layout the routed expert kernel reads (byte
+    containers, no view_as_float, ONE packing and group size over gate / up / down, axis 1, stacks of the compute dtype on the GPU), ops.moe_covers and
+    ops.moe_router_covers for its shapes.  ops.MOE_ROUTE_MAX_T is HQQExperts' own route policy and is not asked: the step has no composed alternative"""
+    from ..core.moe import ROLES
+    from ..core.quantize import Quantizer
+    for blk in model.model.layers:
+        ex, gate = blk.mlp.experts, blk.mlp.gate
+        g = ex.layer_meta["gate"]
+        if any(ex.layer_meta[r]["view_as_float"] or ex.layer_meta[r]["packing"] not in ("4bit_u8", "2bit_u8") or ex.layer_meta[r]["packing"] != g["packing"]
+               or ex.layer_meta[r]["group_size"] != g["group_size"] or ex.layer_meta[r]["axis"] != 1 for r in ROLES):
+            return False
+        if not (ex.gate_W_q.is_cuda and gate.weight.is_cuda) or ex.gate_scale.dtype != dt:
+            return False
+        if not ops.moe_covers(dt, B, gate.top_k, ex.num_experts, ex.hidden_dim, ex.intermediate_dim, g["group_size"], Quantizer._packing_bits[g["packing"]], 1):
+            return False
+        if not ops.moe_router_covers(dt, B, gate.top_k, ex.num_experts, ex.hidden_dim):
+            return False
+    return True
+
+
 def variant_supported(model, variant: StepVariant, batch: int | None = None) -> bool:
     """Whether the fused step of `variant` serves `model` — the one rule behind every supports_* function below.  batch=None asks about one sequence, an
     integer about that many rows, and the two are NOT the same question at 1: on axis 1 without adapters, one sequence asks only that q|k|v and gate|up can
@@ -304,9 +377,11 @@ def variant_supported(model, variant: StepVariant, batch: int | None = None) -> 
       ops.qknorm_rope_cache_batched serves (64 / 128 / 256; ops.bias_rope_cache_batched serves any even one, so qwen2 asks for none);
       axis 0: 1 <= B <= ops.GEMV_MAX_M; q|k|v share (nbits, group_size) and gate|up share them with equal N, so that each group is ONE grouped launch
       (ops.axis0_grouped_covers, gate|up with BLOCK_SILU); o and down on the single-layer kernel (ops.decode_axis0_covers);
-      lora: the wrappers as _lora_wrappers_ok asks for them, any subset of the seven linears adapted, with different ranks."""
+      lora: the wrappers as _lora_wrappers_ok asks for them, any subset of the seven linears adapted, with different ranks;
+      mixtral / qwen3_moe: the axis-1 rule over q|k|v (there is no gate|up pair), B <= ops.MOE_MAX_T, and _moe_covers at B rows; qwen3_moe: qwen3's head_dim."""
     B = 1 if batch is None else int(batch)
-    if B < 1 or (variant.axis0 and B > ops.GEMV_MAX_M) or (variant.lora and not _lora_wrappers_ok(model, B)):
+    moe = FAMILIES[variant.family].moe
+    if B < 1 or (variant.axis0 and B > ops.GEMV_MAX_M) or (variant.lora and not _lora_wrappers_ok(model, B)) or (moe and B > ops.MOE_MAX_T):
         return False
     found = _structure(model, variant)
     if found is None:
@@ -323,11 +398,13 @@ def variant_supported(model, variant: StepVariant, batch: int | None = None) -> 
                 return False
         return True
     for lin in blocks:
-        if len({(L.nbits, L.group_size, L.w3s) for L in lin[:3]}) != 1 or len({(L.nbits, L.group_size, L.w3s) for L in lin[4:6]}) != 1:
+        if len({(L.nbits, L.group_size, L.w3s) for L in lin[:3]}) != 1 or len({(L.nbits, L.group_size, L.w3s) for L in lin[4:6]}) > 1:   # (an MoE block has no gate|up pair)
             return False
         if not ops.decode_covers(dt, 1, lin[0].out_features, lin[0].in_features, lin[0].group_size, lin[0].nbits) and not lin[0].w3s:
             return False
-    if variant.family == "qwen3":
+    if moe and not _moe_covers(model, dt, B):
+        return False
+    if FAMILIES[variant.family].qk_norm:
         cfg = model.config
         if (getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads) not in (64, 128, 256):
             return False
@@ -338,8 +415,9 @@ def variant_supported(model, variant: StepVariant, batch: int | None = None) -> 
 
 def resolve(model, opted, batch: int | None = None) -> StepVariant | None:
     """The variant a decoder gives `model`: the first of VARIANTS — llama, then axis 0, then qwen3, then qwen2, then lora on axis 1, then lora on axis 0 — that
-    is opted into and that variant_supported accepts (at `batch`), or None: the model's own forward.  `opted` holds the opt-ins among "axis0", "qk_norm",
-    "qkv_bias", "lora"; a variant is opted into when every flag it sets is (plain llama sets none: always; lora on axis 0 needs both)."""
+    is opted into and that variant_supported accepts (at `batch`), or None: the model's own forward; mixtral and qwen3_moe come last.  `opted` holds the
+    opt-ins among "axis0", "qk_norm", "qkv_bias", "lora", "moe"; a variant is opted into when every flag it sets is (plain llama sets none: always; lora on
+    axis 0 needs both, and so does qwen3_moe: qk_norm and moe)."""
     opted = set(opted)
     for variant in VARIANTS:
         if all(k in opted for k, on in variant.flags().items() if on) and variant_supported(model, variant, batch):
@@ -392,6 +470,15 @@ def supports_lora_batch(model, B: int, axis0: bool | None = None) -> bool:
     return any(variant_supported(model, StepVariant(axis0=a, lora=True), B) for a in (False, True) if axis0 in (None, a))
 
 
+def supports_moe(model) -> bool:
+    """supports() for a Mixtral or Qwen3-MoE model whose experts are HQQExperts: what FusedLlamaStep(moe=True) (with qk_norm=True for Qwen3-MoE) takes"""
+    return any(variant_supported(model, StepVariant(f)) for f in _ROUTERS)
+
+
+def supports_moe_batch(model, B: int) -> bool:
+    return any(variant_supported(model, StepVariant(f), B) for f in _ROUTERS)
+
+
 def _gopts(Ls) -> int:
     lay = ops.OPT_W3S if Ls[0].w3s else 0
     return ops.layer_opts((ops.OPT_META_SCALABLE if all(L.opts & ops.OPT_META_SCALABLE for L in Ls) else 0) | lay)
@@ -403,7 +490,7 @@ class FusedLlamaStep:
     every glue kernel gives the bits of the batch-1 kernel for sequence b alone, and the linears run at M = batch."""
 
     def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
-                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False):
+                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -416,11 +503,16 @@ class FusedLlamaStep:
         a combination that names none is a ValueError, and so is a model that variant_supported refuses for it at `batch` rows.  axis0 and lora take the
         separate glue kernels (the folded launches read axis-1 meta and serve no adapters: glue="folded" is refused); qk_norm and qkv_bias fold all but their
         rotary-and-cache launch, and with attention="hip" the kernel attends on that launch's rotated q_out (ops.attn_decode_batched).  lora: the adapter
-        terms are added on the input the base launch read — o's on self.delta before the residual add, gate|up's before SiLU — and `scaling` is read once, here."""
+        terms are added on the input the base launch read — o's on self.delta before the residual add, gate|up's before SiLU — and `scaling` is read once, here.
+        moe (Mixtral; with qk_norm=True: Qwen3-MoE): the separate glue kernels (glue="folded" is refused), with ops.moe_router, ops.moe_gate_up and ops.moe_down
+        on the HQQExperts stacks in the place of gate|up, silu_mul and down.  Per block, counted from __call__: add_rmsnorm, q|k|v, the rotary-and-cache launch,
+        o, add_rmsnorm, moe_router, moe_gate_up, moe_down = 8 launches + the attention's (9 with attention="sdpa", whose function is one SDPA launch here).  The
+        router writes idx / weights into per-block buffers that the two expert launches read on the device: nothing is cast or copied in between."""
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
-        self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)
+        self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
         self.axis0, self.qk_norm, self.qkv_bias, self.lora = (variant.flags()[k] for k in ("axis0", "qk_norm", "qkv_bias", "lora"))
+        self.moe = FAMILIES[variant.family].moe
         self.model = model
         inner = model.model
         self.inner = inner
@@ -442,12 +534,13 @@ class FusedLlamaStep:
         self.attention = attention
         if glue not in ("auto", "folded", "kernels"):
             raise ValueError("glue: 'auto', 'folded' or 'kernels'")
-        if glue == "folded" and (self.lora or self.axis0):
-            raise ValueError(f"hqq_amd: glue='folded' reads axis-1 meta and serves no adapters: {'lora=True' if self.lora else 'axis0=True'} takes the separate glue kernels")
+        if glue == "folded" and (self.lora or self.axis0 or self.moe):
+            raise ValueError("hqq_amd: glue='folded' reads axis-1 meta of seven dense linears and serves no adapters: "
+                             f"{'lora=True' if self.lora else 'axis0=True' if self.axis0 else 'moe=True'} takes the separate glue kernels")
         # (a single sequence of an axis-1 Llama is not asked: its callers ask supports(), and models construct here that it refuses)
         if (variant != StepVariant() or B != 1) and not variant_supported(model, variant, None if B == 1 else B):
             on = [k for k, v in variant.flags().items() if v]
-            fn = "supports" + ("_lora" if self.lora else "_" + on[0] if on else "")
+            fn = "supports" + ("_lora" if self.lora else "_moe" if self.moe else "_" + on[0] if on else "")
             raise ValueError(f"hqq_amd: {', '.join(k + '=True' for k in on) or 'a batch'} needs a model of the {variant.family} family whose decoder linears "
                              f"the fused decode kernels serve at {B} rows ({fn} / {fn}_batch)")
         # the rotary-and-cache launch of the family, by name (looked up in ops at every call), and what it takes of block b between v and cos
@@ -457,10 +550,13 @@ class FusedLlamaStep:
             "qwen3": ("qknorm_rope_cache_batched", lambda b: (b["attn"].q_norm.weight, b["attn"].k_norm.weight, b["attn"].q_norm.variance_epsilon, b["attn"].k_norm.variance_epsilon)),
             # Qwen2: the projections' biases added to the bias-free q|k|v, then rotated and cached, one launch
             "qwen2": ("bias_rope_cache_batched", lambda b: b["qkv_bias"]),
+            # the MoE families: the attention half of Mistral's / Qwen3's block
+            "mixtral": ("rope_cache_batched", lambda b: ()),
+            "qwen3_moe": ("qknorm_rope_cache_batched", lambda b: (b["attn"].q_norm.weight, b["attn"].k_norm.weight, b["attn"].q_norm.variance_epsilon, b["attn"].k_norm.variance_epsilon)),
         }[variant.family]
-        blocks = _decoder_linears(model, self.lora)
+        blocks = [lin + [None] * (7 - len(lin)) for lin in _decoder_linears(model, self.lora, self.moe)]   # (an MoE block: q k v o, and no gate up down)
         wrappers = _decoder_wrappers(model) if self.lora else [[None] * 7 for _ in blocks]
-        can_fold = not self.lora and all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
+        can_fold = not self.lora and not self.moe and all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
                        for (q, _, _, o, g, _, d) in blocks for L, norm in ((q, True), (o, False), (g, True), (d, False))) and \
             all(g.out_features == u.out_features for (_, _, _, _, g, u, _) in blocks) and not (ops._default_opts & ops.OPT_FACTORED) and not self.axis0 and B == 1
         if glue == "folded" and not can_fold:
@@ -491,15 +587,29 @@ class FusedLlamaStep:
                 raise ValueError(f"hqq_amd: the fused decode step needs an initialised HF StaticCache of batch {B} and {max_cache_len} positions")
             self.blocks.append({
                 "attn": blk.self_attn, "n1": blk.input_layernorm, "n2": blk.post_attention_layernorm,
-                "qkv": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (q, k, v)], "qkv_opts": _gopts((q, k, v)), "qkv_nbits": q.nbits, "qkv_gs": q.group_size, "gu_gs": g.group_size,
-                "o": o, "gu": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (g, u)], "gu_opts": _gopts((g, u)), "gu_nbits": g.nbits, "d": d,
-                "kc": lay.keys, "vc": lay.values, "len": lay.cumulative_length,
+                "qkv": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (q, k, v)], "qkv_opts": _gopts((q, k, v)), "qkv_nbits": q.nbits, "qkv_gs": q.group_size,
+                "o": o, "kc": lay.keys, "vc": lay.values, "len": lay.cumulative_length,
                 # outputs of the launches (static addresses: the step is captured in a hipGraph)
                 "q": torch.empty(B, q.out_features, dtype=dt, device=dev), "k": torch.empty(B, k.out_features, dtype=dt, device=dev),
                 "v": torch.empty(B, v.out_features, dtype=dt, device=dev), "qr": torch.empty(B, self.n_heads, 1, self.hd, dtype=dt, device=dev),
-                "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
-                "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
             })
+            if self.moe:   # the router's weight and the experts' stacks in place; idx / weights / a are this block's own (static addresses under graph capture)
+                from ..core.quantize import Quantizer
+                gate, ex = blk.mlp.gate, blk.mlp.experts
+                kk = int(gate.top_k)
+                self.blocks[-1].update({
+                    "router": gate.weight, "top_k": kk, "renorm": bool(getattr(gate, "norm_topk_prob", True)), "round_w": variant.family == "qwen3_moe",
+                    "ex": [(getattr(ex, r + "_W_q"), getattr(ex, r + "_scale"), getattr(ex, r + "_zero")) for r in ("gate", "up", "down")],
+                    "ex_dims": (ex.num_experts, ex.hidden_dim, ex.intermediate_dim, ex.layer_meta["gate"]["group_size"], Quantizer._packing_bits[ex.layer_meta["gate"]["packing"]]),
+                    "idx": torch.zeros(B, kk, dtype=torch.int64, device=dev), "w": torch.zeros(B, kk, dtype=torch.float32, device=dev),
+                    "a": torch.empty(B, kk, ex.intermediate_dim, dtype=dt, device=dev),
+                })
+            else:
+                self.blocks[-1].update({
+                    "gu_gs": g.group_size, "gu": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (g, u)], "gu_opts": _gopts((g, u)), "gu_nbits": g.nbits, "d": d,
+                    "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
+                    "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
+                })
             if self.lora:   # per group: the adapted members as (index within the group, A, B, scaling) — the tensors themselves (static addresses under graph capture)
                 for name, lo, hi in LORA_GROUPS:
                     ad = [(i, w.lora_A.data, w.lora_B.data, w._scaling_float()) for i, w in enumerate(wrappers[li][lo:hi]) if w is not None]
@@ -611,7 +721,7 @@ class FusedLlamaStep:
                     att = ops.attn_decode_batched(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
                 else:
                     att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :, :kvl], b["vc"][:, :, :kvl], mask, dropout=0.0, scaling=at.scaling)
-            o, d = b["o"], b["d"]
+            o, d = b["o"], b.get("d")
             if self.folded:
                 # o: h += o(att) in the epilogue; gate|up: RMSNorm prologue + silu(gate) * up epilogue on the paired layer; down: h += down(a) in the epilogue
                 ops.gemv_block(att.reshape(1, -1), None, 0.0, [(o.W_q, o.scale, o.zero, o.out_features)], o.in_features, o.group_size, o.nbits, [h], ops.BLOCK_RESID,
@@ -623,6 +733,12 @@ class FusedLlamaStep:
             self._single(xo, o)
             self._adapters(b, "o", xo, [self.delta])     # before the residual add (the next add_rmsnorm)
             ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
+            if self.moe:   # the router fills the block's idx / weights, the two expert launches read them on the device; self.delta = the routed MLP's output
+                ops.moe_router(self.xn, b["router"], b["top_k"], b["renorm"], b["round_w"], idx=b["idx"], weights=b["w"])
+                ops.moe_gate_up(self.xn, b["idx"], b["ex"][0], b["ex"][1], *b["ex_dims"], a=b["a"])
+                ops.moe_down(b["a"], b["idx"], b["w"], b["ex"][2], *b["ex_dims"], out=self.delta)
+                delta = self.delta
+                continue
             if self.axis0 and not (self.lora and b["lora_gu"]):   # SiLU * up rides in the grouped launch's reduce: no silu_mul launch
                 self._grouped(b, "gu", [b["a"]], flags=ops.BLOCK_SILU)
             else:   # (an adapted gate | up of an axis-0 model too: the adapter terms come before SiLU)
@@ -670,5 +786,5 @@ class FusedLlamaBatchStep(FusedLlamaStep):
     wherever the tables exist)"""
 
     def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False,
-                 lora: bool = False):
-        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora)
+                 lora: bool = False, moe: bool = False):
+        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)

@@ -526,6 +526,33 @@ int hqq_hip_moe_down(int nbits, const void* a, const void* idx, const void* weig
                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The router of a mixture-of-experts block at decode sizes (csrc/moe_router.hip): what MixtralTopKRouter / Qwen3MoeTopKRouter compute (F.linear, softmax,
+ * topk, sum, div and Qwen3-MoE's cast), in ONE launch for T_ rows.  With T the compute dtype (`dtype`) and rnd = round to T:
+ *     l[t, e] = fp32(rnd(x_t . W_e))                              x [T_, H] of T, W [E, H] of T, dense, row-major
+ *     p[t, e] = exp(l[t, e] - max_e l) / sum_e exp(l - max)       in fp32; the sum over e in ascending order, one addition after the other
+ *     sel     = the k experts of largest l[t, .], in descending l; EQUAL LOGITS BY ASCENDING e
+ *     w[t, s] = p[t, sel_s], divided by sum_s p[t, sel_s] (s ascending) if `renorm`, then rounded to T and widened back to fp32 if `round_weights`
+ *               (Qwen3-MoE's `.to(router_logits.dtype)`)
+ * The dot product accumulates in fp32: lane i of a wave takes the 8-element chunks i, i + 64, ... of the row, one fused multiply-add per element in
+ * ascending index into one accumulator, and the 64 partial sums are added as a balanced binary tree in lane order — an order that depends on H alone.
+ * Selection is decided ON THE LOGITS (softmax is monotone) and the order among equal values — lower id first — is this library's own rule: torch.topk
+ * leaves it unspecified, so it is not inherited from anything.  -0 equals +0.  A NaN logit compares as the largest (as in torch.topk), NaNs among
+ * themselves by ascending id; every weight of a row that has one is NaN (as torch's softmax gives).
+ * The one deviation from HF: F.linear rounds the same dot product to T in a summation order of its own, so a logit can differ from HF's by an ulp of T, and
+ * a row whose k-th and (k+1)-th logits are that close can route differently.
+ *   idx [T_, k] int64, weights [T_, k] float32 — what hqq_hip_moe_gate_up / hqq_hip_moe_down read; logits [T_, E] of T, or NULL to skip them.
+ * Two calls give the same bits; a row's result does not depend on T_ or on the other rows.  No atomics, no workspace; nothing outside the three outputs
+ * is written.
+ * Covered: fp16 / bf16; 1 <= T_ <= 16; 1 <= k <= 8; k <= E <= 256; H % 8 == 0, 8 <= H <= 65536.  Anything else: HQQ_ERR_UNSUPPORTED with a message, before
+ * anything is launched and without a GPU; hqq_hip_moe_router_covers answers the same question (1 / 0).  x and W 16-byte aligned, the outputs to their
+ * element size (HQQ_ERR_ALIGN otherwise, as everywhere in this header).
+ * The two symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_moe_router_covers(int64_t T_, int64_t k, int64_t E, int64_t H, int dtype);
+int hqq_hip_moe_router(const void* x, const void* W, void* idx, void* weights, void* logits, int64_t T_, int64_t k, int64_t E, int64_t H, int renorm,
+                       int round_weights, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
