@@ -539,7 +539,7 @@ __global__ __launch_bounds__(256) void token_prologue_kernel(const int64_t* __re
   }
 }
 
-// argmax_advance: next = the FIRST index of the largest logit (torch.argmax's tie rule; logits finite), written to next_tok and tok, pos += 1.  One workgroup:
+// argmax_advance: next = the FIRST index of the largest logit (torch.argmax's tie and NaN rule: the first NaN wins over every number, -0 == +0, +-inf are ordinary values), written to next_tok and tok, pos += 1.  One workgroup:
 // 1024 threads keep (value, index) of their strided share in index order, then a fixed tree in LDS.  blockIdx.x: the sequence of a batch
 // (hqq_hip_argmax_advance_batched): logits row, next_tok / tok / pos element of its own.
 template <bool BF>

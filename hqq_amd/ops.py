@@ -1197,7 +1197,7 @@ def quantize_tensorwise(W: Tensor, nbits=4, round_zero: bool = False):
 
 # ---- the steps either side of the GEMVs in a decode step (csrc/block.hip; include/hqq_hip.h) --------------------------------------------
 def add_rmsnorm(h: Tensor, delta, weight: Tensor, eps: float, out: Tensor | None = None) -> Tensor:
-    """h += delta (in place, if delta is given), then LlamaRMSNorm(h) with `weight` — HF's arithmetic, one kernel.  h: [..., H] fp16, dense."""
+    """h += delta (in place, if delta is given), then LlamaRMSNorm(h) with `weight` — HF's arithmetic, one kernel.  h: [..., H] fp16 / bf16, dense, H a multiple of 8."""
     _dev(h, delta, weight)
     H = h.shape[-1]
     if out is None:
@@ -1430,7 +1430,8 @@ def argmax_advance(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, 
 
 
 def silu_mul(gate: Tensor, up: Tensor, out: Tensor | None = None) -> Tensor:
-    """LlamaMLP's act_fn(gate) * up in one kernel (fp16)"""
+    """LlamaMLP's act_fn(gate) * up in one kernel (fp16 / bf16; n a multiple of 8): silu in fp32, x / (1 + exp(-x)), rounded to the dtype, then the product in the
+    dtype.  The fp32 formula's range is kept: a gate below about -88.72 gives -0 (exp overflows), -inf gives NaN — torch's own result."""
     _dev(gate, up)
     if out is None:
         out = torch.empty_like(gate)
