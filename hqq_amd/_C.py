@@ -92,6 +92,14 @@ SYMBOLS = {
     # the router in front of them, one launch (csrc/moe_router.hip; added at ABI 9 without a bump: nothing that existed changed)
     "hqq_hip_moe_router_covers": (_i32, [_i64, _i64, _i64, _i64, _i32]),
     "hqq_hip_moe_router": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    # the quantised static KV cache: bulk write, expansion, the decode step's write and its attention (csrc/kv_cache.hip; added at ABI 9 without a bump: nothing that existed changed)
+    "hqq_hip_kv_covers": (_i32, [_i32, _i64, _i64, _i64, _i32]),
+    "hqq_hip_kv_quantize": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "hqq_hip_kv_dequantize": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp]),
+    "hqq_hip_rope_kvq_cache_batched": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
+    "hqq_hip_attn_decode_kvq": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
+    "hqq_hip_attn_decode_kvq_batched": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz,
+                                               _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -778,9 +778,7 @@ static int attn_decode_run(const char* who, bool rope, const void* q, const void
 #undef HQQ_ATTN_HD
 #undef HQQ_ATTN_GO
   if (S > 1) {   // (record of head b n_heads + h and output row b, head h: the same offset for a dense [batch, n_heads, HD] output)
-    const dim3 cgrid(static_cast<unsigned>(batch * n_heads));
-    if (bf) hipLaunchKernelGGL(attn_combine_kernel<true>, cgrid, dim3(256), 0, as_stream(stream), wsf, static_cast<u16>(out), S, HD);
-    else hipLaunchKernelGGL(attn_combine_kernel<false>, cgrid, dim3(256), 0, as_stream(stream), wsf, static_cast<u16>(out), S, HD);
+    launch_attn_combine(wsf, out, batch * n_heads, S, HD, bf, as_stream(stream));
   }
   return check_launch(who);
 }
@@ -817,6 +815,13 @@ int hqq_hip_rope_attn_decode_batched(const void* q, const void* k, const void* v
 }
 
 }  // extern "C"
+
+// the merging launch of a split decode-attention call over `heads` records; shared with the quantised-cache attention (kv_cache.hip), whose shares are these records
+void hqq::launch_attn_combine(const float* ws, void* out, int64_t heads, int S, int HD, bool bf, hipStream_t st) {
+  const dim3 cgrid(static_cast<unsigned>(heads));
+  if (bf) hipLaunchKernelGGL(attn_combine_kernel<true>, cgrid, dim3(256), 0, st, ws, static_cast<u16>(out), S, HD);
+  else hipLaunchKernelGGL(attn_combine_kernel<false>, cgrid, dim3(256), 0, st, ws, static_cast<u16>(out), S, HD);
+}
 
 static int token_prologue_run(const char* who, const int64_t* tok_dev, const int64_t* pos_dev, int64_t batch, const void* embed, int64_t vocab, int64_t H, const void* cos_tab,
                               const void* sin_tab, int64_t L, int64_t head_dim, void* h, void* cos, void* sin, void* mask, int dtype, void* stream) {

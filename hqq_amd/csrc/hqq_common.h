@@ -164,4 +164,7 @@ constexpr size_t WS_COUNTER_BYTES = size_t(256) << 10;
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// block.hip: the launch that merges the `S` (max, sum, output) records of each of `heads` heads of a split decode-attention call into out [heads, HD]
+void launch_attn_combine(const float* ws, void* out, int64_t heads, int S, int HD, bool bf, hipStream_t st);
+
 }  // namespace hqq

@@ -1410,6 +1410,147 @@ def rope_attn_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, 
     return rope_attn_decode_batched(q, k, v, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), out, scaling, splits=splits, workspace=workspace)
 
 
+# ---- the quantised static KV cache (csrc/kv_cache.hip; include/hqq_hip.h states the format).  `bufs` is a layer's six buffers in the order
+#      (kq, k_scale, k_zero, vq, v_scale, v_zero): kq / vq [B, n_kv, L, head_dim * nbits / 8] uint8, the four meta tensors [B, n_kv, L, head_dim / gs] of the
+#      compute dtype; nbits and the group size are read off their shapes against head_dim ----------------------------------------------------------------------
+KV_MAX_LEN = 30000   # the decode-attention kernels' limit on cache positions
+
+
+def kv_group_size(head_dim: int) -> int:
+    """the default group size of a quantised cache row: 64, or 32 when head_dim is 64"""
+    return 32 if int(head_dim) == 64 else 64
+
+
+def kv_covers(dtype, nbits, head_dim: int, group_size, cache_len: int = 1) -> bool:
+    """what the quantised-cache kernels serve (pure host arithmetic): fp16 / bf16, nbits 8 / 4, head_dim 64 / 128 / 256, group_size 32 / 64 dividing head_dim with
+    2 * group_size <= head_dim at 4 bits, 1 <= cache_len <= 30000"""
+    if dtype not in (torch.float16, torch.bfloat16) or isinstance(nbits, bool) or not isinstance(nbits, int) or not isinstance(group_size, int):
+        return False
+    return bool(_C.lib().hqq_hip_kv_covers(int(nbits), int(head_dim), int(group_size), int(cache_len), _DT[dtype]))
+
+
+def kv_alloc(B: int, n_kv: int, L: int, head_dim: int, nbits: int, group_size: int, dtype, device) -> tuple:
+    """a layer's six buffers, zeroed (level 0, scale 0 and zero 0 dequantise to 0: an unwritten position holds finite values, as a zeroed dense cache does)"""
+    if not kv_covers(dtype, nbits, head_dim, group_size, L):
+        raise ValueError(f"hqq_amd: no quantised KV cache for dtype {dtype}, nbits {nbits}, head_dim {head_dim}, group_size {group_size}, {L} positions (ops.kv_covers)")
+    lv = lambda: torch.zeros(B, n_kv, L, head_dim * nbits // 8, dtype=torch.uint8, device=device)   # noqa: E731
+    mt = lambda: torch.zeros(B, n_kv, L, head_dim // group_size, dtype=dtype, device=device)        # noqa: E731
+    return (lv(), mt(), mt(), lv(), mt(), mt())
+
+
+def _kv_bufs(bufs, head_dim: int, who: str):
+    """the six buffers checked against each other and head_dim.  Returns (B, n_kv, L, nbits, group_size, dtype)."""
+    if len(bufs) != 6 or not all(isinstance(t, Tensor) for t in bufs):
+        raise ValueError(f"hqq_amd: {who} takes the six cache buffers (kq, k_scale, k_zero, vq, v_scale, v_zero)")
+    kq, ks, kz, vq, vs, vz = bufs
+    _dev(*bufs)
+    if kq.dim() != 4 or kq.dtype != torch.uint8 or vq.dtype != torch.uint8 or vq.shape != kq.shape or ks.dim() != 4 or any(t.shape != ks.shape or t.dtype != ks.dtype for t in (kz, vs, vz)) or \
+            ks.shape[:3] != kq.shape[:3] or not all(t.is_contiguous() for t in bufs) or kq.shape[3] < 1 or ks.shape[3] < 1:
+        raise ValueError(f"hqq_amd: {who} takes dense uint8 level buffers [B, n_kv_heads, cache_len, head_dim * nbits / 8] and four dense meta tensors "
+                         "[B, n_kv_heads, cache_len, head_dim / group_size] of one dtype")
+    B, n_kv, L, rb = (int(s) for s in kq.shape)
+    G = int(ks.shape[3])
+    hd = int(head_dim)
+    if hd < 1 or hd % G or rb * 8 % hd or rb * 8 // hd not in (8, 4):
+        raise ValueError(f"hqq_amd: {who}: buffers of {rb} bytes and {G} groups per row do not hold rows of {hd} values at 8 or 4 bits")
+    nbits, gs = rb * 8 // hd, hd // G
+    if not kv_covers(ks.dtype, nbits, hd, gs, L):
+        raise NotImplementedError(f"hqq_amd: {who}: not covered: dtype {ks.dtype}, nbits {nbits}, head_dim {hd}, group_size {gs}, {L} positions (ops.kv_covers)")
+    return B, n_kv, L, nbits, gs, ks.dtype
+
+
+def kv_quantize(k: Tensor, v: Tensor, bufs, start=0) -> None:
+    """rows k, v [B, n_kv, T, head_dim] (any strides over the first three dimensions that are multiples of 8 elements; head_dim dense) quantised into positions
+    p .. p + T - 1 of the six buffers.  start: a host integer p (0 <= p, p + T <= L), or an int64 device tensor — one element: p for every sequence; B elements:
+    p[b] for sequence b (graph-replay safe; a position outside [0, L) writes nothing).  Nothing but the addressed positions is written."""
+    _dev(k, v)
+    if k.dim() != 4 or k.shape[3] < 1:
+        raise ValueError("hqq_amd: kv_quantize takes k / v [B, n_kv_heads, T, head_dim]")
+    B, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, k.shape[3], "kv_quantize")
+    if v.shape != k.shape or k.dtype != dt or v.dtype != dt or tuple(k.shape[:2]) != (B, n_kv) or k.shape[2] < 1 or k.shape[2] > L or \
+            (k.shape[3] > 1 and (k.stride(3) != 1 or v.stride(3) != 1)):
+        raise ValueError("hqq_amd: kv_quantize takes k / v [B, n_kv_heads, T, head_dim] of the buffers' dtype and batch, 1 <= T <= cache_len, head_dim dense")
+    T = int(k.shape[2])
+    pos, stride, p0 = None, 0, 0
+    if isinstance(start, Tensor):
+        _dev(start)
+        if start.dtype != torch.int64 or start.numel() not in (1, B) or not start.is_contiguous():
+            raise ValueError("hqq_amd: kv_quantize's device positions are a dense int64 tensor of 1 or B elements")
+        pos, stride = start, (1 if start.numel() == B and B > 1 else 0)
+    else:
+        p0 = int(start)
+        if p0 < 0 or p0 + T > L:
+            raise ValueError(f"hqq_amd: kv_quantize: positions {p0} .. {p0 + T - 1} outside a cache of {L}")
+    with torch.cuda.device(k.device):
+        rc = _C.lib().hqq_hip_kv_quantize(nbits, _p(k), _p(v), _i64s(k.stride()[:3]), _i64s(v.stride()[:3]), B, n_kv, T, int(k.shape[3]), gs, p0, _p(pos), stride,
+                                          *(_p(t) for t in bufs), L, _dt(dt), _stream())
+    _C.check(rc, "hqq_hip_kv_quantize")
+
+
+def kv_dequantize(bufs, head_dim: int, n: int | None = None, out=None):
+    """positions 0 .. n - 1 (default: all) of the six buffers as dense tensors (k, v) [B, n_kv, n, head_dim] of the compute dtype: round(round(q - zero) * scale)
+    per element, Quantizer.dequantize's two roundings.  out: a pair of dense tensors of that shape to fill."""
+    B, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, head_dim, "kv_dequantize")
+    n = L if n is None else int(n)
+    if n < 1 or n > L:
+        raise ValueError(f"hqq_amd: kv_dequantize: n = {n} outside [1, {L}]")
+    shape = (B, n_kv, n, int(head_dim))
+    if out is None:
+        out = (torch.empty(shape, dtype=dt, device=bufs[0].device), torch.empty(shape, dtype=dt, device=bufs[0].device))
+    ko, vo = out
+    _dev(ko, vo)
+    if tuple(ko.shape) != shape or tuple(vo.shape) != shape or ko.dtype != dt or vo.dtype != dt or not ko.is_contiguous() or not vo.is_contiguous():
+        raise ValueError(f"hqq_amd: kv_dequantize's outputs are two dense tensors {shape} of the buffers' dtype")
+    with torch.cuda.device(ko.device):
+        rc = _C.lib().hqq_hip_kv_dequantize(nbits, *(_p(t) for t in bufs), B, n_kv, L, n, int(head_dim), gs, _p(ko), _p(vo), _dt(dt), _stream())
+    _C.check(rc, "hqq_hip_kv_dequantize")
+    return ko, vo
+
+
+def rope_kvq_cache_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, bufs, q_out: Tensor) -> Tensor:
+    """rope_cache_batched with a quantised cache write, one launch: q_out [B, n_heads * hd] = rotary(q) (rope_cache_batched's bits); rotary(k) and v
+    ([B, n_kv * hd]) are quantised on chip and stored at position pos[b] of sequence b's rows of the six buffers — the bits of rope_cache_batched into a dense
+    cache followed by kv_quantize of that row; a position outside the cache writes nothing"""
+    _dev(q, k, v, cos, sin, pos, q_out)
+    B = _batch_of(pos, "rope_kvq_cache_batched")
+    hd = cos.numel() // B
+    Bc, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, hd, "rope_kvq_cache_batched")
+    if Bc != B or cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
+            k.numel() != B * n_kv * hd or v.numel() != k.numel() or q_out.numel() != q.numel() or any(t.dtype != dt for t in (q, k, v, cos, sin, q_out)):
+        raise ValueError("hqq_amd: rope_kvq_cache_batched takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd] of the buffers' dtype, "
+                         "B the positions' count and the buffers' batch")
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_rope_kvq_cache_batched(nbits, _p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), B, _p(q_out), *(_p(t) for t in bufs), q.numel() // (B * hd),
+                                                     n_kv, hd, gs, L, _dt(dt), _stream())
+    _C.check(rc, "hqq_hip_rope_kvq_cache_batched")
+    return q_out
+
+
+def attn_decode_kvq_batched(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: float, head_dim: int, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_batched on a quantised cache: q / out [B, n_heads * hd], the six buffers, pos int64 [B] on the device; every row is rebuilt to the compute dtype
+    as it is loaded and the rest is attn_decode_batched's arithmetic in its order — the output has the bits of attn_decode_batched on kv_dequantize's tensors with
+    the same splits.  Nothing at or beyond pos[b] + 1 is read.  splits / workspace as in attn_decode_batched (attn_workspace_batched)."""
+    _dev(q, pos, out)
+    B = _batch_of(pos, "attn_decode_kvq_batched")
+    hd = int(head_dim)
+    Bc, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, hd, "attn_decode_kvq_batched")
+    if Bc != B or q.numel() % (B * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or q.dtype != dt or out.dtype != dt:
+        raise ValueError("hqq_amd: attn_decode_kvq_batched takes dense q / out [B, n_heads * head_dim] of the buffers' dtype, B the positions' count and the buffers' batch")
+    n_heads = q.numel() // (B * hd)
+    if splits > 1 and workspace is None:
+        workspace = attn_workspace_batched(q.device, B, n_heads, hd, splits)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_attn_decode_kvq_batched(nbits, _p(q), *(_p(t) for t in bufs), _p(pos), B, _p(out), n_heads, n_kv, hd, gs, L, float(scaling), _dt(dt),
+                                                      int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
+    _C.check(rc, "hqq_hip_attn_decode_kvq_batched")
+    return out
+
+
+def attn_decode_kvq(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: float, head_dim: int, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_kvq_batched for one sequence: buffers [n_kv, cache_len, ...] (or [1, n_kv, cache_len, ...]), pos int64[1]"""
+    return attn_decode_kvq_batched(q, tuple(t.view(1, *t.shape[-3:]) for t in bufs), _seq1(pos), out, scaling, head_dim, splits=splits, workspace=workspace)
+
+
 def argmax_advance_batched(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, pos: Tensor | None = None) -> None:
     """The back of a greedy decode step for B sequences in one launch, one workgroup per row (hqq_hip_argmax_advance_batched): next_tok[b] = logits[b].argmax() (the first
     index of the largest value; torch.argmax's tie and NaN rule), tok[b] = the same, pos[b] += 1 (each skipped when None).  logits [B, vocab] dense; int64 tensors of

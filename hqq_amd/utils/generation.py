@@ -88,14 +88,24 @@ class GraphedGreedyDecoder:
     Which of these the model gets is decided once, by llama_fused.resolve, and kept as `variant` (None: the model's own forward); the fused_* flags read it.
     generate() and generate_batch() prefill differently and keep different caches, but advance through the same routine (_advance) over a small state
     holder: the device tensors tok / next_tok / pos that the captured graphs read and write, the step (None: the model's own forward), the dictionary
-    its graphs are kept in with the key of an attended length in it, and the rule for that length."""
+    its graphs are kept in with the key of an attended length in it, and the rule for that length.
+    kv_cache: None (default) — HF's dense StaticCache, the code path as before.  "q8" / "q4" (opt-in): generate() and generate_batch() build a
+    kv_cache.QuantizedStaticCache (8 / 4 bits per element, rows of kv_group_size values — None: 64, or 32 when head_dim is 64 — quantised when they are
+    written) where they build a StaticCache; the prefill is the model's own forward into it, so every attended key and value is the stored, dequantised one.  A
+    Llama / Mistral model with attention="hip" then decodes through the fused step on the packed buffers (ops.rope_kvq_cache_batched,
+    ops.attn_decode_kvq_batched); everything else through the model's own forward on that cache, which dequantises it per layer.  `kv_cache_bytes` is what the
+    kept caches hold on the device."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
-                 qkv_bias: str = "model", lora: str = "model", moe: str = "model"):
+                 qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None):
         from transformers import StaticCache
         from . import llama_fused
+        from .kv_cache import check_kv_group_size, kv_cache_bits
         opted = opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
+        self.kv_bits = kv_cache_bits(kv_cache)   # (None: the dense StaticCache)
+        check_kv_group_size(kv_cache, kv_group_size)
+        self.kv_cache, self.kv_group_size = kv_cache, kv_group_size
         self.model = model.eval()
         self.axis0, self.qk_norm, self.qkv_bias, self.lora, self.moe = axis0, qk_norm, qkv_bias, lora, moe
         # the llama_fused.StepVariant this model decodes through (resolve's precedence among the opt-ins), or None: the model's own forward
@@ -124,6 +134,28 @@ class GraphedGreedyDecoder:
     fused_qkv_bias = property(lambda self: self.variant is not None and self.variant.family == "qwen2")
     fused_lora = property(lambda self: self.variant is not None and self.variant.lora)
     fused_moe = property(lambda self: self.variant is not None and self.variant.flags().get("moe", False))
+
+    def _new_cache(self):
+        """the static cache generate() and generate_batch() decode on: HF's dense StaticCache, or (kv_cache="q8" / "q4") the quantised one"""
+        if self.kv_bits is None:
+            return self._StaticCache(config=self.model.config, max_cache_len=self.max_cache_len)
+        from .kv_cache import QuantizedStaticCache
+        return QuantizedStaticCache(self.model.config, self.max_cache_len, self.kv_bits, self.kv_group_size)
+
+    def _step_keywords(self) -> dict:
+        """what the fused steps are told about the cache (nothing with the dense one: their call is the one it was)"""
+        return {} if self.kv_bits is None else {"kv_cache": self.kv_cache}
+
+    @property
+    def kv_cache_bytes(self) -> int:
+        """the device bytes of the KV caches kept between calls: generate()'s, and generate_batch()'s B-row and batch-1 prefill caches"""
+        def nbytes(c):
+            if c is None:
+                return 0
+            if hasattr(c, "nbytes"):
+                return c.nbytes
+            return sum(t.numel() * t.element_size() for lay in c.layers for t in (lay.keys, lay.values) if isinstance(t, Tensor))
+        return nbytes(self.cache) + sum(nbytes(st["cache"]) + nbytes(st["scratch"]) for st in self._batch.values())
 
     @property
     def graph(self):
@@ -215,7 +247,7 @@ class GraphedGreedyDecoder:
         if kept:
             self.cache.reset()
         else:
-            self.cache = self._StaticCache(config=self.model.config, max_cache_len=self.max_cache_len)
+            self.cache = self._new_cache()
         out = self.model(ids, past_key_values=self.cache, cache_position=torch.arange(T, device=self.device), use_cache=True)   # prefill
         first = self._pick(out.logits[:, -1])
         if kept:
@@ -227,7 +259,7 @@ class GraphedGreedyDecoder:
             if self.variant is not None:
                 try:   # (the plain axis-0 variant takes the separate glue kernels whatever `glue` says; with adapters `glue` goes through, and "folded" is refused)
                     self.step = self._fused_mod.FusedLlamaStep(self.model, self.cache, self.max_cache_len, attention=self.attention,
-                                                               glue="kernels" if self.fused_axis0 else self.glue, **self.variant.flags())
+                                                               glue="kernels" if self.fused_axis0 else self.glue, **self.variant.flags(), **self._step_keywords())
                 except ValueError:   # a cache layout / attention configuration the fused step does not restate: the model's own forward serves
                     self.step = None
             self.graphs = {}
@@ -372,6 +404,9 @@ class GraphedGreedyDecoder:
             out = self.model(x, past_key_values=scratch, cache_position=torch.arange(lengths[b], device=self.device), use_cache=True)
             firsts.append(self._pick(out.logits[:, -1]))
             for dst, src in zip(bc.layers, scratch.layers):
+                if self.kv_bits is not None:   # the six buffers of a quantised layer: rows are independent, so a copied row is the row a B-row prefill would have stored
+                    dst.copy_row(b, src, lengths[b])
+                    continue
                 dst.keys[b, :, :lengths[b]].copy_(src.keys[0, :, :lengths[b]])
                 dst.values[b, :, :lengths[b]].copy_(src.values[0, :, :lengths[b]])
         st["tok"].copy_(torch.cat(firsts, dim=0))
@@ -400,13 +435,13 @@ class GraphedGreedyDecoder:
         cfg = self.model.config
         n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
         hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-        cache = self._StaticCache(config=cfg, max_cache_len=self.max_cache_len)
+        cache = self._new_cache()
         cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
         try:   # (without the decoder's `glue`: the batched step has the one-launch front and back wherever they apply)
-            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, **self.variant.flags())
+            step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, **self.variant.flags(), **self._step_keywords())
         except ValueError:
             return None
-        st = {"B": B, "cache": cache, "scratch": self._StaticCache(config=cfg, max_cache_len=self.max_cache_len), "step": step,
+        st = {"B": B, "cache": cache, "scratch": self._new_cache(), "step": step,
               "tok": torch.zeros(B, 1, dtype=torch.int64, device=self.device), "next_tok": torch.zeros(B, 1, dtype=torch.int64, device=self.device),
               "pos": torch.zeros(B, dtype=torch.int64, device=self.device), "graphs": self.batch_graphs, "key": lambda kv: (B, kv),
               # the bucket of the LARGEST row position (batch_kv_bucket's rule): every row attends within it, each masked beyond its own position
@@ -450,10 +485,13 @@ class HFGenerator:
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
                  compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
-                 qkv_bias: str = "model", lora: str = "model", moe: str = "model"):
+                 qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
+        from .kv_cache import check_kv_group_size, kv_cache_bits
+        kv_cache_bits(kv_cache)
+        check_kv_group_size(kv_cache, kv_group_size)
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -466,7 +504,7 @@ class HFGenerator:
         self.use_graph = compile is not None
         self.compile_options = compile_options
         self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
-                                            qkv_bias=qkv_bias, lora=lora, moe=moe)
+                                            qkv_bias=qkv_bias, lora=lora, moe=moe, kv_cache=kv_cache, kv_group_size=kv_group_size)
         self.init()
 
     @staticmethod

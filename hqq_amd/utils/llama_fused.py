@@ -41,6 +41,10 @@ FAMILIES says what each family asks of an architecture, variant_supported(model,
 function, and resolve() is the precedence by which the decoders pick a variant.  Nothing but plain llama is taken without being asked.
 
 Only what the step needs is taken from the model: module weights and the HF StaticCache's tensors are used in place (nothing is copied).
+
+Independently of the variant, FusedLlamaStep(kv_cache="q8" / "q4") (opt-in) runs on a kv_cache.QuantizedStaticCache: ops.rope_kvq_cache_batched and
+ops.attn_decode_kvq_batched on the layers' six packed buffers take the place of the rotary-and-cache launch and the attention, with attention="hip" and for the
+variants whose rotary launch is plain rope_cache; every other combination is refused, and the decoders then run the model's own forward on that cache.
 """
 from __future__ import annotations
 
@@ -490,7 +494,7 @@ class FusedLlamaStep:
     every glue kernel gives the bits of the batch-1 kernel for sequence b alone, and the linears run at M = batch."""
 
     def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
-                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False):
+                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False, kv_cache: str | None = None):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -507,7 +511,12 @@ class FusedLlamaStep:
         moe (Mixtral; with qk_norm=True: Qwen3-MoE): the separate glue kernels (glue="folded" is refused), with ops.moe_router, ops.moe_gate_up and ops.moe_down
         on the HQQExperts stacks in the place of gate|up, silu_mul and down.  Per block, counted from __call__: add_rmsnorm, q|k|v, the rotary-and-cache launch,
         o, add_rmsnorm, moe_router, moe_gate_up, moe_down = 8 launches + the attention's (9 with attention="sdpa", whose function is one SDPA launch here).  The
-        router writes idx / weights into per-block buffers that the two expert launches read on the device: nothing is cast or copied in between."""
+        router writes idx / weights into per-block buffers that the two expert launches read on the device: nothing is cast or copied in between.
+        kv_cache: None — `cache` is an HF StaticCache, as above.  "q8" / "q4" (opt-in) — `cache` is a kv_cache.QuantizedStaticCache of that width, and per block the
+        step launches q|k|v (RMSNorm folded where `glue` allows), ops.rope_kvq_cache_batched (rotary, then the new key and value quantised into the six buffers),
+        ops.attn_decode_kvq_batched on the packed rows, o and the rest as above: no dense key / value tensor exists.  Only with attention="hip" (no SDPA runs on packed
+        bytes), up to 16 rows, and for the variants whose rotary launch is plain rope_cache (the Llama family's, Mixtral); neither the rotary-paired q / k layout nor
+        ops.rope_attn_decode_batched is used with it.  Everything else is a ValueError, which the decoders turn into the model's own forward on that cache."""
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
         self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
@@ -554,6 +563,16 @@ class FusedLlamaStep:
             "mixtral": ("rope_cache_batched", lambda b: ()),
             "qwen3_moe": ("qknorm_rope_cache_batched", lambda b: (b["attn"].q_norm.weight, b["attn"].k_norm.weight, b["attn"].q_norm.variance_epsilon, b["attn"].k_norm.variance_epsilon)),
         }[variant.family]
+        from .kv_cache import QuantizedStaticCache, kv_cache_bits
+        self.kv_bits = kv_cache_bits(kv_cache)   # (None: the dense cache)
+        if self.kv_bits is not None:
+            if attention != "hip" or self._rope_cache != "rope_cache_batched" or not 1 <= B <= 16:
+                raise ValueError("hqq_amd: the fused step reads a quantised KV cache only with attention='hip', for 1 .. 16 rows of a variant whose rotary launch is "
+                                 "rope_cache (Llama / Mistral / Mixtral); the model's own forward serves the rest on that cache")
+            if not isinstance(cache, QuantizedStaticCache) or cache.nbits != self.kv_bits:
+                raise ValueError(f"hqq_amd: kv_cache={kv_cache!r} needs a QuantizedStaticCache of {self.kv_bits} bits")
+        elif isinstance(cache, QuantizedStaticCache):
+            raise ValueError("hqq_amd: a QuantizedStaticCache needs the kv_cache keyword ('q8' / 'q4')")
         blocks = [lin + [None] * (7 - len(lin)) for lin in _decoder_linears(model, self.lora, self.moe)]   # (an MoE block: q k v o, and no gate up down)
         wrappers = _decoder_wrappers(model) if self.lora else [[None] * 7 for _ in blocks]
         can_fold = not self.lora and not self.moe and all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
@@ -582,13 +601,19 @@ class FusedLlamaStep:
         lora_ws_bytes = 0
         for li, (blk, (q, k, v, o, g, u, d)) in enumerate(zip(inner.layers, blocks)):
             lay = cache.layers[li]
-            if not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (B, self.n_kv, max_cache_len, self.hd) or \
+            if self.kv_bits is not None:   # the six buffers in the place of keys / values (kv_cache.QuantizedStaticLayer)
+                if not getattr(lay, "is_initialized", False) or tuple(lay.bufs[0].shape[:3]) != (B, self.n_kv, max_cache_len) or lay.k_head_dim != self.hd or lay.dtype != dt:
+                    raise ValueError(f"hqq_amd: the fused decode step needs an initialised QuantizedStaticCache of batch {B} and {max_cache_len} positions")
+                kv = {"kvq": lay.bufs}
+            elif not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (B, self.n_kv, max_cache_len, self.hd) or \
                     not lay.keys.is_contiguous() or not lay.values.is_contiguous():
                 raise ValueError(f"hqq_amd: the fused decode step needs an initialised HF StaticCache of batch {B} and {max_cache_len} positions")
+            else:
+                kv = {"kc": lay.keys, "vc": lay.values}
             self.blocks.append({
                 "attn": blk.self_attn, "n1": blk.input_layernorm, "n2": blk.post_attention_layernorm,
                 "qkv": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (q, k, v)], "qkv_opts": _gopts((q, k, v)), "qkv_nbits": q.nbits, "qkv_gs": q.group_size,
-                "o": o, "kc": lay.keys, "vc": lay.values, "len": lay.cumulative_length,
+                "o": o, **kv, "len": lay.cumulative_length,
                 # outputs of the launches (static addresses: the step is captured in a hipGraph)
                 "q": torch.empty(B, q.out_features, dtype=dt, device=dev), "k": torch.empty(B, k.out_features, dtype=dt, device=dev),
                 "v": torch.empty(B, v.out_features, dtype=dt, device=dev), "qr": torch.empty(B, self.n_heads, 1, self.hd, dtype=dt, device=dev),
@@ -711,7 +736,10 @@ class FusedLlamaStep:
                 ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
                 self._grouped(b, "qkv", [b["q"], b["k"], b["v"]])
                 self._adapters(b, "qkv", self.xn, [b["q"], b["k"], b["v"]])
-            if self.attention == "hip" and variant.family == "llama":   # rotary + cache write + attention: one launch
+            if self.kv_bits is not None:   # rotary + quantised cache write, then the attention on the packed rows
+                ops.rope_kvq_cache_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kvq"], b["qr"])
+                att = ops.attn_decode_kvq_batched(b["qr"], b["kvq"], pos, self.att, at.scaling, self.hd, splits=splits, workspace=self.attn_ws.get(splits))
+            elif self.attention == "hip" and variant.family == "llama":   # rotary + cache write + attention: one launch
                 att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
                                                    workspace=self.attn_ws.get(splits))
             else:
@@ -786,5 +814,6 @@ class FusedLlamaBatchStep(FusedLlamaStep):
     wherever the tables exist)"""
 
     def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False,
-                 lora: bool = False, moe: bool = False):
-        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
+                 lora: bool = False, moe: bool = False, kv_cache: str | None = None):
+        super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe,
+                         kv_cache=kv_cache)

@@ -553,6 +553,50 @@ int hqq_hip_moe_router(const void* x, const void* W, void* idx, void* weights, v
                        int round_weights, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A quantised static KV cache, 8 or 4 bits per element, and the decode-step launches that write and read it (csrc/kv_cache.hip).
+ * The format, this library's own — one rule per (sequence, kv head, position) row r of head_dim values, keys (after the rotary embedding) and values alike:
+ *     Quantizer.quantize(r.view(head_dim / gs, gs), nbits, group_size=gs, axis=1, optimize=False, round_zero=False, channel_wise=True)
+ * (hqq/core/quantize.py:102-154, as hqq_hip_quantize computes it without its solver), scale and zero then cast to the compute dtype T (`dtype`).  A row depends
+ * on no other row: it is quantised when it is written and never touched again.
+ *   8 bits: byte i of a row is level i.  4 bits: byte i is level[i] << 4 | level[i + head_dim / 2] (BitPack.pack_4bit_u8 on the [head_dim / gs, gs] levels).
+ *   kq, vq [batch, n_kv_heads, cache_len, head_dim * nbits / 8] uint8; k_scale, k_zero, v_scale, v_zero [batch, n_kv_heads, cache_len, head_dim / gs] of T.
+ *   dequantised value: round_T(round_T(q - zero) * scale), the two roundings of Quantizer.dequantize.
+ * Covered (hqq_hip_kv_covers: 1 / 0, pure host arithmetic; every entry point refuses the rest with HQQ_ERR_UNSUPPORTED "not covered" before anything is launched):
+ * fp16 / bf16; nbits 8 / 4; head_dim 64 / 128 / 256; gs 32 / 64 dividing head_dim, 2 gs <= head_dim at 4 bits; 1 <= cache_len <= 30000.
+ * The reference's arithmetic has no guard for a scale or zero beyond T's range (a group of near-equal values far from 0 in fp16 stores an infinite zero), and
+ * none is added.  Level buffers and dense rows 16-byte aligned (HQQ_ERR_ALIGN otherwise).  No atomics, no workspace but the attention's: two calls give the same bits.
+ *
+ * hqq_hip_kv_quantize: dense rows k, v [batch, n_kv_heads, T_, head_dim] of T — strides in ELEMENTS of the first three dimensions in k_strides / v_strides
+ *   (host int64[3], multiples of 8; a row's head_dim values are consecutive) — into positions p .. p + T_ - 1 of sequence b's rows, p = `start` (host) when
+ *   pos_dev is NULL, else pos_dev[b * pos_stride] (device int64; pos_stride 0: one position for every sequence, 1: one each).  A position outside
+ *   [0, cache_len) writes nothing; nothing but the addressed positions is written.
+ * hqq_hip_kv_dequantize: positions 0 .. n - 1 of every (sequence, kv head) -> dense k_out, v_out [batch, n_kv_heads, n, head_dim] of T.
+ * hqq_hip_rope_kvq_cache_batched: hqq_hip_rope_cache_batched's work — the same rotary arithmetic and the same q_out bits — with the rotated key and the value
+ *   row quantised on chip and stored at pos_dev[b]: the stored bits are those of hqq_hip_rope_cache_batched into a dense cache followed by hqq_hip_kv_quantize
+ *   of that row.  A position outside [0, cache_len) writes nothing to the buffers (q_out still is).  v 16-byte aligned.
+ * hqq_hip_attn_decode_kvq / _batched: hqq_hip_attn_decode / _batched on the six buffers.  Each row is rebuilt to T as it is loaded, and everything behind the
+ *   rebuild keeps the dense kernel's order (dot products, shuffles, score buffer, max / sum, accumulation, split records, the merging launch): the output is
+ *   BIT-IDENTICAL to hqq_hip_attn_decode_batched on hqq_hip_kv_dequantize's tensors with the same `splits`.  Nothing at or beyond position pos + 1 is read, in
+ *   levels or in meta.  splits / workspace: hqq_hip_attn_decode_workspace_bytes, the dense kernel's contract.
+ * The seven symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_kv_covers(int nbits, int64_t head_dim, int64_t group_size, int64_t cache_len, int dtype);
+int hqq_hip_kv_quantize(int nbits, const void* k, const void* v, const int64_t* k_strides, const int64_t* v_strides, int64_t batch, int64_t n_kv_heads, int64_t T_,
+                        int64_t head_dim, int64_t group_size, int64_t start, const int64_t* pos_dev, int64_t pos_stride, void* kq, void* k_scale, void* k_zero, void* vq,
+                        void* v_scale, void* v_zero, int64_t cache_len, int dtype, void* stream);
+int hqq_hip_kv_dequantize(int nbits, const void* kq, const void* k_scale, const void* k_zero, const void* vq, const void* v_scale, const void* v_zero, int64_t batch,
+                          int64_t n_kv_heads, int64_t cache_len, int64_t n, int64_t head_dim, int64_t group_size, void* k_out, void* v_out, int dtype, void* stream);
+int hqq_hip_rope_kvq_cache_batched(int nbits, const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch,
+                                   void* q_out, void* kq, void* k_scale, void* k_zero, void* vq, void* v_scale, void* v_zero, int64_t n_heads, int64_t n_kv_heads,
+                                   int64_t head_dim, int64_t group_size, int64_t cache_len, int dtype, void* stream);
+int hqq_hip_attn_decode_kvq(int nbits, const void* q, const void* kq, const void* k_scale, const void* k_zero, const void* vq, const void* v_scale, const void* v_zero,
+                            const int64_t* pos_dev, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t group_size, int64_t cache_len, float scaling,
+                            int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream);
+int hqq_hip_attn_decode_kvq_batched(int nbits, const void* q, const void* kq, const void* k_scale, const void* k_zero, const void* vq, const void* v_scale,
+                                    const void* v_zero, const int64_t* pos_dev, int64_t batch, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
+                                    int64_t group_size, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
