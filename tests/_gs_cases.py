@@ -288,7 +288,10 @@ def coded_bias(c: Case, li: int = 0):
 # ---- activations ---------------------------------------------------------------------------------------------------------------------
 def edges(c: Case):
     """the k at which a kernel's own structure changes: loads and units of the row-per-wave kernel, the first block of every wave's K slice of
-    the 16-row-tile kernel, the K tiles of the output-tile kernels"""
+    the 16-row-tile kernel, the K tiles of the output-tile kernels; a case of another table's own route brings its rule along as own_edges()"""
+    own = getattr(c, "own_edges", None)
+    if own is not None and own() is not None:
+        return own()
     if c.route == "rowwise":
         return list(range(GV_KSTEP, c.K, GV_KSTEP))
     if c.route == "mfma16":
@@ -329,10 +332,14 @@ def activations(c: Case, family: str) -> np.ndarray:
 FAMILIES = ("onehot", "group", "ones")
 
 
+def launch_index(c: Case, rows: int) -> np.ndarray:
+    """which row of a probe set of `rows` rows every row of its whole launches of M rows is (the last launch is filled from the top)"""
+    return np.arange(-(-rows // c.M) * c.M) % rows
+
+
 def launches(c: Case, X: np.ndarray) -> np.ndarray:
     """the rows of X as whole launches of M rows: [n_launches, M, K] (the last launch is filled from the top)"""
-    n = -(-X.shape[0] // c.M)
-    return np.take(X, np.arange(n * c.M) % X.shape[0], axis=0).reshape(n, c.M, c.K)
+    return np.take(X, launch_index(c, X.shape[0]), axis=0).reshape(-1, c.M, c.K)
 
 
 def expected(c: Case, W: np.ndarray, X: np.ndarray, bias) -> np.ndarray:
@@ -372,7 +379,7 @@ def reference_weights(oracle, c: Case, P, s, z, li: int = 0):
     N = c.Ns[li]
     if c.dt == "f16":
         return oracle.dequantize(c.nbits, P, s.numpy(), z.numpy(), N, c.K, c.gs, 1).astype(np.float32)
-    U = oracle.unpack(c.nbits, P).astype(np.float32)
+    U = oracle.unpack(c.nbits, P)[:N * c.K // c.gs].astype(np.float32)   # (the slice drops the 3-bit container's padding rows; a no-op at the byte widths)
     s32, z32 = s.float().numpy().reshape(-1, 1), z.float().numpy().reshape(-1, 1)
     rb = lambda a: (_bf16_bits(a).astype(np.uint32) << 16).view(np.float32)   # noqa: E731
     return rb(rb(U - z32) * s32).reshape(N, c.K)
