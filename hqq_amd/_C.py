@@ -100,6 +100,12 @@ SYMBOLS = {
     "hqq_hip_attn_decode_kvq": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
     "hqq_hip_attn_decode_kvq_batched": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz,
                                                _vp]),
+    # speculative greedy decoding: R rows of ONE sequence on its batch-1 cache, the n-gram proposer and the accept / commit step (csrc/block.hip, csrc/spec.hip;
+    # added at ABI 9 without a bump: nothing that existed changed)
+    "hqq_hip_rope_cache_shared": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
+    "hqq_hip_attn_decode_shared": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
+    "hqq_hip_spec_propose": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "hqq_hip_spec_accept": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

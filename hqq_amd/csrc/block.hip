@@ -117,12 +117,14 @@ __global__ __launch_bounds__(512) void add_rmsnorm_kernel(uint16_t* __restrict__
 }
 
 // ---- rotary embedding of q and k, KV-cache write.  One thread per (head, i < hd / 2): elements i and i + hd / 2 of a head.
-//      blockIdx.y: the sequence of a batch (hqq_hip_rope_cache_batched) — every tensor advances by one sequence's extent, the arithmetic is the same ----
+//      blockIdx.y: the sequence of a batch (hqq_hip_rope_cache_batched) — every tensor advances by one sequence's extent, the arithmetic is the same.
+//      cache_row: the elements between two rows' caches, n_kv * cache_len * hd; 0 (hqq_hip_rope_cache_shared): the rows are positions of ONE sequence
+//      and write into the one cache [n_kv, cache_len, hd], each at its own pos ----
 template <bool BF>
 __global__ __launch_bounds__(256) void rope_cache_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
                                                          const uint16_t* __restrict__ cosv, const uint16_t* __restrict__ sinv, const int64_t* __restrict__ pos,
                                                          uint16_t* __restrict__ q_out, uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
-                                                         int n_heads, int n_kv, int hd, int cache_len) {
+                                                         int n_heads, int n_kv, int hd, int cache_len, int64_t cache_row) {
   const int half = hd / 2;
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   const int total = (n_heads + n_kv) * half;
@@ -135,8 +137,8 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(const uint16_t* __restr
   cosv += row * hd;
   sinv += row * hd;
   pos += row;
-  k_cache += row * n_kv * cache_len * hd;
-  v_cache += row * n_kv * cache_len * hd;
+  k_cache += row * cache_row;
+  v_cache += row * cache_row;
   const int head = id / half, i = id - head * half;
   const bool is_k = head >= n_heads;
   const uint16_t* src = is_k ? k + static_cast<int64_t>(head - n_heads) * hd : q + static_cast<int64_t>(head) * hd;
@@ -298,28 +300,30 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const uint16_t* __restric
 //      KV head's new key itself (rope_cache_kernel's arithmetic, rounding for rounding), uses the new key / value from LDS for position pos — the
 //      cache is only read below pos, so no workgroup depends on another's write — and the first query head of each KV head writes them to the cache.
 //      blockIdx.z: the sequence of a batch (the *_batched entry points) — its own q / k / v rows, cache [n_kv, L, HD], position and output row;
-//      its records are those of head b n_heads + h ----
+//      its records are those of head b n_heads + h.
+//      cache_row: the elements between two sequences' caches, n_kv * L * HD; 0 (hqq_hip_attn_decode_shared, ROPE = false only): the rows are queries of ONE
+//      sequence on the one cache [n_kv, L, HD], row i attending over its own pos[i] + 1 keys — everything else, and so every bit of a row, is unchanged ----
 template <int HD, bool ROPE, bool BF>
 __global__ __launch_bounds__(512) void attn_decode_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc_in, const uint16_t* __restrict__ vc_in,
                                                           const int64_t* __restrict__ pos, uint16_t* __restrict__ out, int n_heads, int n_kv, int L, float scaling,
                                                           const uint16_t* __restrict__ k_raw, const uint16_t* __restrict__ v_raw, const uint16_t* __restrict__ cosv,
                                                           const uint16_t* __restrict__ sinv, uint16_t* __restrict__ kc_out, uint16_t* __restrict__ vc_out,
-                                                          int S, float* __restrict__ ws) {
+                                                          int S, float* __restrict__ ws, int64_t cache_row) {
   using E = El<BF>;
   {
     const int64_t row = blockIdx.z;
     q += row * n_heads * HD;
     out += row * n_heads * HD;
-    kc_in += row * n_kv * L * HD;
-    vc_in += row * n_kv * L * HD;
+    kc_in += row * cache_row;
+    vc_in += row * cache_row;
     pos += row;
     if constexpr (ROPE) {
       k_raw += row * n_kv * HD;
       v_raw += row * n_kv * HD;
       cosv += row * HD;
       sinv += row * HD;
-      kc_out += row * n_kv * L * HD;
-      vc_out += row * n_kv * L * HD;
+      kc_out += row * cache_row;
+      vc_out += row * cache_row;
     }
     if (S > 1) ws += row * n_heads * S * (HD + 2);
   }
@@ -630,7 +634,7 @@ static inline bool batch_ok(int64_t batch, const char* who) {
   return false;
 }
 
-static int rope_cache_run(const char* who, const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out,
+static int rope_cache_run(const char* who, bool shared, const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out,
                           void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
   clear_stale_error();
   if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
@@ -638,11 +642,12 @@ static int rope_cache_run(const char* who, const void* q, const void* k, const v
   if (!q || !k || !v || !cos || !sin || !pos_dev || !q_out || !k_cache || !v_cache || n_heads < 1 || n_kv_heads < 1 || head_dim < 2 || head_dim % 2 || cache_len < 1 ||
       (n_heads + n_kv_heads) * head_dim > INT32_MAX || cache_len > INT32_MAX) { set_error("%s: bad arguments", who); return HQQ_ERR_SHAPE; }
   const int64_t total = (n_heads + n_kv_heads) * (head_dim / 2);
+  const int64_t cache_row = shared ? 0 : n_kv_heads * cache_len * head_dim;
 #define HQQ_ROPE_GO(BFV)                                                                                                                          \
   hipLaunchKernelGGL(rope_cache_kernel<BFV>, dim3(static_cast<unsigned>((total + 255) / 256), static_cast<unsigned>(batch)), dim3(256), 0, as_stream(stream), \
                      static_cast<cu16>(q), static_cast<cu16>(k),                                                                                  \
                      static_cast<cu16>(v), static_cast<cu16>(cos), static_cast<cu16>(sin), pos_dev, static_cast<u16>(q_out), static_cast<u16>(k_cache),  \
-                     static_cast<u16>(v_cache), static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(head_dim), static_cast<int>(cache_len))
+                     static_cast<u16>(v_cache), static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(head_dim), static_cast<int>(cache_len), cache_row)
   if (dtype == HQQ_BF16) HQQ_ROPE_GO(true);
   else HQQ_ROPE_GO(false);
 #undef HQQ_ROPE_GO
@@ -653,12 +658,17 @@ extern "C" {
 
 int hqq_hip_rope_cache(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, void* q_out, void* k_cache,
                        void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
-  return rope_cache_run("hqq_hip_rope_cache", q, k, v, cos, sin, pos_dev, 1, q_out, k_cache, v_cache, n_heads, n_kv_heads, head_dim, cache_len, dtype, stream);
+  return rope_cache_run("hqq_hip_rope_cache", false, q, k, v, cos, sin, pos_dev, 1, q_out, k_cache, v_cache, n_heads, n_kv_heads, head_dim, cache_len, dtype, stream);
 }
 
 int hqq_hip_rope_cache_batched(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* q_out,
                                void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
-  return rope_cache_run("hqq_hip_rope_cache_batched", q, k, v, cos, sin, pos_dev, batch, q_out, k_cache, v_cache, n_heads, n_kv_heads, head_dim, cache_len, dtype, stream);
+  return rope_cache_run("hqq_hip_rope_cache_batched", false, q, k, v, cos, sin, pos_dev, batch, q_out, k_cache, v_cache, n_heads, n_kv_heads, head_dim, cache_len, dtype, stream);
+}
+
+int hqq_hip_rope_cache_shared(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t rows, void* q_out,
+                              void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream) {
+  return rope_cache_run("hqq_hip_rope_cache_shared", true, q, k, v, cos, sin, pos_dev, rows, q_out, k_cache, v_cache, n_heads, n_kv_heads, head_dim, cache_len, dtype, stream);
 }
 
 int hqq_hip_qknorm_rope_cache_batched(const void* q, const void* k, const void* v, const void* q_weight, const void* k_weight, float q_eps, float k_eps, const void* cos,
@@ -726,13 +736,13 @@ int hqq_hip_silu_mul(const void* gate, const void* up, void* out, int64_t n, int
   return check_launch("hqq_hip_silu_mul");
 }
 
-static int attn_decode_run(const char* who, bool rope, const void* q, const void* k_raw, const void* v_raw, const void* cosv, const void* sinv, const int64_t* pos_dev,
+static int attn_decode_run(const char* who, bool rope, bool shared, const void* q, const void* k_raw, const void* v_raw, const void* cosv, const void* sinv, const int64_t* pos_dev,
                            int64_t batch, void* k_cache, void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling,
                            int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
   clear_stale_error();
   if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
   if (!batch_ok(batch, who)) return HQQ_ERR_SHAPE;
-  if (!q || !k_cache || !v_cache || !pos_dev || !out || (rope && (!k_raw || !v_raw || !cosv || !sinv)) || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads ||
+  if (!q || !k_cache || !v_cache || !pos_dev || !out || (rope && (shared || !k_raw || !v_raw || !cosv || !sinv)) || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads ||
       cache_len < 1 || cache_len > 30000 || n_heads > INT32_MAX || batch * n_heads > INT32_MAX) {
     set_error("%s: bad arguments (cache_len <= 30000, n_heads a multiple of n_kv_heads)", who);
     return HQQ_ERR_SHAPE;
@@ -751,6 +761,7 @@ static int attn_decode_run(const char* who, bool rope, const void* q, const void
     return HQQ_ERR_SHAPE;
   }
   float* wsf = static_cast<float*>(workspace);
+  const int64_t cache_row = shared ? 0 : n_kv_heads * cache_len * head_dim;   // (shared: every row's queries on the one cache)
   const int lds = 64 + HD * 6 + 8 * HD * 4 + static_cast<int>((cache_len + S - 1) / S + 8) * 4;
   const dim3 grid(static_cast<unsigned>(n_heads), static_cast<unsigned>(S), static_cast<unsigned>(batch)), block(512);
   static LdsRaised raised[12];
@@ -762,7 +773,8 @@ static int attn_decode_run(const char* who, bool rope, const void* q, const void
     hipLaunchKernelGGL((attn_decode_kernel<HDV, RP, BFV>), grid, block, lds, as_stream(stream), static_cast<cu16>(q), static_cast<cu16>(k_cache), \
                        static_cast<cu16>(v_cache), pos_dev, static_cast<u16>(out), static_cast<int>(n_heads), static_cast<int>(n_kv_heads),  \
                        static_cast<int>(cache_len), scaling, static_cast<cu16>(k_raw), static_cast<cu16>(v_raw),                            \
-                       static_cast<cu16>(cosv), static_cast<cu16>(sinv), static_cast<u16>(k_cache), static_cast<u16>(v_cache), S, wsf);    \
+                       static_cast<cu16>(cosv), static_cast<cu16>(sinv), static_cast<u16>(k_cache), static_cast<u16>(v_cache), S, wsf,     \
+                       cache_row);                                                                                                         \
   } while (0)
 #define HQQ_ATTN_HD(RP, BFV, BASE)                                                                                                         \
   do {                                                                                                                                     \
@@ -789,29 +801,36 @@ size_t hqq_hip_attn_decode_workspace_bytes(int64_t n_heads, int64_t head_dim, in
 
 int hqq_hip_attn_decode(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, void* out, int64_t n_heads, int64_t n_kv_heads,
                         int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
-  return attn_decode_run("hqq_hip_attn_decode", false, q, nullptr, nullptr, nullptr, nullptr, pos_dev, 1, const_cast<void*>(k_cache), const_cast<void*>(v_cache), out,
+  return attn_decode_run("hqq_hip_attn_decode", false, false, q, nullptr, nullptr, nullptr, nullptr, pos_dev, 1, const_cast<void*>(k_cache), const_cast<void*>(v_cache), out,
                          n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype, splits, workspace, workspace_bytes, stream);
 }
 
 int hqq_hip_rope_attn_decode(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, void* k_cache, void* v_cache, void* out,
                              int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  return attn_decode_run("hqq_hip_rope_attn_decode", true, q, k, v, cos, sin, pos_dev, 1, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype,
+  return attn_decode_run("hqq_hip_rope_attn_decode", true, false, q, k, v, cos, sin, pos_dev, 1, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype,
                          splits, workspace, workspace_bytes, stream);
 }
 
 int hqq_hip_attn_decode_batched(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, int64_t batch, void* out, int64_t n_heads,
                                 int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-  return attn_decode_run("hqq_hip_attn_decode_batched", false, q, nullptr, nullptr, nullptr, nullptr, pos_dev, batch, const_cast<void*>(k_cache),
+  return attn_decode_run("hqq_hip_attn_decode_batched", false, false, q, nullptr, nullptr, nullptr, nullptr, pos_dev, batch, const_cast<void*>(k_cache),
                          const_cast<void*>(v_cache), out, n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype, splits, workspace, workspace_bytes, stream);
 }
 
 int hqq_hip_rope_attn_decode_batched(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t batch, void* k_cache,
                                      void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype,
                                      int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
-  return attn_decode_run("hqq_hip_rope_attn_decode_batched", true, q, k, v, cos, sin, pos_dev, batch, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, cache_len,
+  return attn_decode_run("hqq_hip_rope_attn_decode_batched", true, false, q, k, v, cos, sin, pos_dev, batch, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, cache_len,
                          scaling, dtype, splits, workspace, workspace_bytes, stream);
+}
+
+int hqq_hip_attn_decode_shared(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, int64_t rows, void* out, int64_t n_heads,
+                               int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  return attn_decode_run("hqq_hip_attn_decode_shared", false, true, q, nullptr, nullptr, nullptr, nullptr, pos_dev, rows, const_cast<void*>(k_cache),
+                         const_cast<void*>(v_cache), out, n_heads, n_kv_heads, head_dim, cache_len, scaling, dtype, splits, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1410,6 +1410,93 @@ def rope_attn_decode(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, 
     return rope_attn_decode_batched(q, k, v, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), out, scaling, splits=splits, workspace=workspace)
 
 
+# ---- speculative greedy decoding (csrc/block.hip's *_shared entry points, csrc/spec.hip; include/hqq_hip.h hqq_hip_spec_*): R rows that are R consecutive
+#      positions of ONE sequence on its batch-1 cache, the n-gram proposer in front of them and the accept / commit step behind ----------------------------
+SPEC_MAX_ROWS = 16     # rows of a verify step (the decode linears' GEMV_MAX_M)
+SPEC_MAX_NGRAM = 4
+
+
+def _shared_cache(who: str, k_cache: Tensor, v_cache: Tensor):
+    """one sequence's caches [n_kv, L, hd] or [1, n_kv, L, hd] (a batch-1 StaticCache's tensors): (n_kv, L, hd)"""
+    if k_cache.dim() not in (3, 4) or (k_cache.dim() == 4 and k_cache.shape[0] != 1) or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or \
+            not v_cache.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes ONE sequence's dense caches [n_kv_heads, cache_len, head_dim] (or [1, ...])")
+    return tuple(int(x) for x in k_cache.shape[-3:])
+
+
+def rope_cache_shared(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
+    """rope_cache_batched for R rows of ONE sequence (hqq_hip_rope_cache_shared): q / q_out [R, n_heads * hd], k / v [R, n_kv * hd], cos / sin [R, hd], pos int64
+    [R]; the caches are that sequence's [n_kv, L, hd] (or [1, n_kv, L, hd]).  Row i's rotated key and its value go to slot pos[i], q_out[i] has the bits of the
+    batch-1 rope_cache call; a position outside the cache writes nothing.  The positions of a call must be distinct: equal ones leave that slot unspecified."""
+    _dev(q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
+    R = _batch_of(pos, "rope_cache_shared")
+    n_kv, L, hd = _shared_cache("rope_cache_shared", k_cache, v_cache)
+    if cos.numel() != R * hd or sin.numel() != R * hd or any(t.numel() % (R * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
+            k.numel() != R * n_kv * hd or v.numel() != k.numel() or q_out.numel() != q.numel() or \
+            any(t.dtype != q.dtype for t in (k, v, cos, sin, k_cache, v_cache, q_out)):
+        raise ValueError("hqq_amd: rope_cache_shared takes dense q / q_out [R, n_heads * hd], k / v [R, n_kv_heads * hd] and cos / sin [R, hd] of the caches' dtype")
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_rope_cache_shared(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), R, _p(q_out), _p(k_cache), _p(v_cache), q.numel() // (R * hd), n_kv, hd, L,
+                                                _dt(q.dtype), _stream())
+    _C.check(rc, "hqq_hip_rope_cache_shared")
+    return q_out
+
+
+def attn_decode_shared(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_batched for R queries of ONE sequence against that sequence's caches [n_kv, L, hd] (or [1, n_kv, L, hd]) (hqq_hip_attn_decode_shared): q / out
+    [R, n_heads * hd], pos int64 [R]; row i attends over keys [0, pos[i]] and is bit-identical to attn_decode with row i's query and position and the same
+    splits.  Splits and workspace as attn_decode_batched at R rows (attn_workspace_batched(device, R, ...))."""
+    _dev(q, k_cache, v_cache, pos, out)
+    R = _batch_of(pos, "attn_decode_shared")
+    n_kv, L, hd = _shared_cache("attn_decode_shared", k_cache, v_cache)
+    if q.numel() % (R * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or any(t.dtype != q.dtype for t in (k_cache, v_cache, out)):
+        raise ValueError("hqq_amd: attn_decode_shared takes dense q / out [R, n_heads * head_dim] of the caches' dtype")
+    n_heads = q.numel() // (R * hd)
+    if splits > 1 and workspace is None:
+        workspace = attn_workspace_batched(q.device, R, n_heads, hd, splits)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_attn_decode_shared(_p(q), _p(k_cache), _p(v_cache), _p(pos), R, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
+                                                 int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
+    _C.check(rc, "hqq_hip_attn_decode_shared")
+    return out
+
+
+def _i64_dev(who: str, **tensors) -> None:
+    for name, t in tensors.items():
+        if not isinstance(t, Tensor) or t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError(f"hqq_amd: {who} takes `{name}` as a dense int64 tensor on the device")
+
+
+def spec_propose(hist: Tensor, p: Tensor, tok: Tensor, pos: Tensor, ngram_max: int = 3) -> None:
+    """The n-gram proposer of speculative decoding, one workgroup (hqq_hip_spec_propose).  hist int64 [cap]: the sequence's tokens; p: a device int64 scalar, the index
+    of the last committed one.  Writes tok / pos (int64, R = 2..16 elements each): tok[0] = hist[p], pos[i] = p + i, tok[1:] the continuation of the latest earlier
+    occurrence of the longest n-gram (n <= ngram_max <= 4) the history ends with, extended periodically; hist[p] everywhere when nothing matches.  Graph-replay safe."""
+    _dev(hist, p, tok, pos)
+    _i64_dev("spec_propose", hist=hist, p=p, tok=tok, pos=pos)
+    R = pos.numel()
+    if hist.dim() != 1 or p.numel() != 1 or tok.numel() != R or not 2 <= R <= SPEC_MAX_ROWS or isinstance(ngram_max, bool) or not isinstance(ngram_max, int) or \
+            not 0 <= ngram_max <= SPEC_MAX_NGRAM:
+        raise ValueError(f"hqq_amd: spec_propose takes a 1-D history, a scalar p, tok / pos of 2..{SPEC_MAX_ROWS} elements each and ngram_max in 0..{SPEC_MAX_NGRAM}")
+    with torch.cuda.device(hist.device):
+        rc = _C.lib().hqq_hip_spec_propose(_p(hist), hist.numel(), _p(p), R, ngram_max, _p(tok), _p(pos), _stream())
+    _C.check(rc, "hqq_hip_spec_propose")
+
+
+def spec_accept(g: Tensor, tok: Tensor, hist: Tensor, p: Tensor, last: Tensor, eos: Tensor, done: Tensor, steps: Tensor, tokens: Tensor) -> None:
+    """The accept / commit step of speculative decoding, one wave (hqq_hip_spec_accept).  g / tok int64 of R = 2..16 elements: the rows' argmax and what the rows
+    were fed; hist int64 [cap]; p, last, eos, done, steps, tokens: device int64 scalars (last: the index of the last token to emit; eos: -1 for none).  Frozen
+    (done != 0 or p >= last): nothing changes.  Otherwise the longest prefix of drafts the model confirms — tok[i] == g[i - 1] —, cut at `last` and at the first
+    EOS (done = 1), is committed: hist[p + 1 + i] = g[i] for i = 0..a, p += a + 1, steps += 1, tokens += a + 1.  Graph-replay safe."""
+    _dev(g, tok, hist, p, last, eos, done, steps, tokens)
+    _i64_dev("spec_accept", g=g, tok=tok, hist=hist, p=p, last=last, eos=eos, done=done, steps=steps, tokens=tokens)
+    R = g.numel()
+    if hist.dim() != 1 or tok.numel() != R or not 2 <= R <= SPEC_MAX_ROWS or any(t.numel() != 1 for t in (p, last, eos, done, steps, tokens)):
+        raise ValueError(f"hqq_amd: spec_accept takes g / tok of 2..{SPEC_MAX_ROWS} elements each, a 1-D history and scalar p / last / eos / done / steps / tokens")
+    with torch.cuda.device(hist.device):
+        rc = _C.lib().hqq_hip_spec_accept(_p(g), _p(tok), R, _p(hist), hist.numel(), _p(p), _p(last), _p(eos), _p(done), _p(steps), _p(tokens), _stream())
+    _C.check(rc, "hqq_hip_spec_accept")
+
+
 # ---- the quantised static KV cache (csrc/kv_cache.hip; include/hqq_hip.h states the format).  `bufs` is a layer's six buffers in the order
 #      (kq, k_scale, k_zero, vq, v_scale, v_zero): kq / vq [B, n_kv, L, head_dim * nbits / 8] uint8, the four meta tensors [B, n_kv, L, head_dim / gs] of the
 #      compute dtype; nbits and the group size are read off their shapes against head_dim ----------------------------------------------------------------------

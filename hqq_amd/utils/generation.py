@@ -54,6 +54,18 @@ def eos_lengths(rows, eos_token_id, n: int) -> list:
     return out
 
 
+def check_speculation(speculate, draft_rows, ngram_max, do_sample) -> None:
+    """the speculative-decoding keywords of GraphedGreedyDecoder and HFGenerator: speculate None or "ngram", draft_rows an integer in 2 .. ops.SPEC_MAX_ROWS,
+    ngram_max an integer in 0 .. ops.SPEC_MAX_NGRAM, and no sampling with speculation (acceptance is the greedy rule); ValueError naming the first that is not"""
+    if speculate not in (None, "ngram"):
+        raise ValueError("speculate: None or 'ngram'")
+    for name, value, lo, hi in (("draft_rows", draft_rows, 2, ops.SPEC_MAX_ROWS), ("ngram_max", ngram_max, 0, ops.SPEC_MAX_NGRAM)):
+        if isinstance(value, bool) or not isinstance(value, int) or not lo <= value <= hi:
+            raise ValueError(f"{name}: an integer in {lo} .. {hi}")
+    if speculate is not None and do_sample:
+        raise ValueError("speculate: greedy decoding only (do_sample=True draws tokens the n-gram drafts cannot be verified against)")
+
+
 def opt_ins(**keywords) -> set:
     """the decode-step opt-in keywords of GraphedGreedyDecoder and HFGenerator (axis0, qk_norm, qkv_bias, lora, moe), each "model" or "fused": the names of those
     set to "fused" (what llama_fused.resolve takes); ValueError naming the first keyword with another value"""
@@ -94,15 +106,25 @@ class GraphedGreedyDecoder:
     written) where they build a StaticCache; the prefill is the model's own forward into it, so every attended key and value is the stored, dequantised one.  A
     Llama / Mistral model with attention="hip" then decodes through the fused step on the packed buffers (ops.rope_kvq_cache_batched,
     ops.attn_decode_kvq_batched); everything else through the model's own forward on that cache, which dequantises it per layer.  `kv_cache_bytes` is what the
-    kept caches hold on the device."""
+    kept caches hold on the device.
+    speculate: None (default) — one token per step, the code path as before.  "ngram" (opt-in; greedy only): generate() emits SEVERAL tokens per pass over the
+    weights by prompt-lookup speculation.  One captured step is ops.spec_propose (the last committed token + draft_rows - 1 guesses: the continuation of the latest
+    earlier occurrence of the sequence's last n-gram, n <= ngram_max), the verify step (llama_fused.FusedLlamaStep(batch=draft_rows, verify=True): the rows are
+    consecutive positions of the one sequence on its batch-1 cache), the rows' argmax and ops.spec_accept (the guesses the model's own argmax confirms are
+    committed: history, position, EOS flag and counters, all on the device).  The host replays `check_every` steps, then reads the position and the flag in one
+    copy.  The tokens are the greedy tokens of the verify step's arithmetic (the R-row kernels round differently from the one-row kernels, as generate_batch's do).
+    Served where that step is (`speculating`): a Llama / Mistral model, attention="hip", the dense cache, llama_fused.supports_speculation(model, draft_rows);
+    everything else decodes as before.  `spec_stats` holds the last call's {"steps", "tokens"}; generate_batch is untouched."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
-                 qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None):
+                 qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
+                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3):
         from transformers import StaticCache
         from . import llama_fused
         from .kv_cache import check_kv_group_size, kv_cache_bits
         opted = opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
+        check_speculation(speculate, draft_rows, ngram_max, do_sample)
         self.kv_bits = kv_cache_bits(kv_cache)   # (None: the dense StaticCache)
         check_kv_group_size(kv_cache, kv_group_size)
         self.kv_cache, self.kv_group_size = kv_cache, kv_group_size
@@ -126,6 +148,12 @@ class GraphedGreedyDecoder:
         self._state = None     # the state holder of generate(): its tok / next_tok / pos are self.tok / .next_tok / .pos, its step self.step, its graphs self.graphs
         self._batch = {}       # B -> the state holder of generate_batch at B rows (with its B-row cache and its batch-1 prefill cache)
         self.batch_graphs = {} # (B, attended cache length) -> captured batched step
+        # speculative decoding (opt-in): which route generate() takes is known here, as the fused_* flags are; a cache the verify step refuses turns it off in generate()
+        self.speculate, self.draft_rows, self.ngram_max = speculate, int(draft_rows), int(ngram_max)
+        self.speculating = bool(speculate is not None and self.fused and attention == "hip" and self.kv_bits is None and max_cache_len <= ops.KV_MAX_LEN
+                                and llama_fused.supports_speculation(model, self.draft_rows))
+        self._spec = None      # the state holder of the speculative route (its own cache, verify step, history, device scalars and graphs)
+        self.spec_stats = {"steps": 0, "tokens": 0}
 
     # `variant` as flags (what bench.py, the tools and the tests read): `fused` is plain Llama's, the others are the opt-in variants, one true at most
     fused = property(lambda self: self.variant is not None and not any(self.variant.flags().values()))
@@ -155,7 +183,8 @@ class GraphedGreedyDecoder:
             if hasattr(c, "nbytes"):
                 return c.nbytes
             return sum(t.numel() * t.element_size() for lay in c.layers for t in (lay.keys, lay.values) if isinstance(t, Tensor))
-        return nbytes(self.cache) + sum(nbytes(st["cache"]) + nbytes(st["scratch"]) for st in self._batch.values())
+        return nbytes(self.cache) + sum(nbytes(st["cache"]) + nbytes(st["scratch"]) for st in self._batch.values()) + \
+            (0 if self._spec is None else nbytes(self._spec["cache"]))   # (the speculative route decodes on a cache of its own)
 
     @property
     def graph(self):
@@ -187,6 +216,11 @@ class GraphedGreedyDecoder:
     def _decode_once(self, st, kv_len=None) -> None:
         """one whole transition of every row: logits at pos -> next_tok, tok = next_tok, pos += 1 (all on the device, so the captured graph carries the loop state forward by itself)"""
         tok, next_tok, pos = st["tok"], st["next_tok"], st["pos"]
+        if st.get("verify"):   # the speculative route: propose -> verify step -> row argmax -> accept; hist / p / done / the counters carry the loop forward
+            ops.spec_propose(st["hist"], st["p"], tok, pos, self.ngram_max)
+            ops.argmax_advance_batched(st["step"](tok, pos, kv_len), next_tok, None, None)
+            ops.spec_accept(next_tok, tok, st["hist"], st["p"], st["last"], st["eos"], st["done"], st["steps"], st["tokens"])
+            return
         if st["step"] is not None:
             logits = st["step"](tok, pos, kv_len)
             if st["argmax_advance"] and not self.do_sample and logits.dtype in (torch.float16, torch.bfloat16) and logits.is_contiguous():
@@ -228,6 +262,7 @@ class GraphedGreedyDecoder:
         self._state = None
         self._batch = {}
         self.batch_graphs = {}
+        self._spec = None
 
     @torch.no_grad()
     def generate(self, input_ids: Tensor, max_new_tokens: int, use_graph: bool = True, eos_token_id: int | None = None, check_every: int = 16) -> Tensor:
@@ -243,6 +278,10 @@ class GraphedGreedyDecoder:
         if getattr(self, "_fp", None) != fp:   # other weights / layers / backend than the kept step and graphs were built from
             self.reset()
             self._fp = fp
+        if self.speculating:
+            out = self._generate_speculative(ids, max_new_tokens, use_graph, eos_token_id, check_every)
+            if out is not None:   # (None: the verify step refused this cache — `speculating` is off from here on, the plain route below serves)
+                return out
         kept = getattr(self, "cache", None) is not None and getattr(self, "_state", None) is not None
         if kept:
             self.cache.reset()
@@ -291,6 +330,7 @@ class GraphedGreedyDecoder:
         update: account_tokens keeps that counter, outside the captured step)"""
         lens = [] if st["step"] is not None or self.cache is None else \
             [lay.cumulative_length for lay in self.cache.layers if isinstance(getattr(lay, "cumulative_length", None), Tensor)]
+        lens = lens + list(st.get("carried", ()))   # (the speculative route: the history, the device scalars — p, done, the counters — and the rows' argmax)
         return st["tok"].clone(), st["pos"].clone(), [(t, t.clone()) for t in lens]
 
     @staticmethod
@@ -298,6 +338,91 @@ class GraphedGreedyDecoder:
         st["tok"].copy_(snap[0]); st["pos"].copy_(snap[1])
         for t, was in snap[2]:
             t.copy_(was)
+
+    def _spec_state(self):
+        """the kept state holder of the speculative route — a batch-1 cache of its own, the verify step on it, the token history, ONE int64 tensor with the
+        device scalars (p, last, eos, done, steps, tokens: read back in one copy) and the rows' tok / pos / argmax — or None where the verify step refuses"""
+        if self._spec is not None:
+            return self._spec
+        R, dev = self.draft_rows, self.device
+        cfg = self.model.config
+        n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
+        hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+        cache = self._new_cache()
+        cache.early_initialization(1, n_kv, hd, self.model.model.norm.weight.dtype, dev)
+        try:
+            step = self._fused_mod.FusedLlamaStep(self.model, cache, self.max_cache_len, attention=self.attention, batch=R, verify=True)   # (no `glue`: as the batched step)
+        except ValueError:
+            return None
+        scal = torch.zeros(6, dtype=torch.int64, device=dev)
+        st = {"verify": True, "cache": cache, "step": step, "hist": torch.zeros(self.max_cache_len, dtype=torch.int64, device=dev), "scalars": scal,
+              "p": scal[0:1], "last": scal[1:2], "eos": scal[2:3], "done": scal[3:4], "steps": scal[4:5], "tokens": scal[5:6],
+              "tok": torch.zeros(R, 1, dtype=torch.int64, device=dev), "next_tok": torch.zeros(R, 1, dtype=torch.int64, device=dev),
+              "pos": torch.zeros(R, dtype=torch.int64, device=dev), "graphs": {}, "key": lambda kv: kv,
+              "kv_len": lambda p: kv_bucket(p, self.attention, self.max_cache_len) if self.bucket_cache else self.max_cache_len,
+              "argmax_advance": True, "graph": None, "fresh": True}
+        st["carried"] = (st["hist"], scal, st["next_tok"])
+        self._spec = st
+        return st
+
+    @torch.no_grad()
+    def _generate_speculative(self, ids: Tensor, max_new_tokens: int, use_graph: bool, eos_token_id, check_every: int):
+        """generate() by prompt-lookup speculation (the class docstring): the prefill as on the plain route, then captured steps that each commit 1 .. draft_rows
+        tokens on the device.  The host only replays: every `check_every` steps (fewer when fewer can still be needed: a live step commits at least one token) it
+        reads the scalars in one copy and stops at done or p >= last.  The cache bucket of a step comes from the host's upper bound of p: the last value read,
+        plus draft_rows per step since, plus draft_rows - 1 for the step's last row."""
+        st = self._spec_state()
+        if st is None:
+            self.speculating = False
+            return None
+        R, T = self.draft_rows, ids.shape[1]
+        cache = st["cache"]
+        cache.reset()
+        out = self.model(ids, past_key_values=cache, cache_position=torch.arange(T, device=self.device), use_cache=True)   # prefill
+        first = self._pick(out.logits[:, -1])
+        last = T + max_new_tokens - 1   # the index of the last token to emit; the first one is hist[T]
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        st["hist"][:T].copy_(ids[0])
+        st["hist"][T:T + 1].copy_(first.view(-1))
+        ended = eos >= 0 and int(first) == eos   # (one host read per call, before the loop)
+        st["scalars"].copy_(torch.tensor([T, last, eos, int(ended), 0, 0], dtype=torch.int64), non_blocking=False)
+        p, done, since = T, ended, 0   # the host's copy of p as last read, and the steps replayed since
+        while not done and p < last:
+            for _ in range(max(1, min(int(check_every), last - p))):
+                hi = min(p + since * R, last) + R - 1   # the largest position a row of this step can have
+                self._advance(st, hi, use_graph and not st["fresh"])   # (a fresh state's first step runs eagerly, as generate()'s does)
+                st["fresh"] = False
+                since += 1
+            vals = st["scalars"].tolist()   # one host read per check_every steps
+            p, done, since = vals[0], bool(vals[3]), 0
+        vals = st["scalars"].tolist()
+        self.spec_stats = {"steps": vals[4], "tokens": vals[5]}
+        st["step"].account_tokens(p - T)
+        return torch.cat([ids, st["hist"][T:p + 1].view(1, -1)], dim=1)
+
+    @torch.no_grad()
+    def benchmark_speculative(self, input_ids: Tensor, steps: int = 64, warmup: int = 8) -> dict:
+        """the captured speculative step's time at a context of T = input_ids.shape[1] positions: prefill, capture, then time `steps` replays of the step in the
+        FROZEN state (last = p = T: propose, the verify step, the argmax and accept all run — rows at positions T .. T + draft_rows - 1 — and accept commits
+        nothing, so every replay does the same work at the same context).  ms per step; what a step is worth in tokens is a property of the text, not measured here"""
+        assert input_ids.shape[0] == 1 and self.speculating
+        T = input_ids.shape[1]
+        assert T + self.draft_rows + 2 <= self.max_cache_len
+        self.generate(input_ids, 3, use_graph=True)
+        st = self._spec
+        assert st is not None and self.speculating
+        st["scalars"].copy_(torch.tensor([T, T, -1, 0, 0, 0], dtype=torch.int64))
+        hi = T + self.draft_rows - 1
+        for _ in range(max(2, warmup)):
+            self._advance(st, hi, True)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            self._advance(st, hi, True)
+        e1.record()
+        torch.cuda.synchronize()
+        return {"ms_per_step": e0.elapsed_time(e1) / steps, "rows": self.draft_rows, "steps": steps, "prompt_tokens": T}
 
     @torch.no_grad()
     def _advance(self, st, p: int, use_graph: bool) -> None:
@@ -360,7 +485,11 @@ class GraphedGreedyDecoder:
         assert input_ids.shape[0] == 1
         T = input_ids.shape[1]
         assert T + warmup + new_tokens + 4 <= self.max_cache_len
-        self.generate(input_ids, 3, use_graph=True)          # prefill + eager step + captured step (leaves self.graphs, self.tok, self.pos)
+        spec, self.speculating = self.speculating, False     # (the one-token step is what is timed here, whatever `speculate` says: benchmark_speculative times the other)
+        try:
+            self.generate(input_ids, 3, use_graph=True)      # prefill + eager step + captured step (leaves self.graphs, self.tok, self.pos)
+        finally:
+            self.speculating = spec
         assert self.graph is not None
         ms = self._timed_steps(self._state, T + 2, new_tokens, warmup)   # (T + 2: the host's copy of self.pos)
         return {"ms_per_token": ms, "tok_s": 1e3 / ms, "new_tokens": new_tokens, "prompt_tokens": T}
@@ -481,17 +610,21 @@ class HFGenerator:
     linears went through prepare_for_inference(backend="hip"), the model's own forward otherwise.
     Differences a caller can see: EOS is looked for every 16 tokens on the host instead of after every token (no per-token synchronisation; the text returned is cut at
     the EOS all the same); "output_tokens" holds every generated token before the EOS (the reference's slice drops the last one it generated, generation_hf.py:493);
-    a prompt that leaves less than max_new_tokens of cache generates what fits."""
+    a prompt that leaves less than max_new_tokens of cache generates what fits.
+    speculate / draft_rows / ngram_max and attention are GraphedGreedyDecoder's keywords (defaults: no speculation, HF's attention function); speculation is served
+    with attention="hip" only, and everything else decodes as before (`decoder.speculating` says which)."""
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
                  compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
-                 qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None):
+                 qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
+                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, attention: str = "sdpa"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
         from .kv_cache import check_kv_group_size, kv_cache_bits
         kv_cache_bits(kv_cache)
         check_kv_group_size(kv_cache, kv_group_size)
+        check_speculation(speculate, draft_rows, ngram_max, do_sample)
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -504,7 +637,8 @@ class HFGenerator:
         self.use_graph = compile is not None
         self.compile_options = compile_options
         self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
-                                            qkv_bias=qkv_bias, lora=lora, moe=moe, kv_cache=kv_cache, kv_group_size=kv_group_size)
+                                            qkv_bias=qkv_bias, lora=lora, moe=moe, kv_cache=kv_cache, kv_group_size=kv_group_size, speculate=speculate,
+                                            draft_rows=draft_rows, ngram_max=ngram_max, attention=attention)
         self.init()
 
     @staticmethod

@@ -45,6 +45,10 @@ Only what the step needs is taken from the model: module weights and the HF Stat
 Independently of the variant, FusedLlamaStep(kv_cache="q8" / "q4") (opt-in) runs on a kv_cache.QuantizedStaticCache: ops.rope_kvq_cache_batched and
 ops.attn_decode_kvq_batched on the layers' six packed buffers take the place of the rotary-and-cache launch and the attention, with attention="hip" and for the
 variants whose rotary launch is plain rope_cache; every other combination is refused, and the decoders then run the model's own forward on that cache.
+
+FusedLlamaStep(batch=R, verify=True) (opt-in; speculative decoding, GraphedGreedyDecoder(speculate="ngram")) is the batched step whose R rows are R consecutive
+positions of ONE sequence on a batch-1 cache: ops.rope_cache_shared and ops.attn_decode_shared take the place of the rotary-and-cache launch and the attention.
+Plain llama with attention="hip" on the dense cache only (supports_speculation); every other combination is refused.
 """
 from __future__ import annotations
 
@@ -483,6 +487,15 @@ def supports_moe_batch(model, B: int) -> bool:
     return any(variant_supported(model, StepVariant(f), B) for f in _ROUTERS)
 
 
+def supports_speculation(model, rows: int) -> bool:
+    """the coverage rule of the verify step (FusedLlamaStep(batch=rows, verify=True)): 2 .. ops.SPEC_MAX_ROWS rows, a Llama / Mistral model on axis 1 without
+    adapters that the batched step serves at that many rows (variant_supported(model, StepVariant(), rows)), and a head_dim the decode-attention kernel covers"""
+    if isinstance(rows, bool) or not isinstance(rows, int) or not 2 <= rows <= ops.SPEC_MAX_ROWS or not variant_supported(model, StepVariant(), rows):
+        return False
+    cfg = model.config
+    return (getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads) in (64, 128, 256)
+
+
 def _gopts(Ls) -> int:
     lay = ops.OPT_W3S if Ls[0].w3s else 0
     return ops.layer_opts((ops.OPT_META_SCALABLE if all(L.opts & ops.OPT_META_SCALABLE for L in Ls) else 0) | lay)
@@ -494,7 +507,7 @@ class FusedLlamaStep:
     every glue kernel gives the bits of the batch-1 kernel for sequence b alone, and the linears run at M = batch."""
 
     def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
-                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False, kv_cache: str | None = None):
+                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False, kv_cache: str | None = None, verify: bool = False):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -516,7 +529,15 @@ class FusedLlamaStep:
         step launches q|k|v (RMSNorm folded where `glue` allows), ops.rope_kvq_cache_batched (rotary, then the new key and value quantised into the six buffers),
         ops.attn_decode_kvq_batched on the packed rows, o and the rest as above: no dense key / value tensor exists.  Only with attention="hip" (no SDPA runs on packed
         bytes), up to 16 rows, and for the variants whose rotary launch is plain rope_cache (the Llama family's, Mixtral); neither the rotary-paired q / k layout nor
-        ops.rope_attn_decode_batched is used with it.  Everything else is a ValueError, which the decoders turn into the model's own forward on that cache."""
+        ops.rope_attn_decode_batched is used with it.  Everything else is a ValueError, which the decoders turn into the model's own forward on that cache.
+        verify (opt-in; speculative decoding): the `batch` rows are `batch` CONSECUTIVE POSITIONS OF ONE SEQUENCE — the last committed token and batch - 1 guessed
+        ones — on a batch-1 StaticCache (keys / values [1, n_kv, max_cache_len, hd]).  Per block the separate-glue sequence of the batched step runs with
+        ops.rope_cache_shared + ops.attn_decode_shared in the place of the rotary-and-cache launch and the attention: every row's key and value are written first (a
+        launch of its own: row i reads the keys rows < i write in the same step), then row i attends over keys [0, pos[i]].  Row i's logits are those of the
+        sequence's token at pos[i] given the rows before it, so a caller that feeds the true continuation gets every next token in one pass over the weights.  Rows
+        of rejected guesses leave finite stale keys and values beyond the committed length: nothing reads them, and the next step rewrites them before a row that
+        could see them.  Served: the plain Llama / Mistral variant (no axis0 / qk_norm / qkv_bias / lora / moe keyword), attention="hip", the dense cache, 2 .. 16
+        rows of a model supports_speculation accepts; everything else is a ValueError."""
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
         self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
@@ -541,6 +562,10 @@ class FusedLlamaStep:
                                    or max_cache_len > 30000):
             raise ValueError("hqq_amd: the decode-attention kernel covers plain softmax attention with head_dim 64 / 128 / 256 and caches of <= 30000 positions")
         self.attention = attention
+        self.verify = bool(verify)
+        if self.verify and (variant != StepVariant() or attention != "hip" or kv_cache is not None or not supports_speculation(model, B)):
+            raise ValueError(f"hqq_amd: verify=True serves the plain Llama / Mistral step with attention='hip' on a dense cache, for 2 .. {ops.SPEC_MAX_ROWS} rows of a "
+                             "model llama_fused.supports_speculation accepts")
         if glue not in ("auto", "folded", "kernels"):
             raise ValueError("glue: 'auto', 'folded' or 'kernels'")
         if glue == "folded" and (self.lora or self.axis0 or self.moe):
@@ -599,15 +624,16 @@ class FusedLlamaStep:
                 self.extra_weight_bytes = need
         self.blocks = []
         lora_ws_bytes = 0
+        cache_rows = 1 if self.verify else B   # (verify: the B rows share ONE sequence's cache)
         for li, (blk, (q, k, v, o, g, u, d)) in enumerate(zip(inner.layers, blocks)):
             lay = cache.layers[li]
             if self.kv_bits is not None:   # the six buffers in the place of keys / values (kv_cache.QuantizedStaticLayer)
                 if not getattr(lay, "is_initialized", False) or tuple(lay.bufs[0].shape[:3]) != (B, self.n_kv, max_cache_len) or lay.k_head_dim != self.hd or lay.dtype != dt:
                     raise ValueError(f"hqq_amd: the fused decode step needs an initialised QuantizedStaticCache of batch {B} and {max_cache_len} positions")
                 kv = {"kvq": lay.bufs}
-            elif not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (B, self.n_kv, max_cache_len, self.hd) or \
+            elif not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (cache_rows, self.n_kv, max_cache_len, self.hd) or \
                     not lay.keys.is_contiguous() or not lay.values.is_contiguous():
-                raise ValueError(f"hqq_amd: the fused decode step needs an initialised HF StaticCache of batch {B} and {max_cache_len} positions")
+                raise ValueError(f"hqq_amd: the fused decode step needs an initialised HF StaticCache of batch {cache_rows} and {max_cache_len} positions")
             else:
                 kv = {"kc": lay.keys, "vc": lay.values}
             self.blocks.append({
@@ -739,6 +765,9 @@ class FusedLlamaStep:
             if self.kv_bits is not None:   # rotary + quantised cache write, then the attention on the packed rows
                 ops.rope_kvq_cache_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kvq"], b["qr"])
                 att = ops.attn_decode_kvq_batched(b["qr"], b["kvq"], pos, self.att, at.scaling, self.hd, splits=splits, workspace=self.attn_ws.get(splits))
+            elif self.verify:   # the rows are positions of one sequence: all of their keys / values into its cache first, then row i over keys [0, pos[i]]
+                ops.rope_cache_shared(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
+                att = ops.attn_decode_shared(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
             elif self.attention == "hip" and variant.family == "llama":   # rotary + cache write + attention: one launch
                 att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
                                                    workspace=self.attn_ws.get(splits))

@@ -314,6 +314,45 @@ int hqq_hip_rope_attn_decode_batched(const void* q, const void* k, const void* v
                                      void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype,
                                      int64_t splits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Speculative greedy decoding by prompt lookup (opt-in: hqq_amd.utils.llama_fused.FusedLlamaStep(batch = R, verify = True),
+ * GraphedGreedyDecoder(speculate = "ngram")): R consecutive positions of ONE sequence — the last committed token and R - 1 guessed ones — go through
+ * one pass over the weights, and the model's own argmax decides how many guesses stand.  Under greedy decoding the output is the greedy output.
+ * The four symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ *
+ * hqq_hip_rope_cache_shared: hqq_hip_rope_cache_batched for `rows` rows of one sequence.  q / q_out [rows, n_heads, hd], k / v [rows, n_kv_heads, hd],
+ *   cos / sin [rows, hd], pos_dev int64[rows]; the caches are ONE sequence's [n_kv_heads, cache_len, hd] (a batch-1 StaticCache's tensors).  Row i's rotated
+ *   key and its value go to slot pos_dev[i]; q_out[i] has the bits of the batch-1 hqq_hip_rope_cache call on row i; a position outside [0, cache_len)
+ *   writes nothing.  CONTRACT: the positions of one call are distinct.  Rows with equal positions race for that slot: its contents are then unspecified
+ *   (some mixture of those rows' keys and values; never anything outside the slot).  Checks as hqq_hip_rope_cache_batched.
+ * hqq_hip_attn_decode_shared: hqq_hip_attn_decode_batched for `rows` queries of one sequence against that one cache [n_kv_heads, cache_len, hd]: row i
+ *   attends over keys [0, pos_dev[i]].  The same kernel, splits, workspace layout (hqq_hip_attn_decode_workspace_bytes(rows * n_heads, ...)) and merging
+ *   launch; only the cache's row stride is zero.  Row i is BIT-IDENTICAL to hqq_hip_attn_decode on the same cache with row i's query and position and the
+ *   same `splits`.  No rotary-fused form exists: row i reads keys that other rows write in the same step, so the write is a launch of its own
+ *   (hqq_hip_rope_cache_shared).  Every key is read once per row, not once per call.
+ * hqq_hip_spec_propose: the n-gram proposer, one workgroup.  hist_dev int64[cap]: the sequence's tokens; *p_dev: the index of the last committed one.
+ *   rows R in 2..16, ngram_max N in 0..4 (anything else: HQQ_ERR_SHAPE; 1 <= cap < 2^31).  Writes tok_dev[R], pos_dev[R]: tok[0] = hist[p], pos[i] = p + i
+ *   (not clamped: past the cache the kernels above skip their writes and hqq_hip_token_prologue_batched clamps its table rows).  Drafts: take the largest
+ *   n <= min(N, p) for which some e in [n - 1, p - 1] has hist[e - n + 1 .. e] == hist[p - n + 1 .. p]; among those the largest e; draft i (1 .. R - 1) is
+ *   ext[e + i], where ext[m] = hist[m] for m <= p and ext[m] = draft[m - p] beyond (the periodic extension of a loop of period p - e).  No match, or
+ *   N = 0: every draft is hist[p].  A *p_dev outside [0, cap) reads nothing and gives tok = 0.  Any draft is legal — only speed depends on it —, but the
+ *   rule is fixed so that a host restatement can be compared bit for bit.
+ * hqq_hip_spec_accept: one wave.  g_dev[R]: the rows' argmax (hqq_hip_argmax_advance_batched(logits, g, NULL, NULL)); tok_dev[R]: what the rows were
+ *   fed; device scalars *p_dev, *last_dev (the index of the last token to emit), *eos_dev (-1: none), *done_dev, and the counters *steps_dev / *tokens_dev.
+ *   If *done != 0 or p >= last (or p < 0 or last >= cap: nothing could be committed in bounds), NOTHING changes — replays after the end are harmless.
+ *   Otherwise a is the largest value in 0 .. R - 1 with tok[i] == g[i - 1] for all 1 <= i <= a and p + a + 1 <= last; if some g[i] == eos with i <= a,
+ *   a is cut to the first such i and *done = 1.  Then hist[p + 1 + i] = g[i] for i = 0 .. a, p += a + 1, steps += 1, tokens += a + 1.
+ * Both are plain integer work: no atomics, no workspace, fixed orders; every argument is checked before the launch (HQQ_ERR_SHAPE).
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_rope_cache_shared(const void* q, const void* k, const void* v, const void* cos, const void* sin, const int64_t* pos_dev, int64_t rows, void* q_out,
+                              void* k_cache, void* v_cache, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, int dtype, void* stream);
+int hqq_hip_attn_decode_shared(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, int64_t rows, void* out, int64_t n_heads,
+                               int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int hqq_hip_spec_propose(const int64_t* hist_dev, int64_t cap, const int64_t* p_dev, int64_t rows, int64_t ngram_max, int64_t* tok_dev, int64_t* pos_dev, void* stream);
+int hqq_hip_spec_accept(const int64_t* g_dev, const int64_t* tok_dev, int64_t rows, int64_t* hist_dev, int64_t cap, int64_t* p_dev, const int64_t* last_dev,
+                        const int64_t* eos_dev, int64_t* done_dev, int64_t* steps_dev, int64_t* tokens_dev, void* stream);
+
 /* workspace of hqq_hip_forward / hqq_hip_gemm for one layer at M rows (0 = none needed, workspace may be NULL): what the call's route parks
  * (the routes table above marks the ones that need workspace).  Same contract. */
 size_t hqq_hip_forward_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts);
