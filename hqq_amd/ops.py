@@ -1461,6 +1461,26 @@ def attn_decode_shared(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor,
     return out
 
 
+def attn_decode_tiled(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_shared's arguments and semantics through the kernel that reads each key ONCE for all R <= 16 rows (hqq_hip_attn_decode_tiled, csrc/attn_tile.hip):
+    one workgroup per (head, split), the rows as one MFMA tile, flash-decoding over blocks of 32 keys.  Its own contract: deterministic, row i independent of the
+    other rows' queries, within a derived band of float64 attention (tests/_tile_cases.py) — NOT bit-identical to attn_decode.  Splits and workspace as
+    attn_decode_shared (attn_workspace_batched(device, R, ...))."""
+    _dev(q, k_cache, v_cache, pos, out)
+    R = _batch_of(pos, "attn_decode_tiled")
+    n_kv, L, hd = _shared_cache("attn_decode_tiled", k_cache, v_cache)
+    if q.numel() % (R * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or any(t.dtype != q.dtype for t in (k_cache, v_cache, out)):
+        raise ValueError("hqq_amd: attn_decode_tiled takes dense q / out [R, n_heads * head_dim] of the caches' dtype")
+    n_heads = q.numel() // (R * hd)
+    if splits > 1 and workspace is None:
+        workspace = attn_workspace_batched(q.device, R, n_heads, hd, splits)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_attn_decode_tiled(_p(q), _p(k_cache), _p(v_cache), _p(pos), R, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
+                                                int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
+    _C.check(rc, "hqq_hip_attn_decode_tiled")
+    return out
+
+
 def _i64_dev(who: str, **tensors) -> None:
     for name, t in tensors.items():
         if not isinstance(t, Tensor) or t.dtype != torch.int64 or not t.is_contiguous():

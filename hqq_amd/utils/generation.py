@@ -54,9 +54,10 @@ def eos_lengths(rows, eos_token_id, n: int) -> list:
     return out
 
 
-def check_speculation(speculate, draft_rows, ngram_max, do_sample) -> None:
+def check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attention="rows") -> None:
     """the speculative-decoding keywords of GraphedGreedyDecoder and HFGenerator: speculate None or "ngram", draft_rows an integer in 2 .. ops.SPEC_MAX_ROWS,
-    ngram_max an integer in 0 .. ops.SPEC_MAX_NGRAM, and no sampling with speculation (acceptance is the greedy rule); ValueError naming the first that is not"""
+    ngram_max an integer in 0 .. ops.SPEC_MAX_NGRAM, no sampling with speculation (acceptance is the greedy rule), verify_attention "rows" or "tile" and "tile"
+    only with speculation (it names the verify step's attention kernel); ValueError naming the first that is not"""
     if speculate not in (None, "ngram"):
         raise ValueError("speculate: None or 'ngram'")
     for name, value, lo, hi in (("draft_rows", draft_rows, 2, ops.SPEC_MAX_ROWS), ("ngram_max", ngram_max, 0, ops.SPEC_MAX_NGRAM)):
@@ -64,6 +65,10 @@ def check_speculation(speculate, draft_rows, ngram_max, do_sample) -> None:
             raise ValueError(f"{name}: an integer in {lo} .. {hi}")
     if speculate is not None and do_sample:
         raise ValueError("speculate: greedy decoding only (do_sample=True draws tokens the n-gram drafts cannot be verified against)")
+    if isinstance(verify_attention, bool) or verify_attention not in ("rows", "tile"):
+        raise ValueError("verify_attention: 'rows' or 'tile'")
+    if verify_attention == "tile" and speculate is None:
+        raise ValueError("verify_attention: 'tile' is the speculative verify step's attention kernel (speculate='ngram')")
 
 
 def opt_ins(**keywords) -> set:
@@ -114,17 +119,21 @@ class GraphedGreedyDecoder:
     committed: history, position, EOS flag and counters, all on the device).  The host replays `check_every` steps, then reads the position and the flag in one
     copy.  The tokens are the greedy tokens of the verify step's arithmetic (the R-row kernels round differently from the one-row kernels, as generate_batch's do).
     Served where that step is (`speculating`): a Llama / Mistral model, attention="hip", the dense cache, llama_fused.supports_speculation(model, draft_rows);
-    everything else decodes as before.  `spec_stats` holds the last call's {"steps", "tokens"}; generate_batch is untouched."""
+    everything else decodes as before.  `spec_stats` holds the last call's {"steps", "tokens"}; generate_batch is untouched.
+    verify_attention: the verify step's attention kernel.  "rows" (default) — ops.attn_decode_shared, the code path as before.  "tile" (opt-in, with speculate) —
+    ops.attn_decode_tiled, which reads each key once for all rows and holds its own contract (a derived band of float64 attention, not the one-row kernel's
+    bits).  Where speculation is not served the keyword has no effect; assigning `decoder.verify_attention` rebuilds the kept state at the next generate()."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
                  qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
-                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3):
+                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, verify_attention: str = "rows"):
         from transformers import StaticCache
         from . import llama_fused
         from .kv_cache import check_kv_group_size, kv_cache_bits
         opted = opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
-        check_speculation(speculate, draft_rows, ngram_max, do_sample)
+        check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attention)
+        self._verify_attention = verify_attention
         self.kv_bits = kv_cache_bits(kv_cache)   # (None: the dense StaticCache)
         check_kv_group_size(kv_cache, kv_group_size)
         self.kv_cache, self.kv_group_size = kv_cache, kv_group_size
@@ -154,6 +163,16 @@ class GraphedGreedyDecoder:
                                 and llama_fused.supports_speculation(model, self.draft_rows))
         self._spec = None      # the state holder of the speculative route (its own cache, verify step, history, device scalars and graphs)
         self.spec_stats = {"steps": 0, "tokens": 0}
+
+    @property
+    def verify_attention(self) -> str:
+        """the attention kernel of the verify step: "rows" or "tile" ("rows" and "tile" alike have no effect where `speculating` is False)"""
+        return self._verify_attention
+
+    @verify_attention.setter
+    def verify_attention(self, value) -> None:
+        check_speculation(self.speculate, self.draft_rows, self.ngram_max, self.do_sample, value)
+        self._verify_attention = value   # (part of _fingerprint: the kept verify step and its graphs are rebuilt at the next generate())
 
     # `variant` as flags (what bench.py, the tools and the tests read): `fused` is plain Llama's, the others are the opt-in variants, one true at most
     fused = property(lambda self: self.variant is not None and not any(self.variant.flags().values()))
@@ -238,7 +257,7 @@ class GraphedGreedyDecoder:
         bound to (set_backend rebinds it class-wide).  A re-quantised / re-loaded / re-patched model gives another tuple (round-5 advisor: the kept step and
         graphs silently decoded with stale copies).  In-place edits through .data bypass the version counters: call reset() after those."""
         from ..core.quantize import HQQLinear
-        fp = [getattr(HQQLinear, "backend", None)]
+        fp = [getattr(HQQLinear, "backend", None), self._verify_attention]   # (the verify step's attention kernel is baked into the kept step and its graphs)
         for m in self.model.modules():
             W, meta = getattr(m, "W_q", None), getattr(m, "meta", None)
             if isinstance(W, Tensor):
@@ -351,7 +370,8 @@ class GraphedGreedyDecoder:
         cache = self._new_cache()
         cache.early_initialization(1, n_kv, hd, self.model.model.norm.weight.dtype, dev)
         try:
-            step = self._fused_mod.FusedLlamaStep(self.model, cache, self.max_cache_len, attention=self.attention, batch=R, verify=True)   # (no `glue`: as the batched step)
+            step = self._fused_mod.FusedLlamaStep(self.model, cache, self.max_cache_len, attention=self.attention, batch=R, verify=True,
+                                                  verify_attention=self._verify_attention)   # (no `glue`: as the batched step)
         except ValueError:
             return None
         scal = torch.zeros(6, dtype=torch.int64, device=dev)
@@ -611,20 +631,20 @@ class HFGenerator:
     Differences a caller can see: EOS is looked for every 16 tokens on the host instead of after every token (no per-token synchronisation; the text returned is cut at
     the EOS all the same); "output_tokens" holds every generated token before the EOS (the reference's slice drops the last one it generated, generation_hf.py:493);
     a prompt that leaves less than max_new_tokens of cache generates what fits.
-    speculate / draft_rows / ngram_max and attention are GraphedGreedyDecoder's keywords (defaults: no speculation, HF's attention function); speculation is served
+    speculate / draft_rows / ngram_max / verify_attention and attention are GraphedGreedyDecoder's keywords (defaults: no speculation, HF's attention function); speculation is served
     with attention="hip" only, and everything else decodes as before (`decoder.speculating` says which)."""
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
                  compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
                  qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
-                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, attention: str = "sdpa"):
+                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, attention: str = "sdpa", verify_attention: str = "rows"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
         from .kv_cache import check_kv_group_size, kv_cache_bits
         kv_cache_bits(kv_cache)
         check_kv_group_size(kv_cache, kv_group_size)
-        check_speculation(speculate, draft_rows, ngram_max, do_sample)
+        check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attention)
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -638,7 +658,7 @@ class HFGenerator:
         self.compile_options = compile_options
         self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
                                             qkv_bias=qkv_bias, lora=lora, moe=moe, kv_cache=kv_cache, kv_group_size=kv_group_size, speculate=speculate,
-                                            draft_rows=draft_rows, ngram_max=ngram_max, attention=attention)
+                                            draft_rows=draft_rows, ngram_max=ngram_max, attention=attention, verify_attention=verify_attention)
         self.init()
 
     @staticmethod

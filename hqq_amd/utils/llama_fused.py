@@ -48,6 +48,7 @@ variants whose rotary launch is plain rope_cache; every other combination is ref
 
 FusedLlamaStep(batch=R, verify=True) (opt-in; speculative decoding, GraphedGreedyDecoder(speculate="ngram")) is the batched step whose R rows are R consecutive
 positions of ONE sequence on a batch-1 cache: ops.rope_cache_shared and ops.attn_decode_shared take the place of the rotary-and-cache launch and the attention.
+verify_attention="tile" (opt-in) puts ops.attn_decode_tiled — each key read once for all rows, a contract of its own — in ops.attn_decode_shared's place.
 Plain llama with attention="hip" on the dense cache only (supports_speculation); every other combination is refused.
 """
 from __future__ import annotations
@@ -507,7 +508,8 @@ class FusedLlamaStep:
     every glue kernel gives the bits of the batch-1 kernel for sequence b alone, and the linears run at M = batch."""
 
     def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
-                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False, kv_cache: str | None = None, verify: bool = False):
+                 qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False, kv_cache: str | None = None, verify: bool = False,
+                 verify_attention: str = "rows"):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -537,7 +539,11 @@ class FusedLlamaStep:
         sequence's token at pos[i] given the rows before it, so a caller that feeds the true continuation gets every next token in one pass over the weights.  Rows
         of rejected guesses leave finite stale keys and values beyond the committed length: nothing reads them, and the next step rewrites them before a row that
         could see them.  Served: the plain Llama / Mistral variant (no axis0 / qk_norm / qkv_bias / lora / moe keyword), attention="hip", the dense cache, 2 .. 16
-        rows of a model supports_speculation accepts; everything else is a ValueError."""
+        rows of a model supports_speculation accepts; everything else is a ValueError.
+        verify_attention (with verify=True): "rows" (default) — ops.attn_decode_shared, every row bit-identical to the one-row kernel at its position, every key read
+        once PER ROW.  "tile" (opt-in) — ops.attn_decode_tiled in its place: one workgroup per (head, split) reads each key once for ALL rows; deterministic, a row
+        independent of the other rows' queries, within a derived band of float64 attention and NOT bit-identical to the one-row kernel (include/hqq_hip.h).  Any
+        other value, and "tile" without verify=True, is a ValueError."""
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
         self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
@@ -563,6 +569,12 @@ class FusedLlamaStep:
             raise ValueError("hqq_amd: the decode-attention kernel covers plain softmax attention with head_dim 64 / 128 / 256 and caches of <= 30000 positions")
         self.attention = attention
         self.verify = bool(verify)
+        if verify_attention not in ("rows", "tile"):
+            raise ValueError("verify_attention: 'rows' or 'tile'")
+        if verify_attention == "tile" and not self.verify:
+            raise ValueError("hqq_amd: verify_attention='tile' is the verify step's attention: it needs verify=True")
+        self.verify_attention = verify_attention
+        self._verify_attn = ops.attn_decode_tiled if verify_attention == "tile" else ops.attn_decode_shared
         if self.verify and (variant != StepVariant() or attention != "hip" or kv_cache is not None or not supports_speculation(model, B)):
             raise ValueError(f"hqq_amd: verify=True serves the plain Llama / Mistral step with attention='hip' on a dense cache, for 2 .. {ops.SPEC_MAX_ROWS} rows of a "
                              "model llama_fused.supports_speculation accepts")
@@ -767,7 +779,7 @@ class FusedLlamaStep:
                 att = ops.attn_decode_kvq_batched(b["qr"], b["kvq"], pos, self.att, at.scaling, self.hd, splits=splits, workspace=self.attn_ws.get(splits))
             elif self.verify:   # the rows are positions of one sequence: all of their keys / values into its cache first, then row i over keys [0, pos[i]]
                 ops.rope_cache_shared(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
-                att = ops.attn_decode_shared(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
+                att = self._verify_attn(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
             elif self.attention == "hip" and variant.family == "llama":   # rotary + cache write + attention: one launch
                 att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
                                                    workspace=self.attn_ws.get(splits))

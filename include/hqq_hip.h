@@ -353,6 +353,26 @@ int hqq_hip_spec_propose(const int64_t* hist_dev, int64_t cap, const int64_t* p_
 int hqq_hip_spec_accept(const int64_t* g_dev, const int64_t* tok_dev, int64_t rows, int64_t* hist_dev, int64_t cap, int64_t* p_dev, const int64_t* last_dev,
                         const int64_t* eos_dev, int64_t* done_dev, int64_t* steps_dev, int64_t* tokens_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * hqq_hip_attn_decode_tiled (csrc/attn_tile.hip): hqq_hip_attn_decode_shared's arguments, limits and semantics — `rows` (1 .. 16) queries of ONE sequence
+ * against its dense caches [n_kv_heads, cache_len, hd], q / out [rows, n_heads * hd], pos_dev int64[rows]; row i attends over keys [0, pos_dev[i]], positions in
+ * any order, a position outside [0, cache_len) attends as if at cache_len - 1; fp16 / bf16, hd 64 / 128 / 256, cache_len <= 30000, splits <= 64 and the
+ * workspace of hqq_hip_attn_decode_workspace_bytes(rows * n_heads, hd, splits) bytes — with ANOTHER kernel and ANOTHER contract (opt-in:
+ * FusedLlamaStep(verify = True, verify_attention = "tile")).  One workgroup per (query head, split) serves all rows: the keys [k0, k1) of [0, n_max),
+ * n_max = 1 + the largest clamped position, chunk = ceil(n_max / splits), are read from memory ONCE for all rows and go through the matrix cores as
+ * flash-decoding does it: blocks of 32 keys, fp32 scores, a running (max, sum, output) per row, the probabilities ROUNDED TO THE TENSORS' DTYPE for the
+ * product with V, fp32 accumulation, the waves' and the splits' shares merged in fixed order (the splits by the one-row kernels' merging launch).
+ * Added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * CONTRACT.  Deterministic: the same bits call to call (no atomics, fixed orders).  Row i's output depends on its own query, pos_dev[i], the cache, `rows`,
+ *   `splits` and n_max, and on NO other row's query (the columns of the score tile do not mix).  It is NOT bit-identical to hqq_hip_attn_decode: it lies within
+ *   a derived band of float64 attention (tests/_tile_cases.py derives it term by term).  Cache rows from n_max on may hold anything (NaN, Inf, rejected
+ *   guesses): no key row >= the workgroup's k1 is read, so nothing at or beyond n_max is.  Rows i >= `rows` of the 16-row tile read no query memory and write nothing.
+ *   rows outside 1 .. 16, a missing or short workspace: HQQ_ERR_SHAPE, nothing is launched.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_attn_decode_tiled(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, int64_t rows, void* out, int64_t n_heads,
+                              int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* workspace of hqq_hip_forward / hqq_hip_gemm for one layer at M rows (0 = none needed, workspace may be NULL): what the call's route parks
  * (the routes table above marks the ones that need workspace).  Same contract. */
 size_t hqq_hip_forward_workspace_bytes(int nbits, int64_t M, int64_t N, int64_t K, int64_t group_size, int dtype, uint32_t opts);

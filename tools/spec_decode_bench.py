@@ -2,13 +2,15 @@
 """What a speculative step costs: the captured verify step of GraphedGreedyDecoder(speculate="ngram") at 4, 8 and 16 rows against the plain one-row step, on the
 random Llama-2-7B-shaped model of bench.py's end-to-end leg (32 blocks, hidden 4096, intermediate 11008, vocab 32000, fp16, every decoder linear int4 gs 64,
 seed 20250), attention="hip", at a short and a long context.  The ratio of the two step times is the mean number of tokens a step must commit for speculation to
-break even; the attention launches' share of the long-context step says whether a kernel that reads each key once for all rows is worth building.  How many
+break even; the attention launches' share of the long-context step is what the second set of legs is about: the same verify step with verify_attention="tile"
+(ops.attn_decode_tiled, the kernel that reads each key once for all rows) beside verify_attention="rows" (ops.attn_decode_shared), measured in the same run.  How many
 tokens a step DOES commit depends on the text: a random model's greedy output loops, so the tokens per step recorded here are not representative, and no speed
 claim on real text follows from this file.  Needs an MI355X.
 
     python tools/spec_decode_bench.py [--out FILE.json] [--md FILE.md] [--steps 64] [--warmup 8]
 
-Every leg (the plain step, the verify step at one row count) runs in a process of its own; two passes that alternate the legs."""
+Every leg (the plain step, the verify step at one row count with one attention kernel) runs in a process of its own; two passes that alternate the legs.  The
+record is rewritten after every leg, so a run that is cut short keeps what it measured."""
 import argparse
 import json
 import os
@@ -21,7 +23,8 @@ sys.path.insert(0, ROOT)
 
 ROWS = (4, 8, 16)
 CONTEXTS = (256, 3000)
-LEGS = ("plain",) + tuple(f"rows{r}" for r in ROWS)
+KINDS = ("rows", "tile")      # FusedLlamaStep's verify_attention; a leg's name is the kind + the row count
+LEGS = ("plain",) + tuple(f"{k}{r}" for r in ROWS for k in KINDS)
 CACHE_LEN = 4096
 
 
@@ -50,7 +53,8 @@ def build(blocks: int):
 
 
 def attention_ms(step, T: int, R: int, reps: int = 20) -> float:
-    """the step's attention launches alone — per block ops.attn_decode_shared (and its merging launch) on the block's own cache tensors, rows at T .. T + R - 1 —
+    """the step's attention launches alone — per block the step's own verify attention (ops.attn_decode_shared or ops.attn_decode_tiled, and the merging launch) on
+    the block's own cache tensors, rows at T .. T + R - 1 —
     as ONE captured graph of all blocks, replayed `reps` times between two HIP events: ms per step's worth of attention"""
     import torch
     from hqq_amd import ops
@@ -61,7 +65,7 @@ def attention_ms(step, T: int, R: int, reps: int = 20) -> float:
 
     def run():
         for b in step.blocks:
-            ops.attn_decode_shared(b["qr"], b["kc"], b["vc"], pos, step.att, b["attn"].scaling, splits=splits, workspace=ws)
+            step._verify_attn(b["qr"], b["kc"], b["vc"], pos, step.att, b["attn"].scaling, splits=splits, workspace=ws)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -96,13 +100,13 @@ def leg(a):
             assert dec.step is not None
             out["points"][str(T)] = {"ms_per_step": [round(v, 4) for v in ms]}
         else:
-            R = int(a.leg[4:])
-            dec = GraphedGreedyDecoder(model, max_cache_len=CACHE_LEN, attention="hip", speculate="ngram", draft_rows=R)
+            kind, R = a.leg[:4], int(a.leg[4:])
+            dec = GraphedGreedyDecoder(model, max_cache_len=CACHE_LEN, attention="hip", speculate="ngram", draft_rows=R, verify_attention=kind)
             dec.benchmark_speculative(ids, steps=a.steps, warmup=a.warmup)
             ms = [dec.benchmark_speculative(ids, steps=a.steps, warmup=a.warmup)["ms_per_step"] for _ in range(a.reps)]
             att = [attention_ms(dec._spec["step"], T, R) for _ in range(a.reps)]
             dec.generate(ids, 128)
-            assert dec.speculating
+            assert dec.speculating and dec._spec["step"].verify_attention == kind
             out["points"][str(T)] = {"ms_per_step": [round(v, 4) for v in ms], "attention_ms": [round(v, 4) for v in att], "random_model_stats": dict(dec.spec_stats)}
         del dec
         torch.cuda.empty_cache()
@@ -139,19 +143,23 @@ def markdown(res) -> str:
         v = _all(res, "plain", T, "ms_per_step")
         rows.append(f"| {T} | plain, 1 row | {base:.3f} | {min(v):.3f} - {max(v):.3f} | 1.00 | | |")
         for R in ROWS:
-            v = _all(res, f"rows{R}", T, "ms_per_step")
-            m = statistics.median(v)
-            at = statistics.median(_all(res, f"rows{R}", T, "attention_ms"))
-            rows.append(f"| {T} | verify, {R} rows | {m:.3f} | {min(v):.3f} - {max(v):.3f} | **{m / base:.2f}** | {at:.3f} | {100 * at / m:.0f} % |")
+            for kind in KINDS:
+                v = _all(res, f"{kind}{R}", T, "ms_per_step")
+                m = statistics.median(v)
+                av = _all(res, f"{kind}{R}", T, "attention_ms")
+                at = statistics.median(av)
+                rows.append(f"| {T} | verify, {R} rows, `\"{kind}\"` | {m:.3f} | {min(v):.3f} - {max(v):.3f} | **{m / base:.2f}** | {at:.3f} ({min(av):.3f} - {max(av):.3f}) | "
+                            f"{100 * at / m:.0f} % |")
     rows += ["", "## Tokens per step on this model: NOT representative", "",
              "The weights are random and so are the prompts: the greedy output is whatever near-flat logits give — a loop the drafts then follow, or tokens that never "
              "occurred before, of which no draft is confirmed (1.00 tokens per step: every step costs the break-even factor above and commits one token).  The "
              "figures say nothing about real text.  128 new tokens after the prompt, `ngram_max=3`.", "",
-             "| context | rows | steps | tokens | tokens / step |", "|---|---|---|---|---|"]
+             "| context | rows | attention | steps | tokens | tokens / step |", "|---|---|---|---|---|---|"]
     for T in CONTEXTS:
         for R in ROWS:
-            s = res["legs"][f"rows{R}"][0][str(T)]["random_model_stats"]
-            rows.append(f"| {T} | {R} | {s['steps']} | {s['tokens']} | {s['tokens'] / max(1, s['steps']):.2f} |")
+            for kind in KINDS:
+                s = res["legs"][f"{kind}{R}"][0][str(T)]["random_model_stats"]
+                rows.append(f"| {T} | {R} | {kind} | {s['steps']} | {s['tokens']} | {s['tokens'] / max(1, s['steps']):.2f} |")
     if res.get("notes"):
         rows += ["", "## Notes", ""] + [f"- {n}" for n in res["notes"]]
     rows.append("")
@@ -180,6 +188,8 @@ def main():
             r = _child(a, name)
             res["device"] = r["device"]
             res["legs"][name].append(r["points"])
+            with open(out, "w") as fh:
+                json.dump(res, fh, indent=1)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
     if a.md:
