@@ -18,11 +18,14 @@
 //            and the cache beyond n_max may hold anything) and read transposed with ds_read_b64_tr_b16.  O stays in fp32 VGPRs, HD / 16 tiles
 //   end      the waves' (m, l, O) are merged through LDS in wave order (no atomics); S == 1: out[i] = T(O / l) for i < rows; S > 1: the share's record goes
 //            to ((i n_heads + h) S + sp) of the one-row kernels' workspace layout and attn_combine_kernel (block.hip) finishes over rows * n_heads heads
+//   host     the kernel is this file's own algorithm; its entry point goes through the host front of every decode-attention call (attn_decode_core.h: the
+//            argument checks, the (head_dim, dtype) dispatch, the combine launch) and keeps only the row limit and its LDS size
 //
 // Loads: a key row >= k1 is never read (K rows are clamped to k1 - 1 and masked, V rows are not loaded), so nothing at or beyond n_max <= L is touched.
 // Padding rows (i >= rows) read no query memory — their fragment is zero, their position -1: every key masked — and write nothing.
 // exp is expf under -ffp-contract=off, the function and flags tests/_router_cases.py's EXP_ULPS was measured with (tests/_tile_cases.py derives the band).
 #include "block_math.h"
+#include "attn_decode_core.h"
 
 namespace hqq {
 
@@ -189,47 +192,20 @@ int hqq_hip_attn_decode_tiled(const void* q, const void* k_cache, const void* v_
                               size_t workspace_bytes, void* stream) {
   const char* who = "hqq_hip_attn_decode_tiled";
   clear_stale_error();
-  if (dtype != HQQ_F16 && dtype != HQQ_BF16) { set_error("%s: fp16 / bf16 only", who); return HQQ_ERR_UNSUPPORTED; }
+  // this entry's own: the rows are one MFMA tile (first: the shared front would take up to a batch's count of them)
   if (rows < 1 || rows > TILE_ROWS) { set_error("%s: rows must be 1..%d (got %lld)", who, TILE_ROWS, (long long)rows); return HQQ_ERR_SHAPE; }
-  if (!q || !k_cache || !v_cache || !pos_dev || !out || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads || cache_len < 1 || cache_len > 30000 ||
-      rows * n_heads > INT32_MAX) {
-    set_error("%s: bad arguments (cache_len <= 30000, n_heads a multiple of n_kv_heads)", who);
-    return HQQ_ERR_SHAPE;
-  }
-  if (head_dim != 64 && head_dim != 128 && head_dim != 256) { set_error("%s: head_dim %lld not covered (64 / 128 / 256)", who, (long long)head_dim); return HQQ_ERR_UNSUPPORTED; }
-  if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) { set_error("%s: pointers must be 16-byte aligned", who); return HQQ_ERR_ALIGN; }
-  if (splits < 1 || splits > 64) { set_error("%s: splits must be 1..64 (got %lld)", who, (long long)splits); return HQQ_ERR_SHAPE; }
-  const int HD = static_cast<int>(head_dim), S = static_cast<int>(splits);
-  if (S > 1 && (!workspace || workspace_bytes < static_cast<size_t>(rows * n_heads) * S * (HD + 2) * sizeof(float))) {
-    set_error("%s: %lld splits need a workspace of hqq_hip_attn_decode_workspace_bytes(rows * n_heads, ...) bytes", who, (long long)splits);
-    return HQQ_ERR_SHAPE;
-  }
-  float* wsf = static_cast<float*>(workspace);
-  const dim3 grid(static_cast<unsigned>(n_heads), static_cast<unsigned>(S)), block(TILE_WAVES * 64);
-  const bool bf = dtype == HQQ_BF16;
-  using cu16 = const uint16_t*;
-#define HQQ_TILE_GO(HDV, BFV)                                                                                                                       \
-  do {                                                                                                                                              \
-    static LdsRaised raised;                                                                                                                        \
-    constexpr int lds = tile_lds_bytes<HDV>();                                                                                                      \
-    if (lds > 48 * 1024)                                                                                                                            \
-      if (const int rc = raise_lds_limit(raised, reinterpret_cast<const void*>(&attn_tile_kernel<HDV, BFV>), lds, who)) return rc;                    \
-    hipLaunchKernelGGL((attn_tile_kernel<HDV, BFV>), grid, block, lds, as_stream(stream), static_cast<cu16>(q), static_cast<cu16>(k_cache),         \
-                       static_cast<cu16>(v_cache), pos_dev, static_cast<int>(rows), static_cast<uint16_t*>(out), static_cast<int>(n_heads),         \
-                       static_cast<int>(n_kv_heads), static_cast<int>(cache_len), scaling, S, wsf);                                                 \
-  } while (0)
-#define HQQ_TILE_HD(BFV)                                                                                                                            \
-  do {                                                                                                                                              \
-    if (HD == 64) HQQ_TILE_GO(64, BFV);                                                                                                             \
-    else if (HD == 128) HQQ_TILE_GO(128, BFV);                                                                                                      \
-    else HQQ_TILE_GO(256, BFV);                                                                                                                     \
-  } while (0)
-  if (bf) HQQ_TILE_HD(true);
-  else HQQ_TILE_HD(false);
-#undef HQQ_TILE_HD
-#undef HQQ_TILE_GO
-  if (S > 1) launch_attn_combine(wsf, out, rows * n_heads, S, HD, bf, as_stream(stream));
-  return check_launch(who);
+  const AttnCall c{who, rows, n_heads, n_kv_heads, head_dim, cache_len, dtype, splits, workspace, workspace_bytes, out, stream};
+  if (const int rc = attn_check(c, {q, k_cache, v_cache, pos_dev, out}, {q, k_cache, v_cache, out})) return rc;
+  return attn_launch(c, [&](auto HDc, auto BFc) {
+    constexpr auto kern = &attn_tile_kernel<decltype(HDc)::value, decltype(BFc)::value>;
+    constexpr int lds = tile_lds_bytes<decltype(HDc)::value>();
+    static LdsRaised raised;   // (one per instantiation)
+    if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, lds, who)) return rc;
+    hipLaunchKernelGGL(kern, c.grid(1), dim3(TILE_WAVES * 64), lds, as_stream(stream), static_cast<const uint16_t*>(q), static_cast<const uint16_t*>(k_cache),
+                       static_cast<const uint16_t*>(v_cache), pos_dev, static_cast<int>(rows), static_cast<uint16_t*>(out), static_cast<int>(n_heads),
+                       static_cast<int>(n_kv_heads), static_cast<int>(cache_len), scaling, c.S(), c.ws());
+    return 0;
+  });
 }
 
 }  // extern "C"

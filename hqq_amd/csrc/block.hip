@@ -21,6 +21,7 @@
 // Compiled with -ffp-contract=off: a fused multiply-add would remove a rounding HF's separate ops make.
 #include "hqq_common.h"
 #include "block_math.h"
+#include "attn_decode_core.h"
 
 namespace hqq {
 
@@ -292,10 +293,10 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const uint16_t* __restric
   *reinterpret_cast<u32x4*>(out + i) = ov;
 }
 
-// ---- decode attention: one workgroup of 512 threads per query head.  Phase 1: a LANE per key (its 2 HD bytes in 16-byte loads, q broadcast
-//      from LDS, v_dot2 into fp32), scores into LDS, workgroup maximum.  Phase 2: exp(s - max) in place, workgroup sum.  Phase 3: a wave
-//      per key (keys dealt round-robin to the 8 waves), a lane per pair of dims: o += p V[j]; the 8 partial vectors are added in wave order.
-//      Deterministic: no atomics, fixed orders.  Keys beyond pos are never read.
+// ---- decode attention on the dense cache: one workgroup of 512 threads per (query head, share of the keys).  The kernel is the front of attn_decode_body
+//      (attn_decode_core.h: scores + maximum, exp + sum, P V + merge + output or record — one body, two loaders: this kernel's read dense rows, the
+//      quantised cache's, kv_cache.hip, rebuild packed ones): it finds its sequence, clamps the position, puts the query into LDS and states how a key /
+//      value row is loaded.  Keys beyond pos are never read.
 //      ROPE = true (hqq_hip_rope_attn_decode): q, k, v are the RAW projections; the workgroup applies the rotary embedding to its query and to its
 //      KV head's new key itself (rope_cache_kernel's arithmetic, rounding for rounding), uses the new key / value from LDS for position pos — the
 //      cache is only read below pos, so no workgroup depends on another's write — and the first query head of each KV head writes them to the cache.
@@ -309,7 +310,6 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(const uint16_t* __rest
                                                           const uint16_t* __restrict__ k_raw, const uint16_t* __restrict__ v_raw, const uint16_t* __restrict__ cosv,
                                                           const uint16_t* __restrict__ sinv, uint16_t* __restrict__ kc_out, uint16_t* __restrict__ vc_out,
                                                           int S, float* __restrict__ ws, int64_t cache_row) {
-  using E = El<BF>;
   {
     const int64_t row = blockIdx.z;
     q += row * n_heads * HD;
@@ -328,26 +328,18 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(const uint16_t* __rest
     if (S > 1) ws += row * n_heads * S * (HD + 2);
   }
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  float* red = reinterpret_cast<float*>(smem);                 // [16] reduction scratch
-  uint16_t* qs = reinterpret_cast<uint16_t*>(smem + 64);        // [HD] the query; ROPE: + [HD] the new key, [HD] the new value
-  float* part = reinterpret_cast<float*>(smem + 64 + HD * 6);   // [8][HD]
-  float* sc = part + 8 * HD;                                    // [n] scores, then probabilities
-  uint16_t* knew = qs + HD;
-  uint16_t* vnew = qs + 2 * HD;
+  const AttnLds<HD> lds(smem);
+  uint16_t* const qs = lds.qs;
+  uint16_t* const knew = qs + HD;
+  uint16_t* const vnew = qs + 2 * HD;
   const int h = blockIdx.x, sp = blockIdx.y, rep = n_heads / n_kv, kvh = h / rep;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   // a position outside [0, L) must not index the cache or the score buffer (sized from L): attend as if at the last slot, write nothing
   const int64_t p_raw = pos[0];
   const bool p_ok = p_raw >= 0 && p_raw < L;
   const int p0 = p_ok ? static_cast<int>(p_raw) : L - 1;
-  const int n = p0 + 1;
-  // S > 1 (long caches): workgroup (h, sp) attends over keys [k0, k1), a 1 / S share of the pos + 1 visible ones, and parks (max, sum,
-  // unnormalised output) in the workspace; attn_combine_kernel merges the S shares in split order.  One workgroup per head streams 1.3 TB/s:
-  // 48 us at 4096 keys; eight per head 19 (the 64 MB of cache at 3.4 TB/s + the two launches)
-  const int chunk = (n + S - 1) / S;
-  const int k0 = sp * chunk, k1 = (k0 + chunk < n) ? k0 + chunk : n;
-  const uint16_t* K = kc_in + static_cast<int64_t>(kvh) * L * HD;
-  const uint16_t* V = vc_in + static_cast<int64_t>(kvh) * L * HD;
+  const uint16_t* __restrict__ K = kc_in + static_cast<int64_t>(kvh) * L * HD;
+  const uint16_t* __restrict__ V = vc_in + static_cast<int64_t>(kvh) * L * HD;
   if constexpr (ROPE) {
     // thread t < HD / 2: elements t and t + HD / 2 of the query; HD / 2 <= t < HD: of the new key; HD <= t < HD + HD / 8: a 16-byte chunk of the new value
     constexpr int half = HD / 2;
@@ -374,122 +366,12 @@ __global__ __launch_bounds__(512) void attn_decode_kernel(const uint16_t* __rest
   } else {
     if (tid < HD / 8) reinterpret_cast<u32x4*>(qs)[tid] = reinterpret_cast<const u32x4*>(q + static_cast<int64_t>(h) * HD)[tid];
   }
-  __syncthreads();
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  // phase 1: like phase 3 below, a wave instruction covers KPW = 512 / HD whole key rows (LPK = HD / 8 lanes per row, 16 bytes per lane:
-  //          1 KiB of consecutive memory) — a lane per key read 64 different lines per instruction and thrashed the L1;
-  //          the LPK partial dot products of a row are added by shuffles
-  constexpr int LPK = HD / 8, KPW = 64 / LPK, STEP = 8 * KPW;
-  const int sub = lane / LPK, ch = lane - sub * LPK;
-  const u32x4 qf = reinterpret_cast<const u32x4*>(qs)[ch];
-  auto krow = [&](int j) -> u32x4 {
-    const uint16_t* kr = (ROPE && j == p0) ? knew : K + static_cast<int64_t>(j) * HD;   // the new key: from LDS, its cache row is being written by another workgroup
-    return reinterpret_cast<const u32x4*>(kr)[ch];
+  // the rows of the dense cache; ROPE: the new key / value from LDS — their cache row is being written by another workgroup
+  auto row = [&](const uint16_t* __restrict__ base, const uint16_t* fresh, int ch, int j) -> u32x4 {
+    const uint16_t* r = (ROPE && j == p0) ? fresh : base + static_cast<int64_t>(j) * HD;
+    return reinterpret_cast<const u32x4*>(r)[ch];
   };
-  auto score = [&](const u32x4& kv) -> float {
-    float acc = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint32_t qe = qf[e], ke = kv[e];   // (a bit_cast of an ext-vector ELEMENT reads element 0: copy to a scalar first)
-      if constexpr (BF) acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(b2, qe), __builtin_bit_cast(b2, ke), acc, false);
-      else acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, qe), __builtin_bit_cast(h2, ke), acc, false);
-    }
-#pragma unroll
-    for (int off = 1; off < LPK; off <<= 1) acc += __shfl_xor(acc, off, 64);
-    return acc * scaling;
-  };
-  float mx = -INFINITY;
-  {
-    int j = k0 + wave * KPW + sub;
-    for (; j + 3 * STEP < k1; j += 4 * STEP) {
-      u32x4 k4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) k4[u] = krow(j + u * STEP);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float sv = score(k4[u]);
-        if (ch == 0) sc[j + u * STEP - k0] = sv;
-        mx = fmaxf(mx, sv);
-      }
-    }
-    // (the shuffles of score() need every lane of a row group: rows past the end are computed on row k1 - 1 and dropped)
-    for (; j - sub < k1; j += STEP) {
-      const bool live = j < k1;
-      const float sv = score(krow(live ? j : k1 - 1));
-      if (live) {
-        if (ch == 0) sc[j - k0] = sv;
-        mx = fmaxf(mx, sv);
-      }
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int w = 1; w < 8; ++w) mx = fmaxf(mx, red[w]);
-  // phase 2
-  float sum = 0.f;
-  for (int j = tid; j < k1 - k0; j += 512) {
-    const float pj = __expf(sc[j] - mx);
-    sc[j] = pj;
-    sum += pj;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-  if (lane == 0) red[8 + wave] = sum;
-  __syncthreads();
-  sum = ((red[8] + red[9]) + (red[10] + red[11])) + ((red[12] + red[13]) + (red[14] + red[15]));
-  // phase 3: a wave instruction covers KPW = 512 / HD value rows: LPK = HD / 8 lanes per row, 16 bytes (8 dims) per lane; a wave takes rows
-  //          k0 + KPW wave + sub, stepping 8 KPW, four instructions in flight; the KPW row groups of a wave are added by shuffles
-  float o8[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-  auto vrow = [&](int j) -> u32x4 {
-    const uint16_t* vr = (ROPE && j == p0) ? vnew : V + static_cast<int64_t>(j) * HD;
-    return reinterpret_cast<const u32x4*>(vr)[ch];
-  };
-  auto fold = [&](const u32x4& v, float pj) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint32_t w = v[e];   // (element copied to a scalar before its halves are taken)
-      o8[2 * e] = fmaf(pj, E::f(static_cast<uint16_t>(w & 0xFFFFu)), o8[2 * e]);
-      o8[2 * e + 1] = fmaf(pj, E::f(static_cast<uint16_t>(w >> 16)), o8[2 * e + 1]);
-    }
-  };
-  int j = k0 + wave * KPW + sub;
-  for (; j + 3 * STEP < k1; j += 4 * STEP) {
-    u32x4 v4[4];
-    float p4[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { v4[u] = vrow(j + u * STEP); p4[u] = sc[j + u * STEP - k0]; }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) fold(v4[u], p4[u]);
-  }
-  for (; j < k1; j += STEP) fold(vrow(j), sc[j - k0]);
-#pragma unroll
-  for (int off = LPK; off < 64; off <<= 1)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o8[e] += __shfl_xor(o8[e], off, 64);
-  if (sub == 0) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) part[wave * HD + ch * 8 + e] = o8[e];
-  }
-  __syncthreads();
-  if (tid < HD) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) t += part[w * HD + tid];
-    if (S == 1) {
-      out[static_cast<int64_t>(h) * HD + tid] = E::r(t / sum);
-    } else {
-      float* rec = ws + (static_cast<int64_t>(h) * S + sp) * (HD + 2);   // (an empty share leaves max = -inf, sum = 0, output 0)
-      rec[2 + tid] = t;
-      if (tid == 0) { rec[0] = mx; rec[1] = sum; }
-    }
-  }
+  attn_decode_body<HD, BF>(lds, h, sp, p0 + 1, S, scaling, out, ws, [&](int ch, int j) { return row(K, knew, ch, j); }, [&](int ch, int j) { return row(V, vnew, ch, j); });
 }
 
 // ---- the S shares of a head, merged in split order: out = sum_s e^(m_s - m) o_s / sum_s e^(m_s - m) l_s ----
@@ -740,59 +622,26 @@ static int attn_decode_run(const char* who, bool rope, bool shared, const void* 
                            int64_t batch, void* k_cache, void* v_cache, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling,
                            int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
   clear_stale_error();
-  if (!block_dtype_ok(dtype, who)) return HQQ_ERR_UNSUPPORTED;
-  if (!batch_ok(batch, who)) return HQQ_ERR_SHAPE;
-  if (!q || !k_cache || !v_cache || !pos_dev || !out || (rope && (shared || !k_raw || !v_raw || !cosv || !sinv)) || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads ||
-      cache_len < 1 || cache_len > 30000 || n_heads > INT32_MAX || batch * n_heads > INT32_MAX) {
-    set_error("%s: bad arguments (cache_len <= 30000, n_heads a multiple of n_kv_heads)", who);
-    return HQQ_ERR_SHAPE;
-  }
-  if (head_dim != 64 && head_dim != 128 && head_dim != 256) { set_error("%s: head_dim %lld not covered (64 / 128 / 256)", who, (long long)head_dim); return HQQ_ERR_UNSUPPORTED; }
-  if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || (rope && (!aligned16(k_raw) || !aligned16(v_raw)))) {
-    set_error("%s: pointers must be 16-byte aligned", who);
-    return HQQ_ERR_ALIGN;
-  }
-  const int HD = static_cast<int>(head_dim);
-  if (splits < 1 || splits > 64) { set_error("%s: splits must be 1..64 (got %lld)", who, (long long)splits); return HQQ_ERR_SHAPE; }
-  const int S = static_cast<int>(splits);
-  // (a batch's records: those of batch * n_heads heads, hqq_hip_attn_decode_workspace_bytes(batch * n_heads, ...))
-  if (S > 1 && (!workspace || workspace_bytes < static_cast<size_t>(batch * n_heads) * S * (HD + 2) * sizeof(float))) {
-    set_error("%s: %lld splits need a workspace of hqq_hip_attn_decode_workspace_bytes(...) bytes", who, (long long)splits);
-    return HQQ_ERR_SHAPE;
-  }
-  float* wsf = static_cast<float*>(workspace);
+  const AttnCall c{who, batch, n_heads, n_kv_heads, head_dim, cache_len, dtype, splits, workspace, workspace_bytes, out, stream};
+  if (const int rc = attn_check(c, {q, k_cache, v_cache, pos_dev, out}, {q, k_cache, v_cache, out})) return rc;
+  // this runner's own: the raw projections and the rotary tables of the ROPE kernel, which has no shared-cache form
+  if (rope && (shared || !k_raw || !v_raw || !cosv || !sinv)) { set_error("%s: bad arguments (k, v, cos and sin are required)", who); return HQQ_ERR_SHAPE; }
+  if (rope && (!aligned16(k_raw) || !aligned16(v_raw))) { set_error("%s: k and v must be 16-byte aligned", who); return HQQ_ERR_ALIGN; }
   const int64_t cache_row = shared ? 0 : n_kv_heads * cache_len * head_dim;   // (shared: every row's queries on the one cache)
-  const int lds = 64 + HD * 6 + 8 * HD * 4 + static_cast<int>((cache_len + S - 1) / S + 8) * 4;
-  const dim3 grid(static_cast<unsigned>(n_heads), static_cast<unsigned>(S), static_cast<unsigned>(batch)), block(512);
-  static LdsRaised raised[12];
-  constexpr int LDS_MAX = 64 + 256 * 6 + 8 * 256 * 4 + 30000 * 4;
-#define HQQ_ATTN_GO(HDV, RP, BFV, IDX)                                                                                                     \
-  do {                                                                                                                                     \
-    if (lds > 48 * 1024)                                                                                                                   \
-      if (const int rc = raise_lds_limit(raised[IDX], reinterpret_cast<const void*>(&attn_decode_kernel<HDV, RP, BFV>), LDS_MAX, who)) return rc; \
-    hipLaunchKernelGGL((attn_decode_kernel<HDV, RP, BFV>), grid, block, lds, as_stream(stream), static_cast<cu16>(q), static_cast<cu16>(k_cache), \
-                       static_cast<cu16>(v_cache), pos_dev, static_cast<u16>(out), static_cast<int>(n_heads), static_cast<int>(n_kv_heads),  \
-                       static_cast<int>(cache_len), scaling, static_cast<cu16>(k_raw), static_cast<cu16>(v_raw),                            \
-                       static_cast<cu16>(cosv), static_cast<cu16>(sinv), static_cast<u16>(k_cache), static_cast<u16>(v_cache), S, wsf,     \
-                       cache_row);                                                                                                         \
-  } while (0)
-#define HQQ_ATTN_HD(RP, BFV, BASE)                                                                                                         \
-  do {                                                                                                                                     \
-    if (HD == 64) HQQ_ATTN_GO(64, RP, BFV, BASE);                                                                                          \
-    else if (HD == 128) HQQ_ATTN_GO(128, RP, BFV, BASE + 1);                                                                               \
-    else HQQ_ATTN_GO(256, RP, BFV, BASE + 2);                                                                                              \
-  } while (0)
-  const bool bf = dtype == HQQ_BF16;
-  if (rope && bf) HQQ_ATTN_HD(true, true, 0);
-  else if (rope) HQQ_ATTN_HD(true, false, 3);
-  else if (bf) HQQ_ATTN_HD(false, true, 6);
-  else HQQ_ATTN_HD(false, false, 9);
-#undef HQQ_ATTN_HD
-#undef HQQ_ATTN_GO
-  if (S > 1) {   // (record of head b n_heads + h and output row b, head h: the same offset for a dense [batch, n_heads, HD] output)
-    launch_attn_combine(wsf, out, batch * n_heads, S, HD, bf, as_stream(stream));
-  }
-  return check_launch(who);
+  const int lds = attn_lds_launch(c.HD(), cache_len, c.S());
+  return attn_launch(c, [&](auto HDc, auto BFc) {
+    auto go = [&](auto RPc) {
+      constexpr auto kern = &attn_decode_kernel<decltype(HDc)::value, decltype(RPc)::value, decltype(BFc)::value>;
+      static LdsRaised raised;   // (one per instantiation)
+      if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, ATTN_LDS_MAX, who)) return rc;
+      hipLaunchKernelGGL(kern, c.grid(batch), dim3(512), lds, as_stream(stream), static_cast<cu16>(q), static_cast<cu16>(k_cache), static_cast<cu16>(v_cache), pos_dev,
+                         static_cast<u16>(out), static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(cache_len), scaling, static_cast<cu16>(k_raw),
+                         static_cast<cu16>(v_raw), static_cast<cu16>(cosv), static_cast<cu16>(sinv), static_cast<u16>(k_cache), static_cast<u16>(v_cache), c.S(), c.ws(),
+                         cache_row);
+      return 0;
+    };
+    return rope ? go(std::true_type{}) : go(std::false_type{});
+  });
 }
 
 size_t hqq_hip_attn_decode_workspace_bytes(int64_t n_heads, int64_t head_dim, int64_t splits) {

@@ -11,12 +11,13 @@
 //   kv_quantize            dense rows [B, n_kv, T, head_dim] -> positions start .. start + T - 1 of the six buffers (prefill, and the composed route's update)
 //   kv_dequantize          positions 0 .. n - 1 of the six buffers -> dense [B, n_kv, n, head_dim] (the composed route, the tests)
 //   rope_kvq_cache         rope_cache_kernel's work (block.hip) with the rotated key and the value row quantised on chip instead of stored densely
-//   attn_decode_kvq        attn_decode_kernel<ROPE = false> (block.hip) with its two row loads replaced by a packed load + rebuild to T; everything behind the
-//                          rebuild keeps that kernel's order, so the output has the bits of attn_decode on the dequantised cache with the same splits
+//   attn_decode_kvq        the decode attention's one body (attn_decode_core.h) on loaders that read a packed row and rebuild it to T: what runs behind the
+//                          rebuild is the text attn_decode_kernel (block.hip) runs, so the output has the bits of attn_decode on the dequantised cache with the same splits
 // In every kernel a LANE holds 8 consecutive dims of a row (LPK = head_dim / 8 lanes per row, whole rows within a wave); gs is 32 or 64, so a lane's 8 dims
 // share one (scale, zero) pair.  Compiled with -ffp-contract=off: the reference's product and sum round separately.
 #include "hqq_common.h"
 #include "block_math.h"
+#include "attn_decode_core.h"
 
 namespace hqq {
 
@@ -226,14 +227,14 @@ __global__ __launch_bounds__(256) void rope_kvq_cache_kernel(const uint16_t* __r
   kv_quant_store8<HD, NBITS, BF>(x, ch, gs, store, pick(is_v, vq, kq) + d * RB, pick(is_v, vs, ks) + d * G, pick(is_v, vz, kz) + d * G);
 }
 
-// ---- attn_decode_kernel<HD, false, BF> (block.hip) on the six buffers: the same phases, loops, shuffles, reductions and records; only krow / vrow differ
-//      (kv_load8: packed bytes + meta of row j, rebuilt to T).  Rows beyond pos are never read, in levels or in meta ----
+// ---- decode attention on the six buffers: attn_decode_kernel<HD, false, BF>'s front (block.hip) with loaders that rebuild a packed row to T (kv_load8: the bytes
+//      and the meta of row j); the phases behind them are attn_decode_body (attn_decode_core.h), the text the dense kernel runs.  Rows beyond pos are never read,
+//      in levels or in meta ----
 template <int HD, int NBITS, bool BF>
 __global__ __launch_bounds__(512) void attn_decode_kvq_kernel(const uint16_t* __restrict__ q, const uint8_t* __restrict__ kq, const uint16_t* __restrict__ ks,
                                                               const uint16_t* __restrict__ kz, const uint8_t* __restrict__ vq, const uint16_t* __restrict__ vs,
                                                               const uint16_t* __restrict__ vz, const int64_t* __restrict__ pos, uint16_t* __restrict__ out, int n_heads,
                                                               int n_kv, int L, int gs_shift, float scaling, int S, float* __restrict__ ws) {
-  using E = El<BF>;
   constexpr int RB = HD * NBITS / 8;
   const int G = HD >> gs_shift;
   const int h = blockIdx.x, sp = blockIdx.y, rep = n_heads / n_kv, kvh = h / rep;
@@ -248,125 +249,24 @@ __global__ __launch_bounds__(512) void attn_decode_kvq_kernel(const uint16_t* __
     if (S > 1) ws += row * n_heads * S * (HD + 2);
   }
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  float* red = reinterpret_cast<float*>(smem);                 // [16] reduction scratch
-  uint16_t* qs = reinterpret_cast<uint16_t*>(smem + 64);        // [HD] the query (the dense kernel's layout: [HD] x 3)
-  float* part = reinterpret_cast<float*>(smem + 64 + HD * 6);   // [8][HD]
-  float* sc = part + 8 * HD;                                    // [n] scores, then probabilities
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const AttnLds<HD> lds(smem);
+  const int tid = threadIdx.x;
   const int64_t p_raw = pos[0];
-  const bool p_ok = p_raw >= 0 && p_raw < L;
-  const int p0 = p_ok ? static_cast<int>(p_raw) : L - 1;
-  const int n = p0 + 1;
-  const int chunk = (n + S - 1) / S;
-  const int k0 = sp * chunk, k1 = (k0 + chunk < n) ? k0 + chunk : n;
-  if (tid < HD / 8) reinterpret_cast<u32x4*>(qs)[tid] = reinterpret_cast<const u32x4*>(q + static_cast<int64_t>(h) * HD)[tid];
-  __syncthreads();
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  constexpr int LPK = HD / 8, KPW = 64 / LPK, STEP = 8 * KPW;
-  const int sub = lane / LPK, ch = lane - sub * LPK;
-  const u32x4 qf = reinterpret_cast<const u32x4*>(qs)[ch];
-  auto krow = [&](int j) -> u32x4 {
-    return kv_load8<HD, NBITS, BF>(kq + static_cast<int64_t>(j) * RB, ks + static_cast<int64_t>(j) * G, kz + static_cast<int64_t>(j) * G, ch, gs_shift);
+  const int p0 = (p_raw >= 0 && p_raw < L) ? static_cast<int>(p_raw) : L - 1;   // the dense kernel's rule: a position outside the cache attends as if at the last slot
+  if (tid < HD / 8) reinterpret_cast<u32x4*>(lds.qs)[tid] = reinterpret_cast<const u32x4*>(q + static_cast<int64_t>(h) * HD)[tid];
+  // (how a row index, never negative, is widened for the 64-bit row offsets.  8 bits: as unsigned, which costs the loops no sign registers — with the signed
+  //  extension <64, 8, fp16> took 65 VGPRs where the phases written out in this kernel took 64, a wave per SIMD less.  4 bits: signed, the code this kernel
+  //  always had — the unsigned form measured 3 - 7 % slower there.  profiles/attn_refactor_parity.md)
+  using widen_t = std::conditional_t<NBITS == 8, uint32_t, int>;
+  auto krow = [&](int ch, int j) -> u32x4 {
+    const int64_t r = static_cast<widen_t>(j);
+    return kv_load8<HD, NBITS, BF>(kq + r * RB, ks + r * G, kz + r * G, ch, gs_shift);
   };
-  auto score = [&](const u32x4& kv) -> float {
-    float acc = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint32_t qe = qf[e], ke = kv[e];
-      if constexpr (BF) acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(b2, qe), __builtin_bit_cast(b2, ke), acc, false);
-      else acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, qe), __builtin_bit_cast(h2, ke), acc, false);
-    }
-#pragma unroll
-    for (int off = 1; off < LPK; off <<= 1) acc += __shfl_xor(acc, off, 64);
-    return acc * scaling;
+  auto vrow = [&](int ch, int j) -> u32x4 {
+    const int64_t r = static_cast<widen_t>(j);
+    return kv_load8<HD, NBITS, BF>(vq + r * RB, vs + r * G, vz + r * G, ch, gs_shift);
   };
-  float mx = -INFINITY;
-  {
-    int j = k0 + wave * KPW + sub;
-    for (; j + 3 * STEP < k1; j += 4 * STEP) {
-      u32x4 k4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) k4[u] = krow(j + u * STEP);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float sv = score(k4[u]);
-        if (ch == 0) sc[j + u * STEP - k0] = sv;
-        mx = fmaxf(mx, sv);
-      }
-    }
-    for (; j - sub < k1; j += STEP) {
-      const bool live = j < k1;
-      const float sv = score(krow(live ? j : k1 - 1));
-      if (live) {
-        if (ch == 0) sc[j - k0] = sv;
-        mx = fmaxf(mx, sv);
-      }
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int w = 1; w < 8; ++w) mx = fmaxf(mx, red[w]);
-  float sum = 0.f;
-  for (int j = tid; j < k1 - k0; j += 512) {
-    const float pj = __expf(sc[j] - mx);
-    sc[j] = pj;
-    sum += pj;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-  if (lane == 0) red[8 + wave] = sum;
-  __syncthreads();
-  sum = ((red[8] + red[9]) + (red[10] + red[11])) + ((red[12] + red[13]) + (red[14] + red[15]));
-  float o8[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o8[e] = 0.f;
-  auto vrow = [&](int j) -> u32x4 {
-    return kv_load8<HD, NBITS, BF>(vq + static_cast<int64_t>(j) * RB, vs + static_cast<int64_t>(j) * G, vz + static_cast<int64_t>(j) * G, ch, gs_shift);
-  };
-  auto fold = [&](const u32x4& v, float pj) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint32_t w = v[e];
-      o8[2 * e] = fmaf(pj, E::f(static_cast<uint16_t>(w & 0xFFFFu)), o8[2 * e]);
-      o8[2 * e + 1] = fmaf(pj, E::f(static_cast<uint16_t>(w >> 16)), o8[2 * e + 1]);
-    }
-  };
-  int j = k0 + wave * KPW + sub;
-  for (; j + 3 * STEP < k1; j += 4 * STEP) {
-    u32x4 v4[4];
-    float p4[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { v4[u] = vrow(j + u * STEP); p4[u] = sc[j + u * STEP - k0]; }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) fold(v4[u], p4[u]);
-  }
-  for (; j < k1; j += STEP) fold(vrow(j), sc[j - k0]);
-#pragma unroll
-  for (int off = LPK; off < 64; off <<= 1)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o8[e] += __shfl_xor(o8[e], off, 64);
-  if (sub == 0) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) part[wave * HD + ch * 8 + e] = o8[e];
-  }
-  __syncthreads();
-  if (tid < HD) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) t += part[w * HD + tid];
-    if (S == 1) {
-      out[static_cast<int64_t>(h) * HD + tid] = E::r(t / sum);
-    } else {
-      float* rec = ws + (static_cast<int64_t>(h) * S + sp) * (HD + 2);
-      rec[2 + tid] = t;
-      if (tid == 0) { rec[0] = mx; rec[1] = sum; }
-    }
-  }
+  attn_decode_body<HD, BF>(lds, h, sp, p0 + 1, S, scaling, out, ws, krow, vrow);
 }
 
 }  // namespace hqq
@@ -400,54 +300,30 @@ static inline bool kv_batch_ok(int64_t batch, const char* who) {
 // f(HD, NBITS, BF) as integral constants
 template <class F>
 static void kv_dispatch(int64_t hd, int nbits, bool bf, F&& f) {
-  auto on_bf = [&](auto HDc, auto NBc) { if (bf) f(HDc, NBc, std::true_type{}); else f(HDc, NBc, std::false_type{}); };
-  auto on_nb = [&](auto HDc) { if (nbits == 8) on_bf(HDc, std::integral_constant<int, 8>{}); else on_bf(HDc, std::integral_constant<int, 4>{}); };
-  if (hd == 64) on_nb(std::integral_constant<int, 64>{});
-  else if (hd == 128) on_nb(std::integral_constant<int, 128>{});
-  else on_nb(std::integral_constant<int, 256>{});
+  attn_dispatch(hd, bf, [&](auto HDc, auto BFc) { if (nbits == 8) f(HDc, std::integral_constant<int, 8>{}, BFc); else f(HDc, std::integral_constant<int, 4>{}, BFc); });
 }
 
 static int attn_kvq_run(const char* who, int nbits, const void* q, const void* kq, const void* k_scale, const void* k_zero, const void* vq, const void* v_scale,
                         const void* v_zero, const int64_t* pos_dev, int64_t batch, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t group_size,
                         int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
   clear_stale_error();
-  if (const int rc = kv_check(who, nbits, head_dim, group_size, cache_len, dtype)) return rc;
-  if (!kv_batch_ok(batch, who)) return HQQ_ERR_SHAPE;
-  if (!q || !kq || !k_scale || !k_zero || !vq || !v_scale || !v_zero || !pos_dev || !out || n_heads < 1 || n_kv_heads < 1 || n_heads % n_kv_heads ||
-      n_heads > INT32_MAX || batch * n_heads > INT32_MAX) {
-    set_error("%s: bad arguments (n_heads a multiple of n_kv_heads)", who);
-    return HQQ_ERR_SHAPE;
-  }
-  if (!aligned16(q) || !aligned16(kq) || !aligned16(vq) || !aligned16(out)) { set_error("%s: q, out and the level buffers must be 16-byte aligned", who); return HQQ_ERR_ALIGN; }
-  const int HD = static_cast<int>(head_dim);
-  if (splits < 1 || splits > 64) { set_error("%s: splits must be 1..64 (got %lld)", who, (long long)splits); return HQQ_ERR_SHAPE; }
-  const int S = static_cast<int>(splits);
-  if (S > 1 && (!workspace || workspace_bytes < static_cast<size_t>(batch * n_heads) * S * (HD + 2) * sizeof(float))) {
-    set_error("%s: %lld splits need a workspace of hqq_hip_attn_decode_workspace_bytes(...) bytes", who, (long long)splits);
-    return HQQ_ERR_SHAPE;
-  }
-  float* wsf = static_cast<float*>(workspace);
-  const int lds = 64 + HD * 6 + 8 * HD * 4 + static_cast<int>((cache_len + S - 1) / S + 8) * 4;   // (the dense kernel's layout and size)
-  const dim3 grid(static_cast<unsigned>(n_heads), static_cast<unsigned>(S), static_cast<unsigned>(batch)), block(512);
-  constexpr int LDS_MAX = 64 + 256 * 6 + 8 * 256 * 4 + 30000 * 4;
+  if (const int rc = kv_check(who, nbits, head_dim, group_size, cache_len, dtype)) return rc;   // (first: the cache's coverage rule answers with its own code)
+  const AttnCall c{who, batch, n_heads, n_kv_heads, head_dim, cache_len, dtype, splits, workspace, workspace_bytes, out, stream};
+  if (const int rc = attn_check(c, {q, kq, k_scale, k_zero, vq, v_scale, v_zero, pos_dev, out}, {q, kq, vq, out})) return rc;
+  const int lds = attn_lds_launch(c.HD(), cache_len, c.S());   // (the dense kernel's layout and size)
   const int gs_shift = group_size == 64 ? 6 : 5;
-  const bool bf = dtype == HQQ_BF16;
-  int rc = 0;
-  kv_dispatch(head_dim, nbits, bf, [&](auto HDc, auto NBc, auto BFc) {
-    constexpr int HDV = decltype(HDc)::value, NBV = decltype(NBc)::value;
-    constexpr bool BFV = decltype(BFc)::value;
-    static LdsRaised raised;   // (one per instantiation)
-    if (lds > 48 * 1024) {
-      rc = raise_lds_limit(raised, reinterpret_cast<const void*>(&attn_decode_kvq_kernel<HDV, NBV, BFV>), LDS_MAX, who);
-      if (rc) return;
-    }
-    hipLaunchKernelGGL((attn_decode_kvq_kernel<HDV, NBV, BFV>), grid, block, lds, as_stream(stream), static_cast<cu16>(q), static_cast<cu8>(kq), static_cast<cu16>(k_scale),
-                       static_cast<cu16>(k_zero), static_cast<cu8>(vq), static_cast<cu16>(v_scale), static_cast<cu16>(v_zero), pos_dev, static_cast<u16>(out),
-                       static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(cache_len), gs_shift, scaling, S, wsf);
+  return attn_launch(c, [&](auto HDc, auto BFc) {
+    auto go = [&](auto NBc) {
+      constexpr auto kern = &attn_decode_kvq_kernel<decltype(HDc)::value, decltype(NBc)::value, decltype(BFc)::value>;
+      static LdsRaised raised;   // (one per instantiation)
+      if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, ATTN_LDS_MAX, who)) return rc;
+      hipLaunchKernelGGL(kern, c.grid(batch), dim3(512), lds, as_stream(stream), static_cast<cu16>(q), static_cast<cu8>(kq), static_cast<cu16>(k_scale),
+                         static_cast<cu16>(k_zero), static_cast<cu8>(vq), static_cast<cu16>(v_scale), static_cast<cu16>(v_zero), pos_dev, static_cast<u16>(out),
+                         static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(cache_len), gs_shift, scaling, c.S(), c.ws());
+      return 0;
+    };
+    return nbits == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{});
   });
-  if (rc) return rc;
-  if (S > 1) launch_attn_combine(wsf, out, batch * n_heads, S, HD, bf, as_stream(stream));
-  return check_launch(who);
 }
 
 extern "C" {

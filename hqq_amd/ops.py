@@ -1363,6 +1363,14 @@ def attn_workspace(device, n_heads: int, head_dim: int, splits: int):
     return attn_workspace_batched(device, 1, n_heads, head_dim, splits)
 
 
+def _split_workspace(workspace, splits: int, device, rows: int, n_heads: int, head_dim: int):
+    """(pointer, bytes, tensor) of the record buffer a decode-attention launch is given: the caller's, or for splits > 1 without one a fresh
+    attn_workspace_batched(device, rows, ...) — the tensor is returned so that the allocation lives until the launch is queued"""
+    if splits > 1 and workspace is None:
+        workspace = attn_workspace_batched(device, rows, n_heads, head_dim, splits)
+    return _p(workspace), 0 if workspace is None else workspace.numel(), workspace
+
+
 def attn_decode_batched(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
     """one query per head and sequence against the static KV caches, B sequences in one launch (fp16 / bf16; within rounding of SDPA, not bit-identical):
     q / out [B, n_heads * hd] (any dense view of those values), caches [B, n_kv, cache_len, hd], pos int64 [B] on the device; sequence b attends over its own first
@@ -1371,11 +1379,10 @@ def attn_decode_batched(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor
     leaves the surplus shares empty, and the merging launch ignores them"""
     _dev(q, k_cache, v_cache, pos, out)
     B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "attn_decode_batched")
-    if splits > 1 and workspace is None:
-        workspace = attn_workspace_batched(q.device, B, n_heads, hd, splits)
+    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
     with torch.cuda.device(q.device):
         rc = _C.lib().hqq_hip_attn_decode_batched(_p(q), _p(k_cache), _p(v_cache), _p(pos), B, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
-                                                  int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
+                                                  int(splits), ws_ptr, ws_bytes, _stream())
     _C.check(rc, "hqq_hip_attn_decode_batched")
     return out
 
@@ -1395,11 +1402,10 @@ def rope_attn_decode_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: 
     if cos.numel() != B * hd or sin.numel() != B * hd or k.numel() != B * n_kv * hd or v.numel() != k.numel() or \
             not all(t.is_contiguous() for t in (k, v, cos, sin)):
         raise ValueError("hqq_amd: rope_attn_decode_batched takes dense k / v [B, n_kv_heads * head_dim] and cos / sin [B, head_dim]")
-    if splits > 1 and workspace is None:
-        workspace = attn_workspace_batched(q.device, B, n_heads, hd, splits)
+    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
     with torch.cuda.device(q.device):
         rc = _C.lib().hqq_hip_rope_attn_decode_batched(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), B, _p(k_cache), _p(v_cache), _p(out), n_heads, n_kv, hd, L,
-                                                       float(scaling), _dt(q.dtype), int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
+                                                       float(scaling), _dt(q.dtype), int(splits), ws_ptr, ws_bytes, _stream())
     _C.check(rc, "hqq_hip_rope_attn_decode_batched")
     return out
 
@@ -1442,23 +1448,27 @@ def rope_cache_shared(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor,
     return q_out
 
 
+def _attn_decode_rows(symbol: str, who: str, q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int, workspace) -> Tensor:
+    """the R rows of ONE sequence against its caches through entry point `symbol` (attn_decode_shared / attn_decode_tiled: the same arguments)"""
+    _dev(q, k_cache, v_cache, pos, out)
+    R = _batch_of(pos, who)
+    n_kv, L, hd = _shared_cache(who, k_cache, v_cache)
+    if q.numel() % (R * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or any(t.dtype != q.dtype for t in (k_cache, v_cache, out)):
+        raise ValueError(f"hqq_amd: {who} takes dense q / out [R, n_heads * head_dim] of the caches' dtype")
+    n_heads = q.numel() // (R * hd)
+    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, R, n_heads, hd)
+    with torch.cuda.device(q.device):
+        rc = getattr(_C.lib(), symbol)(_p(q), _p(k_cache), _p(v_cache), _p(pos), R, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype), int(splits), ws_ptr, ws_bytes,
+                                       _stream())
+    _C.check(rc, symbol)
+    return out
+
+
 def attn_decode_shared(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
     """attn_decode_batched for R queries of ONE sequence against that sequence's caches [n_kv, L, hd] (or [1, n_kv, L, hd]) (hqq_hip_attn_decode_shared): q / out
     [R, n_heads * hd], pos int64 [R]; row i attends over keys [0, pos[i]] and is bit-identical to attn_decode with row i's query and position and the same
     splits.  Splits and workspace as attn_decode_batched at R rows (attn_workspace_batched(device, R, ...))."""
-    _dev(q, k_cache, v_cache, pos, out)
-    R = _batch_of(pos, "attn_decode_shared")
-    n_kv, L, hd = _shared_cache("attn_decode_shared", k_cache, v_cache)
-    if q.numel() % (R * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or any(t.dtype != q.dtype for t in (k_cache, v_cache, out)):
-        raise ValueError("hqq_amd: attn_decode_shared takes dense q / out [R, n_heads * head_dim] of the caches' dtype")
-    n_heads = q.numel() // (R * hd)
-    if splits > 1 and workspace is None:
-        workspace = attn_workspace_batched(q.device, R, n_heads, hd, splits)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_decode_shared(_p(q), _p(k_cache), _p(v_cache), _p(pos), R, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
-                                                 int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
-    _C.check(rc, "hqq_hip_attn_decode_shared")
-    return out
+    return _attn_decode_rows("hqq_hip_attn_decode_shared", "attn_decode_shared", q, k_cache, v_cache, pos, out, scaling, splits, workspace)
 
 
 def attn_decode_tiled(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
@@ -1466,19 +1476,7 @@ def attn_decode_tiled(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, 
     one workgroup per (head, split), the rows as one MFMA tile, flash-decoding over blocks of 32 keys.  Its own contract: deterministic, row i independent of the
     other rows' queries, within a derived band of float64 attention (tests/_tile_cases.py) — NOT bit-identical to attn_decode.  Splits and workspace as
     attn_decode_shared (attn_workspace_batched(device, R, ...))."""
-    _dev(q, k_cache, v_cache, pos, out)
-    R = _batch_of(pos, "attn_decode_tiled")
-    n_kv, L, hd = _shared_cache("attn_decode_tiled", k_cache, v_cache)
-    if q.numel() % (R * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or any(t.dtype != q.dtype for t in (k_cache, v_cache, out)):
-        raise ValueError("hqq_amd: attn_decode_tiled takes dense q / out [R, n_heads * head_dim] of the caches' dtype")
-    n_heads = q.numel() // (R * hd)
-    if splits > 1 and workspace is None:
-        workspace = attn_workspace_batched(q.device, R, n_heads, hd, splits)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_decode_tiled(_p(q), _p(k_cache), _p(v_cache), _p(pos), R, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
-                                                int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
-    _C.check(rc, "hqq_hip_attn_decode_tiled")
-    return out
+    return _attn_decode_rows("hqq_hip_attn_decode_tiled", "attn_decode_tiled", q, k_cache, v_cache, pos, out, scaling, splits, workspace)
 
 
 def _i64_dev(who: str, **tensors) -> None:
@@ -1644,11 +1642,10 @@ def attn_decode_kvq_batched(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: 
     if Bc != B or q.numel() % (B * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or q.dtype != dt or out.dtype != dt:
         raise ValueError("hqq_amd: attn_decode_kvq_batched takes dense q / out [B, n_heads * head_dim] of the buffers' dtype, B the positions' count and the buffers' batch")
     n_heads = q.numel() // (B * hd)
-    if splits > 1 and workspace is None:
-        workspace = attn_workspace_batched(q.device, B, n_heads, hd, splits)
+    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
     with torch.cuda.device(q.device):
         rc = _C.lib().hqq_hip_attn_decode_kvq_batched(nbits, _p(q), *(_p(t) for t in bufs), _p(pos), B, _p(out), n_heads, n_kv, hd, gs, L, float(scaling), _dt(dt),
-                                                      int(splits), _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
+                                                      int(splits), ws_ptr, ws_bytes, _stream())
     _C.check(rc, "hqq_hip_attn_decode_kvq_batched")
     return out
 
