@@ -210,14 +210,21 @@ class GraphedGreedyDecoder:
         """the graph of the last generate() step that was replayed (None: none yet)"""
         return None if self._state is None else self._state["graph"]
 
-    def _kv_len(self, p: int) -> int:
-        """how much of the static cache a step at position p attends over.  HF's attention function costs what it is given (the whole masked cache:
-        304 tok/s at 1024 positions, 119 at 4096, against 500 at 256), so the fused step hands it a bucket just above the position (64, then
+    def _kv_len(self, p: int, fused: bool | None = None) -> int:
+        """how much of the static cache a step at position p (a batched or verify step: its LARGEST row position — every row attends within the bucket, each
+        masked beyond its own position) attends over; fused: whether a fused step runs it (None: generate()'s, self.step).  HF's attention function costs what it is
+        given (the whole masked cache: 304 tok/s at 1024 positions, 119 at 4096, against 500 at 256), so the fused step hands it a bucket just above the position (64, then
         multiples of 128 to 1024, then multiples of 512) and keeps one captured graph per bucket; the kernel attention reads pos + 1 keys by itself and uses the bucket only to decide
         how many workgroups share a head's keys (one up to 1024 keys)"""
-        if self.step is None or not self.bucket_cache:
+        if not (self.step is not None if fused is None else fused) or not self.bucket_cache:
             return self.max_cache_len
         return kv_bucket(p, self.attention, self.max_cache_len)
+
+    def _holder(self, step, tok: Tensor, next_tok: Tensor, pos: Tensor, graphs: dict, key, argmax_advance: bool = True, **more) -> dict:
+        """a state holder as _advance, _decode_once and _timed_steps read it: the step (None: the model's own forward), the device tensors the captured graphs
+        read and write, the dictionary the graphs are kept in with `key` of an attended length in it, the rule for that length, the last graph replayed"""
+        return {"step": step, "tok": tok, "next_tok": next_tok, "pos": pos, "graphs": graphs, "key": key, "kv_len": lambda p: self._kv_len(p, step is not None),
+                "argmax_advance": argmax_advance, "graph": None, **more}
 
     def _pick(self, logits: Tensor) -> Tensor:
         """logits [B, vocab] -> the next tokens [B, 1].  Greedy: argmax.  do_sample: temperature, then the top_k cut, then one draw from the softmax by the
@@ -322,8 +329,8 @@ class GraphedGreedyDecoder:
                     self.step = None
             self.graphs = {}
             # (glue="kernels" is the comparison leg with the separate front and back: its argmax, hand-over and increment stay torch ops)
-            st = self._state = {"step": self.step, "tok": first, "next_tok": torch.empty_like(first), "pos": torch.tensor([T], device=self.device), "graphs": self.graphs,
-                                "key": lambda kv: kv, "kv_len": self._kv_len, "argmax_advance": self.glue != "kernels", "graph": None}
+            st = self._state = self._holder(self.step, first, torch.empty_like(first), torch.tensor([T], device=self.device), self.graphs, lambda kv: kv,
+                                            argmax_advance=self.glue != "kernels")
         self.tok, self.next_tok, self.pos = st["tok"], st["next_tok"], st["pos"]
         toks = [self.tok.clone()]
         done = 0        # tokens the host has looked at
@@ -365,22 +372,17 @@ class GraphedGreedyDecoder:
             return self._spec
         R, dev = self.draft_rows, self.device
         cfg = self.model.config
-        n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
-        hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         cache = self._new_cache()
-        cache.early_initialization(1, n_kv, hd, self.model.model.norm.weight.dtype, dev)
+        cache.early_initialization(1, getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads, self._fused_mod.head_dim(cfg), self.model.model.norm.weight.dtype, dev)
         try:
             step = self._fused_mod.FusedLlamaStep(self.model, cache, self.max_cache_len, attention=self.attention, batch=R, verify=True,
                                                   verify_attention=self._verify_attention)   # (no `glue`: as the batched step)
         except ValueError:
             return None
         scal = torch.zeros(6, dtype=torch.int64, device=dev)
-        st = {"verify": True, "cache": cache, "step": step, "hist": torch.zeros(self.max_cache_len, dtype=torch.int64, device=dev), "scalars": scal,
-              "p": scal[0:1], "last": scal[1:2], "eos": scal[2:3], "done": scal[3:4], "steps": scal[4:5], "tokens": scal[5:6],
-              "tok": torch.zeros(R, 1, dtype=torch.int64, device=dev), "next_tok": torch.zeros(R, 1, dtype=torch.int64, device=dev),
-              "pos": torch.zeros(R, dtype=torch.int64, device=dev), "graphs": {}, "key": lambda kv: kv,
-              "kv_len": lambda p: kv_bucket(p, self.attention, self.max_cache_len) if self.bucket_cache else self.max_cache_len,
-              "argmax_advance": True, "graph": None, "fresh": True}
+        st = self._holder(step, torch.zeros(R, 1, dtype=torch.int64, device=dev), torch.zeros(R, 1, dtype=torch.int64, device=dev), torch.zeros(R, dtype=torch.int64, device=dev),
+                          {}, lambda kv: kv, verify=True, cache=cache, hist=torch.zeros(self.max_cache_len, dtype=torch.int64, device=dev), scalars=scal,
+                          p=scal[0:1], last=scal[1:2], eos=scal[2:3], done=scal[3:4], steps=scal[4:5], tokens=scal[5:6], fresh=True)
         st["carried"] = (st["hist"], scal, st["next_tok"])
         self._spec = st
         return st
@@ -581,21 +583,15 @@ class GraphedGreedyDecoder:
         fm = self._fused_mod
         if self.variant is None or not fm.variant_supported(self.model, self.variant, B):
             return None
-        cfg = self.model.config
-        n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
-        hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-        cache = self._new_cache()
-        cache.early_initialization(B, n_kv, hd, self.model.model.norm.weight.dtype, self.device)   # (StaticLayer.lazy_initialization with batch B)
+        cfg, dev = self.model.config, self.device
+        cache = self._new_cache()   # (below: StaticLayer.lazy_initialization with batch B)
+        cache.early_initialization(B, getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads, fm.head_dim(cfg), self.model.model.norm.weight.dtype, dev)
         try:   # (without the decoder's `glue`: the batched step has the one-launch front and back wherever they apply)
             step = fm.FusedLlamaBatchStep(self.model, cache, self.max_cache_len, B, attention=self.attention, **self.variant.flags(), **self._step_keywords())
         except ValueError:
             return None
-        st = {"B": B, "cache": cache, "scratch": self._new_cache(), "step": step,
-              "tok": torch.zeros(B, 1, dtype=torch.int64, device=self.device), "next_tok": torch.zeros(B, 1, dtype=torch.int64, device=self.device),
-              "pos": torch.zeros(B, dtype=torch.int64, device=self.device), "graphs": self.batch_graphs, "key": lambda kv: (B, kv),
-              # the bucket of the LARGEST row position (batch_kv_bucket's rule): every row attends within it, each masked beyond its own position
-              "kv_len": lambda p: kv_bucket(p, self.attention, self.max_cache_len) if self.bucket_cache else self.max_cache_len,
-              "argmax_advance": True, "graph": None}
+        st = self._holder(step, torch.zeros(B, 1, dtype=torch.int64, device=dev), torch.zeros(B, 1, dtype=torch.int64, device=dev), torch.zeros(B, dtype=torch.int64, device=dev),
+                          self.batch_graphs, lambda kv: (B, kv), B=B, cache=cache, scratch=self._new_cache())
         self._batch[B] = st
         return st
 

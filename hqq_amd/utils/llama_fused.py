@@ -54,6 +54,7 @@ Plain llama with attention="hip" on the dense cache only (supports_speculation);
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import torch
 from torch import Tensor
@@ -74,6 +75,11 @@ def _is_lora(layer) -> bool:
 def _unwrap(layer):
     """the quantised layer behind an HQQLinearLoRA wrapper (prepare_for_inference keeps the wrapper and patches its linear_layer), or the layer itself"""
     return _hip(layer.linear_layer) if _is_lora(layer) else _hip(layer)
+
+
+def head_dim(cfg) -> int:
+    """the attention head size of an HF config: its own head_dim where it names one (Qwen3's need not be hidden_size // num_attention_heads), else that quotient"""
+    return getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
 
 
 @dataclass(frozen=True)
@@ -153,7 +159,7 @@ def _arch_ok(model, family: Family) -> bool:
             return False
         dt = model.model.norm.weight.dtype
         if family.qk_norm:
-            hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+            hd = head_dim(cfg)
         for blk in model.model.layers:
             at = blk.self_attn
             if any(hasattr(at, n) for n in ("qk_norm", "sinks")) or getattr(at, "sliding_window", None):
@@ -413,10 +419,8 @@ def variant_supported(model, variant: StepVariant, batch: int | None = None) -> 
             return False
     if moe and not _moe_covers(model, dt, B):
         return False
-    if FAMILIES[variant.family].qk_norm:
-        cfg = model.config
-        if (getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads) not in (64, 128, 256):
-            return False
+    if FAMILIES[variant.family].qk_norm and head_dim(model.config) not in (64, 128, 256):
+        return False
     if batch is None and not variant.lora:
         return True
     return batch_covers(dt, B, [(L.out_features, L.in_features, L.group_size, L.nbits, L.w3s) for lin in blocks for L in lin], ops._default_opts)
@@ -493,13 +497,44 @@ def supports_speculation(model, rows: int) -> bool:
     adapters that the batched step serves at that many rows (variant_supported(model, StepVariant(), rows)), and a head_dim the decode-attention kernel covers"""
     if isinstance(rows, bool) or not isinstance(rows, int) or not 2 <= rows <= ops.SPEC_MAX_ROWS or not variant_supported(model, StepVariant(), rows):
         return False
-    cfg = model.config
-    return (getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads) in (64, 128, 256)
+    return head_dim(model.config) in (64, 128, 256)
+
+
+def _rec(L):
+    """a layer as ops.gemv_block and the re-layout functions take it"""
+    return (L.W_q, L.scale, L.zero, L.out_features)
+
+
+def _rec5(L):
+    """a layer as the grouped launches take it (the bias slot stays None: where the model has biases, the rotary-and-cache launch adds them)"""
+    return (L.W_q, L.scale, L.zero, None, L.out_features)
+
+
+def _opts(scalable: bool, w3s: bool) -> int:
+    return ops.layer_opts((ops.OPT_META_SCALABLE if scalable else 0) | (ops.OPT_W3S if w3s else 0))
 
 
 def _gopts(Ls) -> int:
-    lay = ops.OPT_W3S if Ls[0].w3s else 0
-    return ops.layer_opts((ops.OPT_META_SCALABLE if all(L.opts & ops.OPT_META_SCALABLE for L in Ls) else 0) | lay)
+    return _opts(all(L.opts & ops.OPT_META_SCALABLE for L in Ls), Ls[0].w3s)
+
+
+def _relaid_scalable(dt, t, L) -> bool:
+    """whether t = (W_q, scale, zero, N), a re-laid-out copy of layer L's rows (rotary-paired, or paired with another layer's), takes the three-op rebuild: its
+    condition depends on the slab a row sits in (J = 9 - the slab's bit offset) and the re-layout moves rows between slabs, so it is checked again on the
+    copy's tensors, never inherited from the layers"""
+    if dt != torch.float16:
+        return False
+    return ops.w3s_meta_scalable(t[1], t[2], t[3], L.in_features) if L.w3s else ops.meta_scalable(t[1], t[2], t[3], L.in_features, L.group_size, L.nbits)
+
+
+# the rotary-and-cache launch of a family, by its (qk_norm, qkv_bias): the launch's name (looked up in ops at every call) and what it takes of block b between v and cos
+_ROTARY = {
+    (False, False): ("rope_cache_batched", lambda b: ()),
+    # Qwen3 (and the attention half of Qwen3-MoE): the heads of q and k normalised, rotated and cached in one launch
+    (True, False): ("qknorm_rope_cache_batched", lambda b: (b["attn"].q_norm.weight, b["attn"].k_norm.weight, b["attn"].q_norm.variance_epsilon, b["attn"].k_norm.variance_epsilon)),
+    # Qwen2: the projections' biases added to the bias-free q|k|v, then rotated and cached, one launch
+    (False, True): ("bias_rope_cache_batched", lambda b: b["qkv_bias"]),
+}
 
 
 class FusedLlamaStep:
@@ -524,7 +559,7 @@ class FusedLlamaStep:
         rotary-and-cache launch, and with attention="hip" the kernel attends on that launch's rotated q_out (ops.attn_decode_batched).  lora: the adapter
         terms are added on the input the base launch read — o's on self.delta before the residual add, gate|up's before SiLU — and `scaling` is read once, here.
         moe (Mixtral; with qk_norm=True: Qwen3-MoE): the separate glue kernels (glue="folded" is refused), with ops.moe_router, ops.moe_gate_up and ops.moe_down
-        on the HQQExperts stacks in the place of gate|up, silu_mul and down.  Per block, counted from __call__: add_rmsnorm, q|k|v, the rotary-and-cache launch,
+        on the HQQExperts stacks in the place of gate|up, silu_mul and down.  Per block, counted from the stages _choose picks: add_rmsnorm, q|k|v, the rotary-and-cache launch,
         o, add_rmsnorm, moe_router, moe_gate_up, moe_down = 8 launches + the attention's (9 with attention="sdpa", whose function is one SDPA launch here).  The
         router writes idx / weights into per-block buffers that the two expert launches read on the device: nothing is cast or copied in between.
         kv_cache: None — `cache` is an HF StaticCache, as above.  "q8" / "q4" (opt-in) — `cache` is a kv_cache.QuantizedStaticCache of that width, and per block the
@@ -549,32 +584,39 @@ class FusedLlamaStep:
         self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
         self.axis0, self.qk_norm, self.qkv_bias, self.lora = (variant.flags()[k] for k in ("axis0", "qk_norm", "qkv_bias", "lora"))
         self.moe = FAMILIES[variant.family].moe
-        self.model = model
-        inner = model.model
-        self.inner = inner
-        cfg = model.config
-        self.device = dev = inner.embed_tokens.weight.device
-        self.dt = dt = inner.norm.weight.dtype   # fp16 or bf16 (supports())
-        self.B = B = int(batch)
+        self.model, self.inner, cfg = model, model.model, model.config
+        self.device = self.inner.embed_tokens.weight.device
+        self.dt = self.inner.norm.weight.dtype   # fp16 or bf16 (supports())
+        self.B = int(batch)
         self.n_heads = cfg.num_attention_heads
         self.n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
-        self.hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-        self.H = cfg.hidden_size
-        self.L = max_cache_len
+        self.hd = head_dim(cfg)
+        self.H, self.L = cfg.hidden_size, max_cache_len
         self.attn_fn = ALL_ATTENTION_FUNCTIONS.get_interface(cfg._attn_implementation, eager_attention_forward)
+        self.attention, self.verify, self.verify_attention = attention, bool(verify), verify_attention
+        self._rope_cache, self._rope_extra = _ROTARY[FAMILIES[variant.family].qk_norm, FAMILIES[variant.family].qkv_bias]
+        self.kv_bits = self._check(cache, glue, kv_cache)   # (None: the dense cache)
+        self._verify_attn = ops.attn_decode_tiled if verify_attention == "tile" else ops.attn_decode_shared
+        linears = [lin + [None] * (7 - len(lin)) for lin in _decoder_linears(model, self.lora, self.moe)]   # (an MoE block: q k v o, and no gate up down)
+        wrappers = _decoder_wrappers(model) if self.lora else [[None] * 7 for _ in linears]
+        self.folded, self.extra_weight_bytes = self._fold(glue, linears)
+        self.blocks = [self._block(blk, lin, wrs, cache.layers[li]) for li, (blk, lin, wrs) in enumerate(zip(self.inner.layers, linears, wrappers))]
+        self._buffers(glue)
+
+    def _check(self, cache, glue: str, kv_cache):
+        """the constructor's refusals that need no look at a layer, in the order in which they win (the cache is only asked what it is);
+        returns kv_cache's bit width, None for the dense cache"""
+        from .kv_cache import QuantizedStaticCache, kv_cache_bits
+        model, cfg, variant, attention, B = self.model, self.model.config, self.variant, self.attention, self.B
         if attention not in ("sdpa", "hip"):
             raise ValueError("attention: 'sdpa' or 'hip'")
         if attention == "hip" and (self.hd not in (64, 128, 256) or getattr(cfg, "sliding_window", None) or getattr(cfg, "attn_logit_softcapping", None)
-                                   or max_cache_len > 30000):
+                                   or self.L > 30000):
             raise ValueError("hqq_amd: the decode-attention kernel covers plain softmax attention with head_dim 64 / 128 / 256 and caches of <= 30000 positions")
-        self.attention = attention
-        self.verify = bool(verify)
-        if verify_attention not in ("rows", "tile"):
+        if self.verify_attention not in ("rows", "tile"):
             raise ValueError("verify_attention: 'rows' or 'tile'")
-        if verify_attention == "tile" and not self.verify:
+        if self.verify_attention == "tile" and not self.verify:
             raise ValueError("hqq_amd: verify_attention='tile' is the verify step's attention: it needs verify=True")
-        self.verify_attention = verify_attention
-        self._verify_attn = ops.attn_decode_tiled if verify_attention == "tile" else ops.attn_decode_shared
         if self.verify and (variant != StepVariant() or attention != "hip" or kv_cache is not None or not supports_speculation(model, B)):
             raise ValueError(f"hqq_amd: verify=True serves the plain Llama / Mistral step with attention='hip' on a dense cache, for 2 .. {ops.SPEC_MAX_ROWS} rows of a "
                              "model llama_fused.supports_speculation accepts")
@@ -589,123 +631,138 @@ class FusedLlamaStep:
             fn = "supports" + ("_lora" if self.lora else "_moe" if self.moe else "_" + on[0] if on else "")
             raise ValueError(f"hqq_amd: {', '.join(k + '=True' for k in on) or 'a batch'} needs a model of the {variant.family} family whose decoder linears "
                              f"the fused decode kernels serve at {B} rows ({fn} / {fn}_batch)")
-        # the rotary-and-cache launch of the family, by name (looked up in ops at every call), and what it takes of block b between v and cos
-        self._rope_cache, self._rope_extra = {
-            "llama": ("rope_cache_batched", lambda b: ()),
-            # Qwen3: the heads of q and k normalised, rotated and cached in one launch
-            "qwen3": ("qknorm_rope_cache_batched", lambda b: (b["attn"].q_norm.weight, b["attn"].k_norm.weight, b["attn"].q_norm.variance_epsilon, b["attn"].k_norm.variance_epsilon)),
-            # Qwen2: the projections' biases added to the bias-free q|k|v, then rotated and cached, one launch
-            "qwen2": ("bias_rope_cache_batched", lambda b: b["qkv_bias"]),
-            # the MoE families: the attention half of Mistral's / Qwen3's block
-            "mixtral": ("rope_cache_batched", lambda b: ()),
-            "qwen3_moe": ("qknorm_rope_cache_batched", lambda b: (b["attn"].q_norm.weight, b["attn"].k_norm.weight, b["attn"].q_norm.variance_epsilon, b["attn"].k_norm.variance_epsilon)),
-        }[variant.family]
-        from .kv_cache import QuantizedStaticCache, kv_cache_bits
-        self.kv_bits = kv_cache_bits(kv_cache)   # (None: the dense cache)
-        if self.kv_bits is not None:
+        kv_bits = kv_cache_bits(kv_cache)
+        if kv_bits is not None:
             if attention != "hip" or self._rope_cache != "rope_cache_batched" or not 1 <= B <= 16:
                 raise ValueError("hqq_amd: the fused step reads a quantised KV cache only with attention='hip', for 1 .. 16 rows of a variant whose rotary launch is "
                                  "rope_cache (Llama / Mistral / Mixtral); the model's own forward serves the rest on that cache")
-            if not isinstance(cache, QuantizedStaticCache) or cache.nbits != self.kv_bits:
-                raise ValueError(f"hqq_amd: kv_cache={kv_cache!r} needs a QuantizedStaticCache of {self.kv_bits} bits")
+            if not isinstance(cache, QuantizedStaticCache) or cache.nbits != kv_bits:
+                raise ValueError(f"hqq_amd: kv_cache={kv_cache!r} needs a QuantizedStaticCache of {kv_bits} bits")
         elif isinstance(cache, QuantizedStaticCache):
             raise ValueError("hqq_amd: a QuantizedStaticCache needs the kv_cache keyword ('q8' / 'q4')")
-        blocks = [lin + [None] * (7 - len(lin)) for lin in _decoder_linears(model, self.lora, self.moe)]   # (an MoE block: q k v o, and no gate up down)
-        wrappers = _decoder_wrappers(model) if self.lora else [[None] * 7 for _ in blocks]
-        can_fold = not self.lora and not self.moe and all(ops.block_covers(dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
-                       for (q, _, _, o, g, _, d) in blocks for L, norm in ((q, True), (o, False), (g, True), (d, False))) and \
-            all(g.out_features == u.out_features for (_, _, _, _, g, u, _) in blocks) and not (ops._default_opts & ops.OPT_FACTORED) and not self.axis0 and B == 1
+        return kv_bits
+
+    def _fold(self, glue: str, linears):
+        """whether the step runs the folded launches, and the bytes of the layer copies they keep: (folded, extra_weight_bytes)"""
+        can_fold = not self.lora and not self.moe and all(ops.block_covers(self.dt, L.in_features, L.group_size, L.nbits, L.w3s, norm=norm)
+                       for (q, _, _, o, g, _, d) in linears for L, norm in ((q, True), (o, False), (g, True), (d, False))) and \
+            all(g.out_features == u.out_features for (_, _, _, _, g, u, _) in linears) and not (ops._default_opts & ops.OPT_FACTORED) and not self.axis0 and self.B == 1
         if glue == "folded" and not can_fold:
             raise ValueError("hqq_amd: glue='folded' needs one sequence and fp16 / bf16 layers of 4 / 2 bits or the 3-bit stream layout, group_size 64, hidden size <= 8192")
-        self.folded = can_fold and glue != "kernels"
+        if not can_fold or glue == "kernels":
+            return False, 0
         # The folded step keeps re-laid-out COPIES of q, k (rotary-paired rows) and of gate | up (one paired layer) beside the layers' own tensors: about
         # +60 % of the decoder's linear-weight bytes (7B at 4 bits: +1.9 GB).  glue="auto" takes them only when they fit with room to spare; a model that filled
         # the GPU before keeps round 4's separate glue kernels (no copy) instead of running out of memory here (round-5 advisor).  glue="folded" insists.
-        self.extra_weight_bytes = 0
-        if self.folded:
-            def _nbytes(L):
-                return L.W_q.numel() * L.W_q.element_size() + 2 * L.scale.numel() * L.scale.element_size()
-            need = sum(_nbytes(L) for (q, k, _, _, g, u, _) in blocks for L in (q, k, g, u))
-            free_b = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else need * 4
-            if glue == "auto" and free_b < need + need // 4 + (1 << 30):
-                import warnings
-                warnings.warn(f"hqq_amd: the folded decode step needs {need / 1e9:.2f} GB for its paired layer copies, {free_b / 1e9:.2f} GB are free: "
-                              "falling back to the separate glue kernels (glue='kernels')")
-                self.folded = False
-            else:
-                self.extra_weight_bytes = need
-        self.blocks = []
-        lora_ws_bytes = 0
+        need = sum(L.W_q.numel() * L.W_q.element_size() + 2 * L.scale.numel() * L.scale.element_size() for (q, k, _, _, g, u, _) in linears for L in (q, k, g, u))
+        free_b = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else need * 4
+        if glue == "auto" and free_b < need + need // 4 + (1 << 30):
+            import warnings
+            warnings.warn(f"hqq_amd: the folded decode step needs {need / 1e9:.2f} GB for its paired layer copies, {free_b / 1e9:.2f} GB are free: "
+                          "falling back to the separate glue kernels (glue='kernels')")
+            return False, 0
+        return True, need
+
+    def _choose(self, adapted_gu: bool) -> dict:
+        """WHICH LAUNCHES A BLOCK OF THIS STEP RUNS — the one statement of the precedence among the step's modes.  A block is three stages; per stage the first rule
+        that matches wins, and each rule is one method below, holding exactly its launches.  The constructor calls this once per block (adapted_gu: the block's
+        gate | up carry an adapter), builds what the chosen stages ask for, and __call__ runs them; nothing else restates a condition.
+          q|k|v          1  folded, the SDPA attention, the llama family, an even head_dim: gemv_block with BLOCK_NORM | BLOCK_ROPE on the rotary-paired copies of
+                            q / k (which exist because of this rule: "qkv_rope"), writing the rotated q into qr and k / v into the caches                 _qkv_folded_rope
+                         2  folded otherwise: gemv_block with BLOCK_NORM into q, k, v                                                                     _qkv_folded
+                         3  else: add_rmsnorm(h, delta, n1), the grouped q|k|v launch (axis 0 or 1), the qkv adapters                                    _qkv_kernels
+          rotary, cache  1  a quantised cache: rope_kvq_cache_batched, attn_decode_kvq_batched                                                            _attend_kvq
+          and attention  2  the verify step: rope_cache_shared, then _verify_attn (attn_decode_shared or attn_decode_tiled)                               _attend_verify
+                         3  the kernel attention in the llama family (its axis-0 and lora variants too): rope_attn_decode_batched, one launch             _attend_rope_attn
+                         4  else the family's rotary-and-cache launch (_ROTARY) — unless q|k|v rule 1 has rotated and cached already —, then
+                            attn_decode_batched ("hip") or self.attn_fn on the first kv_len positions ("sdpa")                     _attend_rotary_hip / _attend_rotary_sdpa / _attend_sdpa
+          o and the MLP  1  folded: three gemv_block launches — o with BLOCK_RESID, the paired gate|up with BLOCK_NORM | BLOCK_SILU, down with BLOCK_RESID;
+                            no delta is left for the next add_rmsnorm                                                                                     _mlp_folded
+                         2  else the single-layer o launch, the o adapters, add_rmsnorm(h, delta, n2), then
+                            an MoE family: moe_router, moe_gate_up, moe_down                                                                              _mlp_moe
+                            axis 0 whose gate | up carry no adapter: ONE grouped launch with BLOCK_SILU, down, the down adapters                          _mlp_silu_in_reduce
+                            otherwise: grouped gate|up, the gu adapters (they come before SiLU), silu_mul, down, the down adapters                        _mlp_kernels
+        The grouped and single-layer launches themselves are the axis-0 or the axis-1 pair."""
+        S, hip, llama = FusedLlamaStep, self.attention == "hip", self.variant.family == "llama"
+        qkv = S._qkv_kernels if not self.folded else S._qkv_folded_rope if not hip and llama and self.hd % 2 == 0 else S._qkv_folded
+        if self.kv_bits is not None:
+            attend = S._attend_kvq
+        elif self.verify:
+            attend = S._attend_verify
+        elif hip:
+            attend = S._attend_rope_attn if llama else S._attend_rotary_hip
+        else:
+            attend = S._attend_sdpa if qkv is S._qkv_folded_rope else S._attend_rotary_sdpa
+        mlp = S._mlp_folded if self.folded else S._mlp_moe if self.moe else S._mlp_silu_in_reduce if self.axis0 and not adapted_gu else S._mlp_kernels
+        grouped, single = (S._grouped_axis0, S._single_axis0) if self.axis0 else (S._grouped_axis1, S._single_axis1)
+        # (plain functions, called with the step: a record that held bound methods would tie the step and its layer copies into a reference cycle)
+        return {"qkv_stage": qkv, "attend_stage": attend, "mlp_stage": mlp, "grouped": grouped, "single": single}
+
+    def _block(self, blk, lin, wrs, lay) -> dict:
+        """one block's record: its modules, launch records and output buffers, the cache tensors of `lay`, the adapters of `wrs`, the stages _choose picks and
+        the re-laid-out layer copies those stages ask for"""
+        q, k, v, o, g, u, d = lin
+        B, dt, dev, S = self.B, self.dt, self.device, FusedLlamaStep
         cache_rows = 1 if self.verify else B   # (verify: the B rows share ONE sequence's cache)
-        for li, (blk, (q, k, v, o, g, u, d)) in enumerate(zip(inner.layers, blocks)):
-            lay = cache.layers[li]
-            if self.kv_bits is not None:   # the six buffers in the place of keys / values (kv_cache.QuantizedStaticLayer)
-                if not getattr(lay, "is_initialized", False) or tuple(lay.bufs[0].shape[:3]) != (B, self.n_kv, max_cache_len) or lay.k_head_dim != self.hd or lay.dtype != dt:
-                    raise ValueError(f"hqq_amd: the fused decode step needs an initialised QuantizedStaticCache of batch {B} and {max_cache_len} positions")
-                kv = {"kvq": lay.bufs}
-            elif not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (cache_rows, self.n_kv, max_cache_len, self.hd) or \
-                    not lay.keys.is_contiguous() or not lay.values.is_contiguous():
-                raise ValueError(f"hqq_amd: the fused decode step needs an initialised HF StaticCache of batch {cache_rows} and {max_cache_len} positions")
-            else:
-                kv = {"kc": lay.keys, "vc": lay.values}
-            self.blocks.append({
-                "attn": blk.self_attn, "n1": blk.input_layernorm, "n2": blk.post_attention_layernorm,
-                "qkv": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (q, k, v)], "qkv_opts": _gopts((q, k, v)), "qkv_nbits": q.nbits, "qkv_gs": q.group_size,
-                "o": o, **kv, "len": lay.cumulative_length,
-                # outputs of the launches (static addresses: the step is captured in a hipGraph)
-                "q": torch.empty(B, q.out_features, dtype=dt, device=dev), "k": torch.empty(B, k.out_features, dtype=dt, device=dev),
-                "v": torch.empty(B, v.out_features, dtype=dt, device=dev), "qr": torch.empty(B, self.n_heads, 1, self.hd, dtype=dt, device=dev),
+        if self.kv_bits is not None:   # the six buffers in the place of keys / values (kv_cache.QuantizedStaticLayer)
+            if not getattr(lay, "is_initialized", False) or tuple(lay.bufs[0].shape[:3]) != (B, self.n_kv, self.L) or lay.k_head_dim != self.hd or lay.dtype != dt:
+                raise ValueError(f"hqq_amd: the fused decode step needs an initialised QuantizedStaticCache of batch {B} and {self.L} positions")
+            kv = {"kvq": lay.bufs}
+        elif not getattr(lay, "is_initialized", False) or tuple(lay.keys.shape) != (cache_rows, self.n_kv, self.L, self.hd) or \
+                not lay.keys.is_contiguous() or not lay.values.is_contiguous():
+            raise ValueError(f"hqq_amd: the fused decode step needs an initialised HF StaticCache of batch {cache_rows} and {self.L} positions")
+        else:
+            kv = {"kc": lay.keys, "vc": lay.values}
+        b = {
+            "attn": blk.self_attn, "n1": blk.input_layernorm, "n2": blk.post_attention_layernorm,
+            "qkv": [_rec5(L) for L in (q, k, v)], "qkv_opts": _gopts((q, k, v)), "qkv_nbits": q.nbits, "qkv_gs": q.group_size,
+            "o": o, **kv, "len": lay.cumulative_length,
+            # outputs of the launches (static addresses: the step is captured in a hipGraph)
+            "q": torch.empty(B, q.out_features, dtype=dt, device=dev), "k": torch.empty(B, k.out_features, dtype=dt, device=dev),
+            "v": torch.empty(B, v.out_features, dtype=dt, device=dev), "qr": torch.empty(B, self.n_heads, 1, self.hd, dtype=dt, device=dev),
+        }
+        if self.moe:   # the router's weight and the experts' stacks in place; idx / weights / a are this block's own (static addresses under graph capture)
+            from ..core.quantize import Quantizer
+            gate, ex = blk.mlp.gate, blk.mlp.experts
+            kk = int(gate.top_k)
+            b.update({
+                "router": gate.weight, "top_k": kk, "renorm": bool(getattr(gate, "norm_topk_prob", True)), "round_w": self.variant.family == "qwen3_moe",
+                "ex": [(getattr(ex, r + "_W_q"), getattr(ex, r + "_scale"), getattr(ex, r + "_zero")) for r in ("gate", "up", "down")],
+                "ex_dims": (ex.num_experts, ex.hidden_dim, ex.intermediate_dim, ex.layer_meta["gate"]["group_size"], Quantizer._packing_bits[ex.layer_meta["gate"]["packing"]]),
+                "idx": torch.zeros(B, kk, dtype=torch.int64, device=dev), "w": torch.zeros(B, kk, dtype=torch.float32, device=dev),
+                "a": torch.empty(B, kk, ex.intermediate_dim, dtype=dt, device=dev),
             })
-            if self.moe:   # the router's weight and the experts' stacks in place; idx / weights / a are this block's own (static addresses under graph capture)
-                from ..core.quantize import Quantizer
-                gate, ex = blk.mlp.gate, blk.mlp.experts
-                kk = int(gate.top_k)
-                self.blocks[-1].update({
-                    "router": gate.weight, "top_k": kk, "renorm": bool(getattr(gate, "norm_topk_prob", True)), "round_w": variant.family == "qwen3_moe",
-                    "ex": [(getattr(ex, r + "_W_q"), getattr(ex, r + "_scale"), getattr(ex, r + "_zero")) for r in ("gate", "up", "down")],
-                    "ex_dims": (ex.num_experts, ex.hidden_dim, ex.intermediate_dim, ex.layer_meta["gate"]["group_size"], Quantizer._packing_bits[ex.layer_meta["gate"]["packing"]]),
-                    "idx": torch.zeros(B, kk, dtype=torch.int64, device=dev), "w": torch.zeros(B, kk, dtype=torch.float32, device=dev),
-                    "a": torch.empty(B, kk, ex.intermediate_dim, dtype=dt, device=dev),
-                })
-            else:
-                self.blocks[-1].update({
-                    "gu_gs": g.group_size, "gu": [(L.W_q, L.scale, L.zero, None, L.out_features) for L in (g, u)], "gu_opts": _gopts((g, u)), "gu_nbits": g.nbits, "d": d,
-                    "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
-                    "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
-                })
-            if self.lora:   # per group: the adapted members as (index within the group, A, B, scaling) — the tensors themselves (static addresses under graph capture)
-                for name, lo, hi in LORA_GROUPS:
-                    ad = [(i, w.lora_A.data, w.lora_B.data, w._scaling_float()) for i, w in enumerate(wrappers[li][lo:hi]) if w is not None]
-                    self.blocks[-1]["lora_" + name] = ad
-                    if ad:
-                        lora_ws_bytes = max(lora_ws_bytes, ops.lora_decode_workspace_bytes(B, ad[0][1].shape[0], [a[1].shape[1] for a in ad]))
-            if self.qkv_bias:   # the three layers' own bias tensors (static addresses under graph capture); the launch records above stay bias-free
-                self.blocks[-1]["qkv_bias"] = (q.bias, k.bias, v.bias)
-            if self.folded and attention != "hip" and self.hd % 2 == 0 and variant.family == "llama":
-                # q and k in the rotary-paired row order (ops.rotary_pair_layout): the q|k|v launch's epilogue applies the rotary embedding and writes the cache
-                # (the kernel attention folds the rotary embedding into the attention launch instead: it keeps the natural order)
-                def _sub_ok(t, L_):
-                    if dt != torch.float16:
-                        return False
-                    return ops.w3s_meta_scalable(t[1], t[2], t[3], L_.in_features) if L_.w3s else ops.meta_scalable(t[1], t[2], t[3], L_.in_features, L_.group_size, L_.nbits)
-                qp = ops.rotary_pair_layout((q.W_q, q.scale, q.zero, q.out_features), q.in_features, q.group_size, q.nbits, self.hd, w3s=q.w3s)
-                kp = ops.rotary_pair_layout((k.W_q, k.scale, k.zero, k.out_features), k.in_features, k.group_size, k.nbits, self.hd, w3s=k.w3s)
-                sub = _sub_ok(qp, q) and _sub_ok(kp, k) and bool(v.opts & ops.OPT_META_SCALABLE)   # (the permutation moves rows between slabs: checked again)
-                self.blocks[-1]["qkv_rope"] = [qp, kp, (v.W_q, v.scale, v.zero, v.out_features)]
-                self.blocks[-1]["qkv_rope_opts"] = ops.layer_opts((ops.OPT_META_SCALABLE if sub else 0) | (ops.OPT_W3S if q.w3s else 0))
-            if self.folded:   # gate|up as ONE paired layer: a packed row holds gate row n and up row n (ops.pair_layers); the layers' own tensors stay as they are
-                pair = ops.pair_layers((g.W_q, g.scale, g.zero, g.out_features), (u.W_q, u.scale, u.zero, u.out_features), g.in_features, g.group_size, g.nbits, w3s=g.w3s)
-                # the three-op rebuild's condition depends on the slab a row sits in (J = 9 - the slab's bit offset), and the pairing moves rows between
-                # slabs: checked again on the paired tensors, never inherited from the two layers
-                if dt != torch.float16:
-                    sub = False
-                elif g.w3s:
-                    sub = ops.w3s_meta_scalable(pair[1], pair[2], pair[3], g.in_features)
-                else:
-                    sub = ops.meta_scalable(pair[1], pair[2], pair[3], g.in_features, g.group_size, g.nbits)
-                self.blocks[-1]["gu_pair"] = [pair]
-                self.blocks[-1]["gu_pair_opts"] = ops.layer_opts((ops.OPT_META_SCALABLE if sub else 0) | (ops.OPT_W3S if g.w3s else 0))
+        else:
+            b.update({
+                "gu_gs": g.group_size, "gu": [_rec5(L) for L in (g, u)], "gu_opts": _gopts((g, u)), "gu_nbits": g.nbits, "d": d,
+                "g": torch.empty(B, g.out_features, dtype=dt, device=dev), "u": torch.empty(B, u.out_features, dtype=dt, device=dev),
+                "a": torch.empty(B, g.out_features, dtype=dt, device=dev),
+            })
+        if self.lora:   # per group: the adapted members as (index within the group, A, B, scaling) — the tensors themselves (static addresses under graph capture)
+            for name, lo, hi in LORA_GROUPS:
+                b["lora_" + name] = [(i, w.lora_A.data, w.lora_B.data, w._scaling_float()) for i, w in enumerate(wrs[lo:hi]) if w is not None]
+        if self.qkv_bias:   # the three layers' own bias tensors (static addresses under graph capture); the launch records above stay bias-free
+            b["qkv_bias"] = (q.bias, k.bias, v.bias)
+        b.update(self._choose(bool(b.get("lora_gu"))))
+        if b["qkv_stage"] is S._qkv_folded_rope:
+            # q and k in the rotary-paired row order (ops.rotary_pair_layout): the q|k|v launch's epilogue applies the rotary embedding and writes the cache
+            # (the kernel attention folds the rotary embedding into the attention launch instead: it keeps the natural order)
+            qp, kp = (ops.rotary_pair_layout(_rec(L), L.in_features, L.group_size, L.nbits, self.hd, w3s=L.w3s) for L in (q, k))
+            b["qkv_rope"] = [qp, kp, _rec(v)]
+            b["qkv_rope_opts"] = _opts(_relaid_scalable(dt, qp, q) and _relaid_scalable(dt, kp, k) and bool(v.opts & ops.OPT_META_SCALABLE), q.w3s)
+        if b["mlp_stage"] is S._mlp_folded:
+            # gate|up as ONE paired layer: a packed row holds gate row n and up row n (ops.pair_layers); the layers' own tensors stay as they are
+            pair = ops.pair_layers(_rec(g), _rec(u), g.in_features, g.group_size, g.nbits, w3s=g.w3s)
+            b["gu_pair"], b["gu_pair_opts"] = [pair], _opts(_relaid_scalable(dt, pair, g), g.w3s)
+            b["o_rec"], b["o_opts"], b["d_rec"], b["d_opts"] = [_rec(o)], ops.layer_opts(o.opts), [_rec(d)], ops.layer_opts(d.opts)
+        return b
+
+    def _buffers(self, glue: str) -> None:
+        """the step's own buffers (static addresses: the step is captured in a hipGraph), the rotary tables and what the front of a call is"""
+        inner, cfg, B, dt, dev = self.inner, self.model.config, self.B, self.dt, self.device
         # ONE adapter workspace for the whole step, sized for its largest group (the groups run one after the other on one stream)
+        groups = [ad for b in self.blocks for name, _, _ in LORA_GROUPS if (ad := b.get("lora_" + name))]
+        lora_ws_bytes = max((ops.lora_decode_workspace_bytes(B, ad[0][1].shape[0], [a[1].shape[1] for a in ad]) for ad in groups), default=0)
         self.lora_ws = torch.empty(lora_ws_bytes, dtype=torch.uint8, device=dev) if self.lora else None
         self.h = torch.empty(B, self.H, dtype=dt, device=dev)       # the residual stream
         self.xn = torch.empty(B, self.H, dtype=dt, device=dev)      # its normalised copy, input of the next linears
@@ -714,13 +771,15 @@ class FusedLlamaStep:
         self.attn_ws = {}                                                          # splits -> record buffer of the split attention launches
         # the causal mask of one query per sequence over the static cache, in the additive form SDPA turns a boolean mask into on every call
         # (where(mask, 0, -inf) in the query dtype): built once per token here instead of once per decoder block inside the attention function
-        self.mask = torch.zeros(B, 1, 1, max_cache_len, dtype=dt, device=dev)
-        self.ar = torch.arange(max_cache_len, device=dev)
+        self.mask = torch.zeros(B, 1, 1, self.L, dtype=dt, device=dev)
+        # what the front of a call fills of it: nothing for the kernel attention, which masks by position itself (and shares a head's keys out over `splits` workgroups)
+        self._mask_rows = None if self.attention == "hip" else self.mask.view(B, -1)
+        self.ar = torch.arange(self.L, device=dev)
         # cos / sin of every cache position, from the model's own rotary module called once (elementwise in the position: the rows equal what a
         # per-token call returns); rope types whose frequencies depend on the sequence length ("dynamic", "longrope") keep the per-token call
         self.cos_tab = self.sin_tab = None
         if getattr(inner.rotary_emb, "rope_type", "default") in ("default", "linear", "llama3", "yarn") and \
-                max_cache_len <= getattr(cfg, "max_position_embeddings", max_cache_len):
+                self.L <= getattr(cfg, "max_position_embeddings", self.L):
             with torch.no_grad():
                 c, s_ = inner.rotary_emb(torch.empty(1, 1, self.H, dtype=dt, device=dev), self.ar.view(1, -1))
             self.cos_tab, self.sin_tab = c[0].contiguous(), s_[0].contiguous()   # [max_cache_len, hd]
@@ -740,12 +799,21 @@ class FusedLlamaStep:
         kv_len (host integer > the LARGEST position, default the whole cache): HF's attention function attends over the first kv_len cache positions only
         (each row masked beyond its own position) — its cost follows the length it is given, so a caller that knows the positions passes a bucket just
         above them; the kernel attention takes its split count from it"""
-        inner, B, h, variant = self.inner, self.B, self.h, self.variant
+        c = self._front(tok, pos, kv_len)
+        for b in self.blocks:   # (the stages _choose picked when the step was built)
+            b["qkv_stage"](self, b, c)
+            b["mlp_stage"](self, b, c, b["attend_stage"](self, b, c))
+        ops.add_rmsnorm(self.h, c.delta, self.inner.norm.weight, self.inner.norm.variance_epsilon, out=self.xn)
+        return self.model.lm_head(self.xn)
+
+    def _front(self, tok: Tensor, pos: Tensor, kv_len):
+        """the residual stream's first rows, and what the stages of this call share: cos / sin of the rows' positions, pos, the attended length kvl with the
+        mask's slice over it, the attention's split count, and delta — what the next add_rmsnorm has to add to h (None: nothing yet, or added already)"""
+        inner, B, h = self.inner, self.B, self.h
         # (the positions themselves are device memory — the step is graph-replayed —: the kernels that index the cache with them skip their
         #  writes beyond the cache's last slot, csrc/block.hip; callers that know the positions on the host check them there, generation.py)
         if self.one_launch_front:   # embedding rows, rotary table rows and the causal masks in ONE launch (csrc/block.hip: copies and compares, the same bits as the ops below)
-            ops.token_prologue_batched(tok, pos, inner.embed_tokens.weight, h, self.cos_tab, self.sin_tab, self.cos_v, self.sin_v,
-                                       None if self.attention == "hip" else self.mask.view(B, -1))
+            ops.token_prologue_batched(tok, pos, inner.embed_tokens.weight, h, self.cos_tab, self.sin_tab, self.cos_v, self.sin_v, self._mask_rows)
             cos, sin = self.cos_v, self.sin_v
         else:
             h.copy_(inner.embed_tokens(tok).view(B, self.H))
@@ -754,94 +822,115 @@ class FusedLlamaStep:
             else:
                 cos, sin = inner.rotary_emb(h.view(B, 1, self.H), pos.view(B, 1))   # [B, 1, hd] each, the model's own rotary module
                 cos, sin = cos.reshape(B, -1).contiguous(), sin.reshape(B, -1).contiguous()
-            if self.attention != "hip":
-                torch.where(self.ar.view(1, -1) <= pos.view(-1, 1), self.zero, self.ninf, out=self.mask.view(B, -1))   # the causal mask of one query per row at its `pos`
+            if self._mask_rows is not None:
+                torch.where(self.ar.view(1, -1) <= pos.view(-1, 1), self.zero, self.ninf, out=self._mask_rows)   # the causal mask of one query per row at its `pos`
         kvl = self.L if kv_len is None else min(int(kv_len), self.L)
-        mask = self.mask[..., :kvl]
-        splits = ops.attn_splits(kvl) if self.attention == "hip" else 1   # (kernel attention: kv_len only picks how many workgroups share a head)
+        splits = ops.attn_splits(kvl) if self._mask_rows is None else 1   # (kernel attention: kv_len only picks how many workgroups share a head)
         if splits > 1 and splits not in self.attn_ws:
             self.attn_ws[splits] = ops.attn_workspace_batched(self.device, B, self.n_heads, self.hd, splits)
-        delta = None
-        K = self.H
-        for b in self.blocks:
-            at = b["attn"]
-            if self.folded and "qkv_rope" in b:   # RMSNorm in the prologue, rotary embedding + cache write in the epilogue: q|k|v lands rotated in qr / the caches
-                ops.gemv_block(h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv_rope"], K, b["qkv_gs"], b["qkv_nbits"], [b["qr"], b["kc"], b["vc"]],
-                               ops.BLOCK_NORM | ops.BLOCK_ROPE, opts=b["qkv_rope_opts"], rope=(cos, sin, pos, self.hd, self.L))
-            elif self.folded:   # RMSNorm in the launch's prologue: every workgroup normalises h itself while its first weights are in flight
-                ops.gemv_block(h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv"], K, b["qkv_gs"], b["qkv_nbits"], [b["q"], b["k"], b["v"]], ops.BLOCK_NORM, opts=b["qkv_opts"])
-            else:
-                ops.add_rmsnorm(h, delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
-                self._grouped(b, "qkv", [b["q"], b["k"], b["v"]])
-                self._adapters(b, "qkv", self.xn, [b["q"], b["k"], b["v"]])
-            if self.kv_bits is not None:   # rotary + quantised cache write, then the attention on the packed rows
-                ops.rope_kvq_cache_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kvq"], b["qr"])
-                att = ops.attn_decode_kvq_batched(b["qr"], b["kvq"], pos, self.att, at.scaling, self.hd, splits=splits, workspace=self.attn_ws.get(splits))
-            elif self.verify:   # the rows are positions of one sequence: all of their keys / values into its cache first, then row i over keys [0, pos[i]]
-                ops.rope_cache_shared(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], b["qr"])
-                att = self._verify_attn(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
-            elif self.attention == "hip" and variant.family == "llama":   # rotary + cache write + attention: one launch
-                att = ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], cos, sin, pos, b["kc"], b["vc"], self.att, at.scaling, splits=splits,
-                                                   workspace=self.attn_ws.get(splits))
-            else:
-                if not (self.folded and "qkv_rope" in b):   # (the q|k|v epilogue has not rotated and cached already); either attention then reads the rotated qr
-                    getattr(ops, self._rope_cache)(b["q"], b["k"], b["v"], *self._rope_extra(b), cos, sin, pos, b["kc"], b["vc"], b["qr"])
-                if self.attention == "hip":
-                    att = ops.attn_decode_batched(b["qr"], b["kc"], b["vc"], pos, self.att, at.scaling, splits=splits, workspace=self.attn_ws.get(splits))
-                else:
-                    att, _ = self.attn_fn(at, b["qr"], b["kc"][:, :, :kvl], b["vc"][:, :, :kvl], mask, dropout=0.0, scaling=at.scaling)
-            o, d = b["o"], b.get("d")
-            if self.folded:
-                # o: h += o(att) in the epilogue; gate|up: RMSNorm prologue + silu(gate) * up epilogue on the paired layer; down: h += down(a) in the epilogue
-                ops.gemv_block(att.reshape(1, -1), None, 0.0, [(o.W_q, o.scale, o.zero, o.out_features)], o.in_features, o.group_size, o.nbits, [h], ops.BLOCK_RESID,
-                               opts=ops.layer_opts(o.opts))
-                ops.gemv_block(h, b["n2"].weight, b["n2"].variance_epsilon, b["gu_pair"], K, b["gu_gs"], b["gu_nbits"], [b["a"]], ops.BLOCK_NORM | ops.BLOCK_SILU, opts=b["gu_pair_opts"])
-                ops.gemv_block(b["a"], None, 0.0, [(d.W_q, d.scale, d.zero, d.out_features)], d.in_features, d.group_size, d.nbits, [h], ops.BLOCK_RESID, opts=ops.layer_opts(d.opts))
-                continue
-            xo = att.reshape(B, -1)
-            self._single(xo, o)
-            self._adapters(b, "o", xo, [self.delta])     # before the residual add (the next add_rmsnorm)
-            ops.add_rmsnorm(h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
-            if self.moe:   # the router fills the block's idx / weights, the two expert launches read them on the device; self.delta = the routed MLP's output
-                ops.moe_router(self.xn, b["router"], b["top_k"], b["renorm"], b["round_w"], idx=b["idx"], weights=b["w"])
-                ops.moe_gate_up(self.xn, b["idx"], b["ex"][0], b["ex"][1], *b["ex_dims"], a=b["a"])
-                ops.moe_down(b["a"], b["idx"], b["w"], b["ex"][2], *b["ex_dims"], out=self.delta)
-                delta = self.delta
-                continue
-            if self.axis0 and not (self.lora and b["lora_gu"]):   # SiLU * up rides in the grouped launch's reduce: no silu_mul launch
-                self._grouped(b, "gu", [b["a"]], flags=ops.BLOCK_SILU)
-            else:   # (an adapted gate | up of an axis-0 model too: the adapter terms come before SiLU)
-                self._grouped(b, "gu", [b["g"], b["u"]])
-                self._adapters(b, "gu", self.xn, [b["g"], b["u"]])
-                ops.silu_mul(b["g"], b["u"], out=b["a"])
-            self._single(b["a"], d)
-            self._adapters(b, "d", b["a"], [self.delta])
-            delta = self.delta
-        ops.add_rmsnorm(h, delta, inner.norm.weight, inner.norm.variance_epsilon, out=self.xn)
-        return self.model.lm_head(self.xn)
+        return SimpleNamespace(cos=cos, sin=sin, pos=pos, kvl=kvl, mask=self.mask[..., :kvl], splits=splits, delta=None)
 
-    def _grouped(self, b, which: str, outs, flags: int = 0) -> None:
-        """q|k|v ("qkv") or gate|up ("gu") of block b on the normalised rows self.xn: one grouped launch, on the layers' own tensors"""
-        if self.axis0:
-            ops.gemv_axis0_grouped(self.xn, b[which], self.H, b[which + "_gs"], b[which + "_nbits"], outs=outs, flags=flags)
-        else:
-            ops.gemv_grouped(self.xn, b[which], self.H, b[which + "_gs"], b[which + "_nbits"], outs=outs, opts=b[which + "_opts"])
+    # ---- the q|k|v stage (b: the block's record, c: _front's) -----------------------------------------------------------------------------------------------
+    def _qkv_folded_rope(self, b, c) -> None:   # RMSNorm in the prologue, rotary embedding + cache write in the epilogue: q|k|v lands rotated in qr / the caches
+        ops.gemv_block(self.h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv_rope"], self.H, b["qkv_gs"], b["qkv_nbits"], [b["qr"], b["kc"], b["vc"]],
+                       ops.BLOCK_NORM | ops.BLOCK_ROPE, opts=b["qkv_rope_opts"], rope=(c.cos, c.sin, c.pos, self.hd, self.L))
+
+    def _qkv_folded(self, b, c) -> None:   # RMSNorm in the launch's prologue: every workgroup normalises h itself while its first weights are in flight
+        ops.gemv_block(self.h, b["n1"].weight, b["n1"].variance_epsilon, b["qkv"], self.H, b["qkv_gs"], b["qkv_nbits"], [b["q"], b["k"], b["v"]], ops.BLOCK_NORM, opts=b["qkv_opts"])
+
+    def _qkv_kernels(self, b, c) -> None:
+        ops.add_rmsnorm(self.h, c.delta, b["n1"].weight, b["n1"].variance_epsilon, out=self.xn)
+        b["grouped"](self, b, "qkv", [b["q"], b["k"], b["v"]])
+        self._adapters(b, "qkv", self.xn, [b["q"], b["k"], b["v"]])
+
+    # ---- the rotary / cache / attention stage -> the attention's output ---------------------------------------------------------------------------------------
+    def _attend_kvq(self, b, c) -> Tensor:   # rotary + quantised cache write, then the attention on the packed rows
+        ops.rope_kvq_cache_batched(b["q"], b["k"], b["v"], c.cos, c.sin, c.pos, b["kvq"], b["qr"])
+        return ops.attn_decode_kvq_batched(b["qr"], b["kvq"], c.pos, self.att, b["attn"].scaling, self.hd, splits=c.splits, workspace=self.attn_ws.get(c.splits))
+
+    def _attend_verify(self, b, c) -> Tensor:   # the rows are positions of one sequence: all of their keys / values into its cache first, then row i over keys [0, pos[i]]
+        ops.rope_cache_shared(b["q"], b["k"], b["v"], c.cos, c.sin, c.pos, b["kc"], b["vc"], b["qr"])
+        return self._verify_attn(b["qr"], b["kc"], b["vc"], c.pos, self.att, b["attn"].scaling, splits=c.splits, workspace=self.attn_ws.get(c.splits))
+
+    def _attend_rope_attn(self, b, c) -> Tensor:   # rotary + cache write + attention: one launch
+        return ops.rope_attn_decode_batched(b["q"], b["k"], b["v"], c.cos, c.sin, c.pos, b["kc"], b["vc"], self.att, b["attn"].scaling, splits=c.splits,
+                                            workspace=self.attn_ws.get(c.splits))
+
+    def _rotary(self, b, c) -> None:   # the family's rotary-and-cache launch; either attention then reads the rotated qr
+        getattr(ops, self._rope_cache)(b["q"], b["k"], b["v"], *self._rope_extra(b), c.cos, c.sin, c.pos, b["kc"], b["vc"], b["qr"])
+
+    def _attend_rotary_hip(self, b, c) -> Tensor:
+        self._rotary(b, c)
+        return ops.attn_decode_batched(b["qr"], b["kc"], b["vc"], c.pos, self.att, b["attn"].scaling, splits=c.splits, workspace=self.attn_ws.get(c.splits))
+
+    def _attend_rotary_sdpa(self, b, c) -> Tensor:
+        self._rotary(b, c)
+        return self._attend_sdpa(b, c)
+
+    def _attend_sdpa(self, b, c) -> Tensor:   # (alone where the q|k|v epilogue has rotated and cached already)
+        return self.attn_fn(b["attn"], b["qr"], b["kc"][:, :, :c.kvl], b["vc"][:, :, :c.kvl], c.mask, dropout=0.0, scaling=b["attn"].scaling)[0]
+
+    # ---- the o / MLP stage (att: the attention's output) ------------------------------------------------------------------------------------------------------
+    def _mlp_folded(self, b, c, att) -> None:
+        # o: h += o(att) in the epilogue; gate|up: RMSNorm prologue + silu(gate) * up epilogue on the paired layer; down: h += down(a) in the epilogue
+        o, d = b["o"], b["d"]
+        ops.gemv_block(att.reshape(1, -1), None, 0.0, b["o_rec"], o.in_features, o.group_size, o.nbits, [self.h], ops.BLOCK_RESID, opts=b["o_opts"])
+        ops.gemv_block(self.h, b["n2"].weight, b["n2"].variance_epsilon, b["gu_pair"], self.H, b["gu_gs"], b["gu_nbits"], [b["a"]], ops.BLOCK_NORM | ops.BLOCK_SILU, opts=b["gu_pair_opts"])
+        ops.gemv_block(b["a"], None, 0.0, b["d_rec"], d.in_features, d.group_size, d.nbits, [self.h], ops.BLOCK_RESID, opts=b["d_opts"])
+
+    def _o_kernels(self, b, att) -> None:
+        """self.delta = o(att) + its adapter terms; h += that, and self.xn = the MLP's normalised input"""
+        xo = att.reshape(self.B, -1)
+        b["single"](self, xo, b["o"])
+        self._adapters(b, "o", xo, [self.delta])     # before the residual add (the next add_rmsnorm)
+        ops.add_rmsnorm(self.h, self.delta, b["n2"].weight, b["n2"].variance_epsilon, out=self.xn)
+
+    def _down_kernels(self, b, c) -> None:
+        b["single"](self, b["a"], b["d"])
+        self._adapters(b, "d", b["a"], [self.delta])
+        c.delta = self.delta
+
+    def _mlp_moe(self, b, c, att) -> None:   # the router fills the block's idx / weights, the two expert launches read them on the device; self.delta = the routed MLP's output
+        self._o_kernels(b, att)
+        ops.moe_router(self.xn, b["router"], b["top_k"], b["renorm"], b["round_w"], idx=b["idx"], weights=b["w"])
+        ops.moe_gate_up(self.xn, b["idx"], b["ex"][0], b["ex"][1], *b["ex_dims"], a=b["a"])
+        ops.moe_down(b["a"], b["idx"], b["w"], b["ex"][2], *b["ex_dims"], out=self.delta)
+        c.delta = self.delta
+
+    def _mlp_silu_in_reduce(self, b, c, att) -> None:   # SiLU * up rides in the grouped launch's reduce: no silu_mul launch
+        self._o_kernels(b, att)
+        b["grouped"](self, b, "gu", [b["a"]], flags=ops.BLOCK_SILU)
+        self._down_kernels(b, c)
+
+    def _mlp_kernels(self, b, c, att) -> None:   # (an adapted gate | up of an axis-0 model too: the adapter terms come before SiLU)
+        self._o_kernels(b, att)
+        b["grouped"](self, b, "gu", [b["g"], b["u"]])
+        self._adapters(b, "gu", self.xn, [b["g"], b["u"]])
+        ops.silu_mul(b["g"], b["u"], out=b["a"])
+        self._down_kernels(b, c)
+
+    # ---- the launches of the unfolded stages: q|k|v ("qkv") or gate|up ("gu") of block b on the normalised rows self.xn as one grouped launch on the layers'
+    # own tensors; o or down as self.delta = L(x), added to the residual stream by the next add_rmsnorm ----------------------------------------------------------
+    def _grouped_axis0(self, b, which: str, outs, flags: int = 0) -> None:
+        ops.gemv_axis0_grouped(self.xn, b[which], self.H, b[which + "_gs"], b[which + "_nbits"], outs=outs, flags=flags)
+
+    def _grouped_axis1(self, b, which: str, outs) -> None:
+        ops.gemv_grouped(self.xn, b[which], self.H, b[which + "_gs"], b[which + "_nbits"], outs=outs, opts=b[which + "_opts"])
+
+    def _single_axis0(self, x: Tensor, L) -> None:
+        ops.gemv_axis0(x, L.W_q, L.scale, L.zero, None, L.out_features, L.in_features, L.group_size, L.nbits, out=self.delta)
+
+    def _single_axis1(self, x: Tensor, L) -> None:
+        ops.gemv(x, L.W_q, L.scale, L.zero, None, L.out_features, L.in_features, L.group_size, L.nbits, out=self.delta, opts=ops.layer_opts(L.opts))
 
     def _adapters(self, b, which: str, x: Tensor, ys) -> None:
         """the adapter terms of group `which` of block b added to the base launch's outputs ys, on the rows x that launch read: one lora_shrink + one
         lora_expand over the adapted members; nothing where the group has none (or the step serves no adapters)"""
-        ad = b["lora_" + which] if self.lora else None
+        ad = b.get("lora_" + which)
         if not ad:
             return
         ops.lora_shrink(x, [a[1] for a in ad], self.lora_ws)
         ops.lora_expand(self.lora_ws, [a[2] for a in ad], [a[3] for a in ad], [ys[a[0]] for a in ad], x.shape[-1])
-
-    def _single(self, x: Tensor, L) -> None:
-        """o or down: self.delta = L(x), added to the residual stream by the next add_rmsnorm"""
-        if self.axis0:
-            ops.gemv_axis0(x, L.W_q, L.scale, L.zero, None, L.out_features, L.in_features, L.group_size, L.nbits, out=self.delta)
-        else:
-            ops.gemv(x, L.W_q, L.scale, L.zero, None, L.out_features, L.in_features, L.group_size, L.nbits, out=self.delta, opts=ops.layer_opts(L.opts))
 
     def account_tokens(self, n: int) -> None:
         """StaticLayer.update's bookkeeping for the n tokens the fused steps appended (kept out of the captured step: one add per layer).  For the
