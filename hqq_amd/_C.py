@@ -85,6 +85,11 @@ SYMBOLS = {
     "hqq_hip_lora_decode_workspace_bytes": (_sz, [_i32, _vp, _i64, _i64]),
     "hqq_hip_lora_shrink": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _sz, _vp]),
     "hqq_hip_lora_expand": (_i32, [_i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
+    # the same pair with one adapter per ROW, picked on the device from a bank of stacked adapters (csrc/lora_decode.hip; added at ABI 9 without a bump:
+    # nothing that existed changed)
+    "hqq_hip_lora_routed_covers": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _i32, _i32]),
+    "hqq_hip_lora_shrink_routed": (_i32, [_i32, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _sz, _vp]),
+    "hqq_hip_lora_expand_routed": (_i32, [_i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
     # the routed expert MLP of a mixture-of-experts block (csrc/moe.hip; added at ABI 9 without a bump: nothing that existed changed)
     "hqq_hip_moe_covers": (_i32, [_i32, _i64, _i64, _i64, _i64, _i64, _i64, _i32]),
     "hqq_hip_moe_gate_up": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),

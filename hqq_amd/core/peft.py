@@ -310,3 +310,125 @@ class PeftUtils:
         autoname_modules(model)
         for _, layer in _lora_layers(model):
             layer.load_state_dict(params[layer.name])
+
+
+class LoRABank:
+    """Several adapters for ONE adapted model, stacked per wrapper so that the fused decode step can pick one per batch row on the device
+    (ops.lora_shrink_routed / ops.lora_expand_routed; llama_fused.FusedLlamaStep(lora=True, lora_bank=bank)).
+
+    `model` already carries its HQQLinearLoRA wrappers (PeftUtils.add_lora).  Every adapter is a {module_name: state_dict} dictionary keyed by
+    autoname_modules names — what PeftUtils.save_lora_weights writes as "parameters" (v0.2), or the bare v0.1 dictionary.  Per wrapper the bank holds
+    A [n, K, r] and B [n, r, N] in `dtype` (default: the dtype of the wrapper's lora_A) and scaling float32 [n] — float32(float(scaling)), the value the
+    one-adapter kernels are passed as a host float — all on the wrapper's device.  Refused, each with a ValueError that names the layer and the adapter's
+    index: an adapter that lacks a wrapped layer, lora_A / lora_B of another shape than the wrapper's [K, r] / [r, N] (one rank per layer across the
+    bank), a bias that is not None, lora_A and lora_B of different dtypes.
+
+    The tensors are allocated once: set() and activate() copy in place, so a decode step or a captured graph built on the bank stays valid whatever
+    is loaded into it later.  activate(model, i) makes the WRAPPERS hold adapter i (or no adapter: i = -1 zeroes lora_B), which is how the model's own
+    forward — the prefill, the composed decode route — runs under an adapter of the bank; the wrappers are left holding the last adapter activated."""
+
+    def __init__(self, model: nn.Module, adapters, dtype: Optional[torch.dtype] = None):
+        autoname_modules(model)
+        self.names = [name for name, _ in _lora_layers(model)]
+        if not self.names:
+            raise ValueError("hqq_amd: LoRABank needs a model that carries HQQLinearLoRA wrappers (PeftUtils.add_lora)")
+        adapters = list(adapters)
+        if not adapters:
+            raise ValueError("hqq_amd: LoRABank needs at least one adapter")
+        self.n = len(adapters)
+        self._layers = {}
+        self._host_scaling = {name: [0.0] * self.n for name in self.names}   # the float32 values of the scaling tensors, as Python floats (activate reads these)
+        for name, w in _lora_layers(model):
+            dt = w.lora_A.dtype if dtype is None else dtype
+            K, r, N = w.in_features, w.r, w.out_features
+            dev = w.lora_A.device
+            self._layers[name] = (torch.empty(self.n, K, r, dtype=dt, device=dev), torch.empty(self.n, r, N, dtype=dt, device=dev),
+                                  torch.empty(self.n, dtype=float32, device=dev))
+        for i, params in enumerate(adapters):
+            self.set(i, params)
+
+    @staticmethod
+    def _params(file_or_params) -> dict:
+        """the {module_name: state_dict} dictionary of a file PeftUtils.save_lora_weights wrote (v0.2, or the bare v0.1 form), or of such a dictionary"""
+        data = file_or_params
+        if not isinstance(data, dict):
+            data = torch.load(data, map_location="cpu", weights_only=True)
+        if ("peft_config" in data) and ("parameters" in data):
+            data = data["parameters"]
+        return data
+
+    @classmethod
+    def from_files(cls, model: nn.Module, filenames, dtype: Optional[torch.dtype] = None) -> "LoRABank":
+        return cls(model, [cls._params(f) for f in filenames], dtype)
+
+    @classmethod
+    def from_params(cls, model: nn.Module, parameters, dtype: Optional[torch.dtype] = None) -> "LoRABank":
+        return cls(model, [cls._params(p) for p in parameters], dtype)
+
+    @staticmethod
+    def _scaling(s) -> float:
+        return float(s.detach().float().item()) if isinstance(s, Tensor) else float(s)
+
+    def set(self, i: int, file_or_params) -> None:
+        """adapter `i` <- the file or dictionary, copied into the bank's tensors in place (their addresses stay: no step or graph is invalidated)"""
+        if not 0 <= int(i) < self.n:
+            raise ValueError(f"hqq_amd: LoRABank.set: adapter index {i} outside 0 .. {self.n - 1}")
+        params = self._params(file_or_params)
+        checked = []
+        for name in self.names:
+            A_bank, B_bank, _ = self._layers[name]
+            sd = params.get(name) if isinstance(params, dict) else None
+            if not isinstance(sd, dict) or any(k not in sd for k in ("lora_A", "lora_B", "scaling")):
+                raise ValueError(f"hqq_amd: LoRABank: adapter {i} has no entry for the adapted layer {name!r}")
+            A, B = sd["lora_A"], sd["lora_B"]
+            A, B = getattr(A, "data", A), getattr(B, "data", B)
+            if tuple(A.shape) != tuple(A_bank.shape[1:]) or tuple(B.shape) != tuple(B_bank.shape[1:]):
+                raise ValueError(f"hqq_amd: LoRABank: adapter {i}, layer {name!r}: lora_A {tuple(A.shape)} / lora_B {tuple(B.shape)} where the wrapper has "
+                                 f"{tuple(A_bank.shape[1:])} / {tuple(B_bank.shape[1:])} (one rank per layer across the bank)")
+            if sd.get("bias") is not None:
+                raise ValueError(f"hqq_amd: LoRABank: adapter {i}, layer {name!r} carries a bias, which the routed kernels do not serve")
+            if A.dtype != B.dtype:
+                raise ValueError(f"hqq_amd: LoRABank: adapter {i}, layer {name!r}: lora_A is {A.dtype} and lora_B {B.dtype} (mixed dtypes)")
+            checked.append((name, A, B, self._scaling(sd["scaling"])))
+        for name, A, B, s in checked:   # (nothing is written before the whole adapter has been accepted)
+            A_bank, B_bank, sc = self._layers[name]
+            A_bank[i].copy_(A)
+            B_bank[i].copy_(B)
+            sc[i] = s
+            self._host_scaling[name][i] = float(torch.tensor(s, dtype=float32))
+
+    def layer(self, name: str):
+        """(A [n, K, r], B [n, r, N], scaling float32 [n]) of the wrapper called `name`"""
+        return self._layers[name]
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for ts in self._layers.values() for t in ts)
+
+    def pointers(self) -> tuple:
+        """the addresses of the bank's tensors and n: what a decoder keeps its step and graphs by"""
+        return (self.n,) + tuple(t.data_ptr() for name in self.names for t in self._layers[name])
+
+    def scaling_key(self, i: int):
+        """adapter i's scalings over the bank's layers as a hashable value (None for -1): what a captured forward of the WRAPPERS depends on beyond the
+        tensors activate() rewrites in place — `scaling` is a Python float there, a constant of the capture"""
+        return None if int(i) < 0 else tuple(self._host_scaling[name][int(i)] for name in self.names)
+
+    def activate(self, model: nn.Module, i: int) -> None:
+        """the model's wrappers <- adapter i, in place (lora_A.data.copy_, lora_B.data.copy_, scaling as a Python float); i = -1: lora_B <- 0, the base
+        model.  The wrappers are left holding it."""
+        i = int(i)
+        if not -1 <= i < self.n:
+            raise ValueError(f"hqq_amd: LoRABank.activate: adapter index {i} outside -1 .. {self.n - 1}")
+        wrappers = dict(_lora_layers(model))
+        if sorted(wrappers) != sorted(self.names):
+            raise ValueError("hqq_amd: LoRABank.activate: the model's wrappers are not the ones the bank was stacked for")
+        for name in self.names:
+            w = wrappers[name]
+            A_bank, B_bank, sc = self._layers[name]
+            if i < 0:
+                w.lora_B.data.zero_()
+                continue
+            w.lora_A.data.copy_(A_bank[i])
+            w.lora_B.data.copy_(B_bank[i])
+            w.scaling = self._host_scaling[name][i]

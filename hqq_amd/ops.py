@@ -998,6 +998,103 @@ def lora_apply(x: Tensor, adapters, ys, workspace: Tensor | None = None):
     return ys
 
 
+# ---- the same pair with one adapter per ROW, picked on the device from banks of stacked adapters (hqq_hip_lora_shrink_routed / _expand_routed) -----------
+LORA_MAX_ADAPTERS = 256
+
+
+def lora_routed_covers(dtype, lora_dtype, n_adapters, M, Ns, K, rs) -> bool:
+    """what hqq_hip_lora_shrink_routed / hqq_hip_lora_expand_routed serve (the library's own answer, nothing launched): what lora_decode_covers
+    accepts, with 1 .. LORA_MAX_ADAPTERS adapters in the bank"""
+    Ns, rs = tuple(Ns), tuple(rs)
+    if dtype not in _DT or lora_dtype not in _DT or len(Ns) != len(rs) or not rs:
+        return False
+    return bool(_C.lib().hqq_hip_lora_routed_covers(len(rs), _i64s(Ns), _i64s(rs), int(n_adapters), int(M), int(K), _DT[dtype], _DT[lora_dtype]))
+
+
+def _lora_slots(slots: Tensor, M: int, device, who: str) -> None:
+    if not isinstance(slots, Tensor) or slots.dtype != torch.int64 or slots.dim() != 1 or slots.numel() != M or not slots.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes one slot per row: a dense int64 tensor of {M} elements")
+    if slots.device != device:
+        raise TypeError(f"hqq_amd: {who} reads the slots on the device the rows are on")
+
+
+def lora_shrink_routed(x: Tensor, A_banks, slots: Tensor, workspace: Tensor) -> None:
+    """lora_shrink with one adapter per row: A_banks are [n, K, r_l] each (one dtype, contiguous, the same n), slots int64 [M] on the device; row m
+    reads A_banks[l][slots[m]], and a row whose slot is outside [0, n) (-1: no adapter) reads nothing and leaves no partial.  ONE launch
+    (hqq_hip_lora_shrink_routed); the slots are read by the kernel only, so a captured call follows a later slots.copy_().  A row's bits are those of
+    lora_shrink on that row alone with its adapter.  Raises NotImplementedError outside lora_routed_covers()."""
+    As = list(A_banks)
+    n = len(As)
+    _dev(x, workspace, slots, *As)
+    _lora_ws(workspace, "lora_shrink_routed")
+    if not 1 <= n <= GEMV_MAX_GROUP:
+        raise NotImplementedError(f"hqq_amd: lora_shrink_routed takes 1 .. {GEMV_MAX_GROUP} banks per call, got {n}")
+    K = x.shape[-1]
+    if any(A.dim() != 3 or A.shape[1] != K or A.shape[0] != As[0].shape[0] or not A.is_contiguous() for A in As):
+        raise ValueError(f"hqq_amd: lora_shrink_routed needs dense A banks [n, K, r] of one n for x of {K} features, got {[tuple(A.shape) for A in As]}")
+    if len({A.dtype for A in As}) != 1 or any(A.device != x.device for A in As) or workspace.device != x.device:
+        raise TypeError("hqq_amd: lora_shrink_routed needs banks of ONE dtype, on x's device together with the workspace")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    _lora_slots(slots, x2.shape[0], x.device, "lora_shrink_routed")
+    VP = ctypes.c_void_p * n
+    with torch.cuda.device(x.device):
+        rc = _C.lib().hqq_hip_lora_shrink_routed(n, _p(x2), VP(*[_p(A) for A in As]), _i64s(A.shape[2] for A in As), int(As[0].shape[0]), _p(slots),
+                                                 x2.shape[0], int(K), _dt(x.dtype), _dt(As[0].dtype), _p(workspace), workspace.numel(), _stream())
+    _C.check(rc, "hqq_hip_lora_shrink_routed")
+
+
+def lora_expand_routed(workspace: Tensor, B_banks, scalings, slots: Tensor, ys, K: int) -> None:
+    """lora_expand with one adapter per row, for the group lora_shrink_routed just served with the same slots: B_banks [n, r_l, N_l] each (one dtype,
+    contiguous), scalings float32 [n] tensors ON THE DEVICE (one per bank: replacing an adapter's scaling does not touch a captured call), ys dense
+    [M, N_l] outputs in fp16 / bf16 that hold the base layers' results.  Row m of y_l takes scalings[l][slots[m]] and B_banks[l][slots[m]]; a row whose
+    slot is outside [0, n) is not written.  ONE launch (hqq_hip_lora_expand_routed)."""
+    Bs, ys, scalings = list(B_banks), list(ys), list(scalings)
+    n = len(Bs)
+    _dev(workspace, slots, *Bs, *ys)
+    _lora_ws(workspace, "lora_expand_routed")
+    if not 1 <= n <= GEMV_MAX_GROUP:
+        raise NotImplementedError(f"hqq_amd: lora_expand_routed takes 1 .. {GEMV_MAX_GROUP} banks per call, got {n}")
+    if len(ys) != n or len(scalings) != n:
+        raise ValueError("hqq_amd: lora_expand_routed needs one scaling tensor and one output per bank")
+    if any(B.dim() != 3 or B.shape[0] != Bs[0].shape[0] or not B.is_contiguous() for B in Bs):
+        raise ValueError("hqq_amd: lora_expand_routed needs dense B banks [n, r, N] of one n")
+    na = int(Bs[0].shape[0])
+    if any(not isinstance(s, Tensor) or s.dtype != torch.float32 or s.dim() != 1 or s.numel() != na or not s.is_contiguous() for s in scalings):
+        raise ValueError(f"hqq_amd: lora_expand_routed needs the scalings as dense float32 tensors of {na} elements")
+    M = ys[0].numel() // Bs[0].shape[2]
+    if any(y.numel() != M * B.shape[2] or y.shape[-1] != B.shape[2] or not y.is_contiguous() or y.dtype != ys[0].dtype for y, B in zip(ys, Bs)):
+        raise ValueError(f"hqq_amd: lora_expand_routed updates dense [M, N] outputs of one dtype and {M} rows, N that of each bank")
+    if len({B.dtype for B in Bs}) != 1 or any(t.device != workspace.device for t in Bs + ys + scalings):
+        raise TypeError("hqq_amd: lora_expand_routed needs banks of ONE dtype, on the workspace's device together with the scalings and the outputs")
+    _lora_slots(slots, M, workspace.device, "lora_expand_routed")
+    VP = ctypes.c_void_p * n
+    with torch.cuda.device(workspace.device):
+        rc = _C.lib().hqq_hip_lora_expand_routed(n, _p(workspace), workspace.numel(), VP(*[_p(B) for B in Bs]), VP(*[_p(s) for s in scalings]),
+                                                 VP(*[_p(y) for y in ys]), _i64s(B.shape[2] for B in Bs), _i64s(B.shape[1] for B in Bs), na, _p(slots),
+                                                 int(M), int(K), _dt(ys[0].dtype), _dt(Bs[0].dtype), _stream())
+    _C.check(rc, "hqq_hip_lora_expand_routed")
+
+
+def lora_apply_routed(x: Tensor, banks, slots: Tensor, ys, workspace: Tensor | None = None):
+    """ys[l][m] += (x[m] @ A_l[a] @ B_l[a] * scaling_l[a]).to(x.dtype) in place with a = slots[m], for `banks` = [(A_bank_l, B_bank_l, scaling_l), ...]
+    that share x: lora_shrink_routed, then lora_expand_routed (two launches for the whole group).  Rows whose slot names no adapter keep ys[l][m].
+    workspace: lora_decode_workspace(...) of at least this group's size; None allocates one.  Returns ys."""
+    banks = list(banks)
+    As, Bs = [b[0] for b in banks], [b[1] for b in banks]
+    if any(A.dim() != 3 or B.dim() != 3 or A.shape[2] != B.shape[1] or A.shape[0] != B.shape[0] for A, B in zip(As, Bs)):
+        raise ValueError("hqq_amd: lora_apply_routed needs A [n, K, r] and B [n, r, N] per bank")
+    if any(A.dtype != B.dtype for A, B in zip(As, Bs)):
+        raise TypeError("hqq_amd: lora_apply_routed: the A and B banks must share a dtype")
+    K = x.shape[-1]
+    if workspace is None:
+        workspace = lora_decode_workspace(x.device, x.numel() // K, K, [A.shape[2] for A in As])
+    lora_shrink_routed(x, As, slots, workspace)
+    lora_expand_routed(workspace, Bs, [b[2] for b in banks], slots, ys, K)
+    return ys
+
+
 def _forward_axis0(x, W_q, scale, zero, bias, N, K, group_size, nbits, out, opts, library_gemm: bool = False) -> Tensor:
     """axis-0 layers: decode sizes through hqq_hip_gemv_axis0; GEMV_MAX_M + 1 .. AXIS0_GEMM_ROUTE_MAX_M rows through hqq_hip_gemm_axis0 (unless
     library_gemm); everything else as HQQLinear has always run them — the HIP dequantise kernel (axis 0) + torch.matmul, then `out += bias`

@@ -71,6 +71,25 @@ def check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attent
         raise ValueError("verify_attention: 'tile' is the speculative verify step's attention kernel (speculate='ngram')")
 
 
+def check_adapters(bank, adapters, B: int) -> list:
+    """the `adapter` / `adapters` keyword of generate() / generate_batch() as one bank index per prompt: None — every prompt decodes on the base model (-1) when
+    there is a bank, and nothing is asked when there is none; otherwise a bank is needed and every entry is an int in [-1, bank.n) (-1: the base model).  Returns the
+    list (empty without a bank); anything else is a ValueError"""
+    if bank is None:
+        if adapters is not None:
+            raise ValueError("hqq_amd: adapter / adapters pick from a LoRABank: the decoder was built without one (lora_bank=)")
+        return []
+    if adapters is None:
+        return [-1] * B
+    adapters = list(adapters)
+    if len(adapters) != B:
+        raise ValueError(f"hqq_amd: {len(adapters)} adapters for {B} prompts")
+    for a in adapters:
+        if isinstance(a, bool) or not isinstance(a, int) or not -1 <= a < bank.n:
+            raise ValueError(f"hqq_amd: adapter {a!r} is not an index into the bank (-1 .. {bank.n - 1}; -1: the base model)")
+    return adapters
+
+
 def opt_ins(**keywords) -> set:
     """the decode-step opt-in keywords of GraphedGreedyDecoder and HFGenerator (axis0, qk_norm, qkv_bias, lora, moe), each "model" or "fused": the names of those
     set to "fused" (what llama_fused.resolve takes); ValueError naming the first keyword with another value"""
@@ -98,6 +117,14 @@ class GraphedGreedyDecoder:
     (default): the model's own forward, as before.  "fused" (opt-in): where llama_fused.supports_lora accepts the model, the fused step with one
     ops.lora_shrink + one ops.lora_expand behind each base launch that has adapted layers (`fused_lora`; `fused` stays the Llama flag), and
     generate_batch's batched step where supports_lora_batch accepts the batch.  An adapted model quantised along axis 0 needs axis0="fused" as well.
+    lora_bank (opt-in): a core.peft.LoRABank stacked for the model — several adapters over the one quantised base.  generate(ids, n, adapter=i) and
+    generate_batch(prompts, n, adapters=[...]) then decode each prompt under the adapter it names (-1 or None: the base model): the prefill of a prompt is
+    bank.activate(model, i) followed by the model's own forward, and with lora="fused" the fused step reads the bank itself and picks row b's adapter on the device
+    from step.slots (ops.lora_shrink_routed / ops.lora_expand_routed), so prompts under different adapters share one pass over the base weights.  The kept step and
+    graphs depend on the bank's tensors, not on the wrappers': another adapter=, another mix of adapters= and bank.set(...) rebuild nothing.  Where the fused step is
+    not taken (lora="model", a model or batch it refuses) the bank still serves: activate, then the existing route, prompt after prompt.  Either way the model's
+    wrappers are LEFT HOLDING THE LAST ADAPTER ACTIVATED (the last prompt's), lora_B zeroed after a base-model prompt.  adapter / adapters without a bank, or an
+    entry outside [-1, bank.n), is a ValueError.
     moe: what a Mixtral or Qwen3-MoE model whose experts are HQQExperts decodes through.  "model" (default): the model's own forward, as before.  "fused"
     (opt-in): where llama_fused.supports_moe accepts the model, the fused step with ops.moe_router, ops.moe_gate_up and ops.moe_down in the MLP's place
     (`fused_moe`; `fused` stays the Llama flag), and generate_batch's batched step where supports_moe_batch accepts the batch (otherwise the prompts decode one
@@ -127,7 +154,7 @@ class GraphedGreedyDecoder:
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
                  qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
-                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, verify_attention: str = "rows"):
+                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, verify_attention: str = "rows", lora_bank=None):
         from transformers import StaticCache
         from . import llama_fused
         from .kv_cache import check_kv_group_size, kv_cache_bits
@@ -138,6 +165,7 @@ class GraphedGreedyDecoder:
         check_kv_group_size(kv_cache, kv_group_size)
         self.kv_cache, self.kv_group_size = kv_cache, kv_group_size
         self.model = model.eval()
+        self.lora_bank = lora_bank
         self.axis0, self.qk_norm, self.qkv_bias, self.lora, self.moe = axis0, qk_norm, qkv_bias, lora, moe
         # the llama_fused.StepVariant this model decodes through (resolve's precedence among the opt-ins), or None: the model's own forward
         self.variant = llama_fused.resolve(model, opted) if fused else None
@@ -191,7 +219,10 @@ class GraphedGreedyDecoder:
 
     def _step_keywords(self) -> dict:
         """what the fused steps are told about the cache (nothing with the dense one: their call is the one it was)"""
-        return {} if self.kv_bits is None else {"kv_cache": self.kv_cache}
+        kw = {} if self.kv_bits is None else {"kv_cache": self.kv_cache}
+        if self.lora_bank is not None and self.fused_lora:   # (the other variants serve no adapters: with them the bank works through activate alone)
+            kw["lora_bank"] = self.lora_bank
+        return kw
 
     @property
     def kv_cache_bytes(self) -> int:
@@ -265,6 +296,9 @@ class GraphedGreedyDecoder:
         graphs silently decoded with stale copies).  In-place edits through .data bypass the version counters: call reset() after those."""
         from ..core.quantize import HQQLinear
         fp = [getattr(HQQLinear, "backend", None), self._verify_attention]   # (the verify step's attention kernel is baked into the kept step and its graphs)
+        bank = self.lora_bank
+        if bank is not None:   # the bank's tensors in the place of the wrappers' adapter tensors below (activate rewrites those; set / activate keep the bank's)
+            fp.append(bank.pointers())
         for m in self.model.modules():
             W, meta = getattr(m, "W_q", None), getattr(m, "meta", None)
             if isinstance(W, Tensor):
@@ -272,7 +306,7 @@ class GraphedGreedyDecoder:
                 ver = lambda t: None if (t is None or t.is_inference()) else t._version   # noqa: E731
                 fp.append((id(m), W.data_ptr(), ver(W), None if sc is None else sc.data_ptr(), ver(sc)))
             A, B = getattr(m, "lora_A", None), getattr(m, "lora_B", None)
-            if isinstance(A, Tensor) and isinstance(B, Tensor) and hasattr(m, "linear_layer"):
+            if isinstance(A, Tensor) and isinstance(B, Tensor) and hasattr(m, "linear_layer") and bank is None:
                 # an adapter: load_lora_weights / cast replace .data (a kept step or graph would read freed tensors); `scaling` is baked into the step
                 ver = lambda t: None if t.is_inference() else t._version   # noqa: E731
                 sc = m._scaling_float() if hasattr(m, "_scaling_float") else getattr(m, "scaling", None)
@@ -291,12 +325,17 @@ class GraphedGreedyDecoder:
         self._spec = None
 
     @torch.no_grad()
-    def generate(self, input_ids: Tensor, max_new_tokens: int, use_graph: bool = True, eos_token_id: int | None = None, check_every: int = 16) -> Tensor:
+    def generate(self, input_ids: Tensor, max_new_tokens: int, use_graph: bool = True, eos_token_id: int | None = None, check_every: int = 16,
+                 adapter: int | None = None) -> Tensor:
         """continuation of a single sequence [1, T] — greedy, or sampled when the decoder was built with do_sample=True; returns [1, T + n], n = max_new_tokens, or fewer
         when eos_token_id is given and was produced (the sequence then ends with it; the host looks at the tokens every `check_every` steps, never per token).
         The static cache, the fused step (its paired / rotary-paired layer copies) and the captured graphs are KEPT between calls: the next prompt resets the cache in
-        place (StaticCache.reset keeps the tensors) and replays the same graphs — hqq/utils/generation_hf.py:190-207, :313-327 keep theirs the same way; reset() drops them."""
+        place (StaticCache.reset keeps the tensors) and replays the same graphs — hqq/utils/generation_hf.py:190-207, :313-327 keep theirs the same way; reset() drops them.
+        adapter (with lora_bank): the bank's adapter the sequence decodes under; None or -1: the base model.  The wrappers are left holding it."""
         assert input_ids.shape[0] == 1, "one sequence (the decode-shaped bs=1 path)"
+        slot = check_adapters(self.lora_bank, None if adapter is None else [adapter], 1)
+        if slot:
+            self.lora_bank.activate(self.model, slot[0])
         T = input_ids.shape[1]
         assert T + max_new_tokens <= self.max_cache_len
         ids = input_ids.to(self.device)
@@ -331,6 +370,13 @@ class GraphedGreedyDecoder:
             # (glue="kernels" is the comparison leg with the separate front and back: its argmax, hand-over and increment stay torch ops)
             st = self._state = self._holder(self.step, first, torch.empty_like(first), torch.tensor([T], device=self.device), self.graphs, lambda kv: kv,
                                             argmax_advance=self.glue != "kernels")
+        if slot and getattr(self.step, "slots", None) is not None:
+            self.step.slots.fill_(slot[0])
+        elif slot:
+            # the composed route under a bank: a captured forward of the wrappers reads lora_A / lora_B in place (activate keeps their addresses) but holds
+            # `scaling`, a Python float, as a constant — so its graphs are kept per set of scalings (adapters trained with one alpha / r share them)
+            sk = self.lora_bank.scaling_key(slot[0])
+            st["key"] = lambda kv: (sk, kv)
         self.tok, self.next_tok, self.pos = st["tok"], st["next_tok"], st["pos"]
         toks = [self.tok.clone()]
         done = 0        # tokens the host has looked at
@@ -518,7 +564,8 @@ class GraphedGreedyDecoder:
 
     # ---- a batch of prompts through ONE fused step per token (llama_fused.FusedLlamaStep with batch = B) ----------------------------------------------------------
     @torch.no_grad()
-    def generate_batch(self, prompts, max_new_tokens: int, use_graph: bool = True, eos_token_id: int | None = None, check_every: int = 16) -> list:
+    def generate_batch(self, prompts, max_new_tokens: int, use_graph: bool = True, eos_token_id: int | None = None, check_every: int = 16,
+                       adapters=None) -> list:
         """continuations of B prompts of any lengths (a list of 1-D or [1, T_b] int64 tensors), decoded together: each decode step runs the B sequences
         through one fused step (every linear launch takes the B rows at once, so the weights are streamed once per step for all of them) and is
         captured / replayed as generate()'s is, one graph per (B, cache bucket of the largest row position), kept across calls.  Returns one
@@ -528,15 +575,18 @@ class GraphedGreedyDecoder:
         are copied into row b of a kept B-row StaticCache; row b's first token comes from its own prefill logits.  The B-row cache's cumulative_length
         is not meaningful (its rows have different lengths): only the fused step reads that cache.
         B == 1 is generate().  A model the batched step does not cover at B rows (llama_fused.supports_batch), or a cache / attention setting it refuses,
-        decodes the prompts one after another through generate() instead: the same tokens, only slower."""
+        decodes the prompts one after another through generate() instead: the same tokens, only slower.
+        adapters (with lora_bank): one bank index per prompt (-1: the base model); None: the base model for all.  Prompt b is prefilled under its adapter
+        (bank.activate, then the model's own forward) and row b of the batched step decodes under it (step.slots), in one pass over the base weights for all rows."""
         ids = [torch.as_tensor(p).view(1, -1).to(device=self.device, dtype=torch.int64) for p in prompts]
         B = len(ids)
+        slots = check_adapters(self.lora_bank, adapters, B)
         if B == 0:
             return []
         lengths = [x.shape[1] for x in ids]
         check_batch_lengths(lengths, max_new_tokens, self.max_cache_len)
         if B == 1:
-            return [self.generate(ids[0], max_new_tokens, use_graph=use_graph, eos_token_id=eos_token_id, check_every=check_every)]
+            return [self.generate(ids[0], max_new_tokens, use_graph=use_graph, eos_token_id=eos_token_id, check_every=check_every, adapter=slots[0] if slots else None)]
         fp = self._fingerprint()
         if getattr(self, "_fp", None) != fp:
             self.reset()
@@ -546,12 +596,15 @@ class GraphedGreedyDecoder:
         if not kept:
             st = self._batch_state(B)
             if st is None:   # not covered: one prompt after another
-                return [self.generate(x, max_new_tokens, use_graph=use_graph, eos_token_id=eos_token_id, check_every=check_every) for x in ids]
+                return [self.generate(x, max_new_tokens, use_graph=use_graph, eos_token_id=eos_token_id, check_every=check_every, adapter=slots[b] if slots else None)
+                        for b, x in enumerate(ids)]
         bc, scratch = st["cache"], st["scratch"]
         bc.reset()
         firsts = []
         for b, x in enumerate(ids):   # prefill: each prompt alone, then its first T_b key / value positions into row b
             scratch.reset()
+            if slots:
+                self.lora_bank.activate(self.model, slots[b])
             out = self.model(x, past_key_values=scratch, cache_position=torch.arange(lengths[b], device=self.device), use_cache=True)
             firsts.append(self._pick(out.logits[:, -1]))
             for dst, src in zip(bc.layers, scratch.layers):
@@ -562,6 +615,8 @@ class GraphedGreedyDecoder:
                 dst.values[b, :, :lengths[b]].copy_(src.values[0, :, :lengths[b]])
         st["tok"].copy_(torch.cat(firsts, dim=0))
         st["pos"].copy_(torch.tensor(lengths, device=self.device))
+        if slots and getattr(st["step"], "slots", None) is not None:
+            st["step"].slots.copy_(torch.tensor(slots, dtype=torch.int64))
         toks = [st["tok"].clone()]
         done = 0
         n = max_new_tokens
@@ -628,12 +683,13 @@ class HFGenerator:
     the EOS all the same); "output_tokens" holds every generated token before the EOS (the reference's slice drops the last one it generated, generation_hf.py:493);
     a prompt that leaves less than max_new_tokens of cache generates what fits.
     speculate / draft_rows / ngram_max / verify_attention and attention are GraphedGreedyDecoder's keywords (defaults: no speculation, HF's attention function); speculation is served
-    with attention="hip" only, and everything else decodes as before (`decoder.speculating` says which)."""
+    with attention="hip" only, and everything else decodes as before (`decoder.speculating` says which).
+    lora_bank, and the adapter / adapters keywords of generate / generate_batch, are GraphedGreedyDecoder's: passed through."""
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
                  compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
                  qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
-                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, attention: str = "sdpa", verify_attention: str = "rows"):
+                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, attention: str = "sdpa", verify_attention: str = "rows", lora_bank=None):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
@@ -654,7 +710,7 @@ class HFGenerator:
         self.compile_options = compile_options
         self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
                                             qkv_bias=qkv_bias, lora=lora, moe=moe, kv_cache=kv_cache, kv_group_size=kv_group_size, speculate=speculate,
-                                            draft_rows=draft_rows, ngram_max=ngram_max, attention=attention, verify_attention=verify_attention)
+                                            draft_rows=draft_rows, ngram_max=ngram_max, attention=attention, verify_attention=verify_attention, lora_bank=lora_bank)
         self.init()
 
     @staticmethod
@@ -697,7 +753,7 @@ class HFGenerator:
         return self.tokenizer([prompt], return_tensors="pt").to(device=self.device)
 
     @torch.no_grad()   # (not inference_mode: graph capture updates generator state tensors in place, which inference tensors refuse outside that mode)
-    def generate(self, prompt: str, use_chat_template: bool = True, verbose: bool = True, print_tokens: bool = False) -> dict:
+    def generate(self, prompt: str, use_chat_template: bool = True, verbose: bool = True, print_tokens: bool = False, adapter: int | None = None) -> dict:
         inputs = self.tokenize_prompt(prompt, use_chat_template=use_chat_template)
         ids = inputs["input_ids"].to(torch.int64)
         T = ids.shape[1]
@@ -705,7 +761,7 @@ class HFGenerator:
         if n < 1:
             raise ValueError(f"hqq_amd: the prompt ({T} tokens) leaves no room in a cache of {self.cache_size}")
         eos = getattr(self.tokenizer, "eos_token_id", None)
-        out = self.decoder.generate(ids, n, use_graph=self.use_graph, eos_token_id=eos)
+        out = self.decoder.generate(ids, n, use_graph=self.use_graph, eos_token_id=eos, **({} if adapter is None else {"adapter": adapter}))
         new = out[0, T:]
         if eos is not None and new.numel() and int(new[-1]) == eos:
             new = new[:-1]
@@ -716,7 +772,7 @@ class HFGenerator:
         return {"output_text": output_text, "output_tokens": output_tokens, "input_tokens": ids[0].cpu()}
 
     @torch.no_grad()
-    def generate_batch(self, prompts, use_chat_template: bool = True, verbose: bool = True, print_tokens: bool = False) -> list:
+    def generate_batch(self, prompts, use_chat_template: bool = True, verbose: bool = True, print_tokens: bool = False, adapters=None) -> list:
         """generate() for several prompts decoded together (GraphedGreedyDecoder.generate_batch): one dict per prompt with generate()'s keys.  Every prompt gets
         the same number of new tokens: max_new_tokens, or what the longest prompt leaves of the cache"""
         ids = [self.tokenize_prompt(p, use_chat_template=use_chat_template)["input_ids"].to(torch.int64) for p in prompts]
@@ -727,7 +783,7 @@ class HFGenerator:
         if n < 1:
             raise ValueError(f"hqq_amd: the longest prompt ({T} tokens) leaves no room in a cache of {self.cache_size}")
         eos = getattr(self.tokenizer, "eos_token_id", None)
-        outs = self.decoder.generate_batch(ids, n, use_graph=self.use_graph, eos_token_id=eos)
+        outs = self.decoder.generate_batch(ids, n, use_graph=self.use_graph, eos_token_id=eos, **({} if adapters is None else {"adapters": adapters}))
         res = []
         for x, out in zip(ids, outs):
             new = out[0, x.shape[1]:]

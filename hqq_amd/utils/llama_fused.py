@@ -30,6 +30,8 @@ That is the base sequence.  WHICH model gets which sequence is one value, a Step
                                                      rotary-paired q / k (their epilogue rotates before a bias could be added)
     llama + lora          lora                       behind each of the four base launches that has adapted layers, one                 8 + 2 per adapted
                                                      ops.lora_shrink + one ops.lora_expand; never folded                                group
+                                                     (lora_bank=: ops.lora_shrink_routed + ops.lora_expand_routed in their place,
+                                                     one adapter of a core.peft.LoRABank per row, picked on the device from step.slots)
     llama + lora + axis0  lora and axis0             both of the above; an adapted gate|up runs without SiLU in its reduce, then        7 or 8, + 2 per
                                                      silu_mul (the adapter terms come before SiLU)                                      adapted group
     mixtral               moe                        ops.moe_router (logits, softmax, top-k and renormalisation in one launch, into     8, never folded
@@ -544,7 +546,7 @@ class FusedLlamaStep:
 
     def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
                  qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False, kv_cache: str | None = None, verify: bool = False,
-                 verify_attention: str = "rows"):
+                 verify_attention: str = "rows", lora_bank=None):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -578,7 +580,13 @@ class FusedLlamaStep:
         verify_attention (with verify=True): "rows" (default) — ops.attn_decode_shared, every row bit-identical to the one-row kernel at its position, every key read
         once PER ROW.  "tile" (opt-in) — ops.attn_decode_tiled in its place: one workgroup per (head, split) reads each key once for ALL rows; deterministic, a row
         independent of the other rows' queries, within a derived band of float64 attention and NOT bit-identical to the one-row kernel (include/hqq_hip.h).  Any
-        other value, and "tile" without verify=True, is a ValueError."""
+        other value, and "tile" without verify=True, is a ValueError.
+        lora_bank (opt-in, with lora=True): a core.peft.LoRABank stacked for this model.  The four adapter stages then call ops.lora_shrink_routed /
+        ops.lora_expand_routed on the bank's tensors, and row b decodes under adapter self.slots[b] — int64 [batch] on the device at a static address, -1 (no
+        adapter, the base model; the initial value) or an index into the bank.  The caller writes it with slots.copy_(...) between steps; a captured step follows
+        it, as it follows bank.set(...).  The wrappers' own lora_A / lora_B / scaling are not read.  Row b's logits are the bits of the one-adapter step on the model
+        with adapter slots[b] in its wrappers.  A bank without lora=True, with verify=True, whose layers are not exactly the model's decoder wrappers, or that
+        ops.lora_routed_covers refuses for a group at `batch` rows, is a ValueError."""
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
         self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
@@ -595,10 +603,16 @@ class FusedLlamaStep:
         self.attn_fn = ALL_ATTENTION_FUNCTIONS.get_interface(cfg._attn_implementation, eager_attention_forward)
         self.attention, self.verify, self.verify_attention = attention, bool(verify), verify_attention
         self._rope_cache, self._rope_extra = _ROTARY[FAMILIES[variant.family].qk_norm, FAMILIES[variant.family].qkv_bias]
+        self.lora_bank = lora_bank
+        if lora_bank is not None and (not lora or verify):
+            raise ValueError("hqq_amd: lora_bank serves the lora=True variants of the decode step (and no verify step): " +
+                             ("verify=True takes no bank" if verify else "it needs lora=True"))
         self.kv_bits = self._check(cache, glue, kv_cache)   # (None: the dense cache)
         self._verify_attn = ops.attn_decode_tiled if verify_attention == "tile" else ops.attn_decode_shared
         linears = [lin + [None] * (7 - len(lin)) for lin in _decoder_linears(model, self.lora, self.moe)]   # (an MoE block: q k v o, and no gate up down)
         wrappers = _decoder_wrappers(model) if self.lora else [[None] * 7 for _ in linears]
+        if lora_bank is not None:
+            self._check_bank(linears, wrappers)
         self.folded, self.extra_weight_bytes = self._fold(glue, linears)
         self.blocks = [self._block(blk, lin, wrs, cache.layers[li]) for li, (blk, lin, wrs) in enumerate(zip(self.inner.layers, linears, wrappers))]
         self._buffers(glue)
@@ -641,6 +655,25 @@ class FusedLlamaStep:
         elif isinstance(cache, QuantizedStaticCache):
             raise ValueError("hqq_amd: a QuantizedStaticCache needs the kv_cache keyword ('q8' / 'q4')")
         return kv_bits
+
+    def _check_bank(self, linears, wrappers) -> None:
+        """the constructor's refusals of a LoRABank: its layers are exactly the model's decoder wrappers, its tensors are where and what the routed kernels read"""
+        bank = self.lora_bank
+        named = {getattr(w, "name", None): (L, w) for lin, wrs in zip(linears, wrappers) for L, w in zip(lin, wrs) if w is not None}
+        if None in named or sorted(named) != sorted(bank.names):
+            raise ValueError("hqq_amd: the LoRABank's layers are not exactly the HQQLinearLoRA wrappers of the model's decoder linears")
+        for name, (L, w) in named.items():
+            A, Bm, sc = bank.layer(name)
+            if tuple(A.shape) != (bank.n, L.in_features, w.r) or tuple(Bm.shape) != (bank.n, w.r, L.out_features) or A.dtype != Bm.dtype or \
+                    not (A.is_contiguous() and Bm.is_contiguous()) or any(t.device != L.W_q.device for t in (A, Bm, sc)):
+                raise ValueError(f"hqq_amd: the LoRABank's tensors for {name!r} are not the stacked [n, K, r] / [n, r, N] of that layer on its device")
+        for lin, wrs in zip(linears, wrappers):
+            for _, lo, hi in LORA_GROUPS:
+                ad = [(L, bank.layer(w.name)[0]) for L, w in zip(lin[lo:hi], wrs[lo:hi]) if w is not None]
+                if ad and (len({A.dtype for _, A in ad}) != 1 or
+                           not ops.lora_routed_covers(self.dt, ad[0][1].dtype, bank.n, self.B, [L.out_features for L, _ in ad], ad[0][0].in_features,
+                                                      [A.shape[2] for _, A in ad])):
+                    raise ValueError(f"hqq_amd: the routed adapter kernels do not cover this LoRABank at {self.B} rows (ops.lora_routed_covers)")
 
     def _fold(self, glue: str, linears):
         """whether the step runs the folded launches, and the bytes of the layer copies they keep: (folded, extra_weight_bytes)"""
@@ -740,6 +773,9 @@ class FusedLlamaStep:
             })
         if self.lora:   # per group: the adapted members as (index within the group, A, B, scaling) — the tensors themselves (static addresses under graph capture)
             for name, lo, hi in LORA_GROUPS:
+                if self.lora_bank is not None:   # (index, A [n, K, r], B [n, r, N], scaling fp32 [n]): the bank's tensors in the wrappers' place
+                    b["lora_" + name] = [(i,) + tuple(self.lora_bank.layer(w.name)) for i, w in enumerate(wrs[lo:hi]) if w is not None]
+                    continue
                 b["lora_" + name] = [(i, w.lora_A.data, w.lora_B.data, w._scaling_float()) for i, w in enumerate(wrs[lo:hi]) if w is not None]
         if self.qkv_bias:   # the three layers' own bias tensors (static addresses under graph capture); the launch records above stay bias-free
             b["qkv_bias"] = (q.bias, k.bias, v.bias)
@@ -762,8 +798,10 @@ class FusedLlamaStep:
         inner, cfg, B, dt, dev = self.inner, self.model.config, self.B, self.dt, self.device
         # ONE adapter workspace for the whole step, sized for its largest group (the groups run one after the other on one stream)
         groups = [ad for b in self.blocks for name, _, _ in LORA_GROUPS if (ad := b.get("lora_" + name))]
-        lora_ws_bytes = max((ops.lora_decode_workspace_bytes(B, ad[0][1].shape[0], [a[1].shape[1] for a in ad]) for ad in groups), default=0)
+        lora_ws_bytes = max((ops.lora_decode_workspace_bytes(B, ad[0][1].shape[-2], [a[1].shape[-1] for a in ad]) for ad in groups), default=0)
         self.lora_ws = torch.empty(lora_ws_bytes, dtype=torch.uint8, device=dev) if self.lora else None
+        # with a bank: the adapter of every row, read by the routed kernels on the device (-1: none)
+        self.slots = torch.full((B,), -1, dtype=torch.int64, device=dev) if self.lora_bank is not None else None
         self.h = torch.empty(B, self.H, dtype=dt, device=dev)       # the residual stream
         self.xn = torch.empty(B, self.H, dtype=dt, device=dev)      # its normalised copy, input of the next linears
         self.delta = torch.empty(B, self.H, dtype=dt, device=dev)   # output of o / down, added by the next add_rmsnorm
@@ -925,9 +963,14 @@ class FusedLlamaStep:
 
     def _adapters(self, b, which: str, x: Tensor, ys) -> None:
         """the adapter terms of group `which` of block b added to the base launch's outputs ys, on the rows x that launch read: one lora_shrink + one
-        lora_expand over the adapted members; nothing where the group has none (or the step serves no adapters)"""
+        lora_expand over the adapted members; nothing where the group has none (or the step serves no adapters).  With a bank: the routed pair on the bank's
+        tensors, every row under the adapter self.slots names for it"""
         ad = b.get("lora_" + which)
         if not ad:
+            return
+        if self.lora_bank is not None:
+            ops.lora_shrink_routed(x, [a[1] for a in ad], self.slots, self.lora_ws)
+            ops.lora_expand_routed(self.lora_ws, [a[2] for a in ad], [a[3] for a in ad], self.slots, [ys[a[0]] for a in ad], x.shape[-1])
             return
         ops.lora_shrink(x, [a[1] for a in ad], self.lora_ws)
         ops.lora_expand(self.lora_ws, [a[2] for a in ad], [a[3] for a in ad], [ys[a[0]] for a in ad], x.shape[-1])
@@ -944,6 +987,6 @@ class FusedLlamaBatchStep(FusedLlamaStep):
     wherever the tables exist)"""
 
     def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False,
-                 lora: bool = False, moe: bool = False, kv_cache: str | None = None):
+                 lora: bool = False, moe: bool = False, kv_cache: str | None = None, lora_bank=None):
         super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe,
-                         kv_cache=kv_cache)
+                         kv_cache=kv_cache, lora_bank=lora_bank)

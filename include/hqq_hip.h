@@ -558,6 +558,34 @@ int hqq_hip_lora_expand(int n_layers, const void* workspace, size_t workspace_by
                         const int64_t* N, const int64_t* r, int64_t M, int64_t K, int dtype, int lora_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same adapter term with ONE ADAPTER PER ROW, picked on the device from a bank of stacked adapters (csrc/lora_decode.hip): several adapters served
+ * over one quantised base in one pass, and an adapter changed between calls without touching a captured graph.
+ *     A_bank[l]        [n_adapters, K, r_l]       dense, `lora_dtype`                    B_bank[l]   [n_adapters, r_l, N_l]   dense, `lora_dtype`
+ *     scaling_dev[l]   fp32 [n_adapters]          in DEVICE memory                       slot_dev    int64 [M]                in DEVICE memory
+ * The host arrays of pointers (A_bank, B_bank, scaling_dev, y, N, r) are read during the call and not kept; slot_dev and scaling_dev[l] are read by the
+ * kernels only — no host read, so the pair can be captured in a graph and replayed after the slots, a scaling or an adapter's elements were rewritten
+ * in place.
+ *   1. Row m with slot_dev[m] = a in [0, n_adapters): y_l[m, :] gets the bits hqq_hip_lora_shrink + hqq_hip_lora_expand give that row alone with
+ *      A_bank[l][a], B_bank[l][a] and the float scaling_dev[l][a] — the slice size, the order inside a slice, the slice order, ascending j, one fused
+ *      multiply-add per term and the two final roundings are theirs, functions of (K, r_l) alone.  Every row keeps its own chain: no term of another row's
+ *      adapter enters it, not even a zero one.
+ *   2. Row m with any other slot value (-1 is the documented "no adapter"; also >= n_adapters, other negatives): y_l[m, :] is not written and no
+ *      adapter byte is read for the row; its partials in the workspace are neither written nor read.
+ *   3. An adapter that no row selects is not read (it may hold anything, NaN included); one that several rows select is read once per workgroup.
+ *   4. No atomics, no arrival counters: the same bits call after call, whatever the workspace held.
+ * Covered: what hqq_hip_lora_shrink / hqq_hip_lora_expand cover, and 1 <= n_adapters <= 256; hqq_hip_lora_routed_covers answers 1 / 0.  The workspace
+ * is theirs: hqq_hip_lora_decode_workspace_bytes(n_layers, r, M, K) bytes, layout [layer][slice][M][r_l].  x and the workspace 16-byte aligned, slot_dev
+ * 8-byte aligned, everything else to its element size.  Nothing outside the selected rows of y_l and their part of the workspace is written.
+ * The three symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_lora_routed_covers(int n_layers, const int64_t* N, const int64_t* r, int64_t n_adapters, int64_t M, int64_t K, int dtype, int lora_dtype);
+int hqq_hip_lora_shrink_routed(int n_layers, const void* x, const void* const* A_bank, const int64_t* r, int64_t n_adapters, const int64_t* slot_dev,
+                               int64_t M, int64_t K, int dtype, int lora_dtype, void* workspace, size_t workspace_bytes, void* stream);
+int hqq_hip_lora_expand_routed(int n_layers, const void* workspace, size_t workspace_bytes, const void* const* B_bank, const float* const* scaling_dev,
+                               void* const* y, const int64_t* N, const int64_t* r, int64_t n_adapters, const int64_t* slot_dev, int64_t M, int64_t K,
+                               int dtype, int lora_dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The routed expert MLP of a mixture-of-experts block at decode sizes (csrc/moe.hip) — what transformers' fused experts modules compute
  * (MixtralExperts.forward and its copies: gate_up_proj [E, 2I, H], down_proj [E, H, I], SiLU) over experts quantised along axis 1, in two launches
  * without a host read of the routing.  With T the compute dtype (`dtype`), rnd = round to T, e = idx[t, s]:
