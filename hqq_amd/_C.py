@@ -113,6 +113,11 @@ SYMBOLS = {
     "hqq_hip_spec_accept": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # the verify step's other attention: one workgroup per (head, split) reads each key once for all rows (csrc/attn_tile.hip; added at ABI 9 without a bump)
     "hqq_hip_attn_decode_tiled": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
+    # decode attention with one workgroup per KV-head group: each key read (and rebuilt) once for the group's query heads (csrc/attn_gqa.hip; added at ABI 9
+    # without a bump: nothing that existed changed)
+    "hqq_hip_attn_decode_gqa_batched": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
+    "hqq_hip_attn_decode_gqa_kvq_batched": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp,
+                                                   _sz, _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

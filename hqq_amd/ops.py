@@ -1752,6 +1752,74 @@ def attn_decode_kvq(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: float, h
     return attn_decode_kvq_batched(q, tuple(t.view(1, *t.shape[-3:]) for t in bufs), _seq1(pos), out, scaling, head_dim, splits=splits, workspace=workspace)
 
 
+# ---- decode attention with one workgroup per KV-head GROUP (csrc/attn_gqa.hip): the arguments of attn_decode_batched / attn_decode_kvq_batched through the kernel
+#      that makes the G = n_heads / n_kv_heads query heads of a group one MFMA query tile, so each key is read — and a packed key rebuilt — once per group.
+#      Its contract is attn_decode_tiled's (deterministic, a head independent of the other heads' queries, within tests/_tile_cases.py's band of float64
+#      attention), NOT attn_decode_batched's bits ---------------------------------------------------------------------------------------------------------------
+ATTN_MAX_SPLITS = 64   # csrc/attn_decode_core.h
+ATTN_GQA_MAX_G = 16    # the rows of the query tile
+ATTN_GQA_SPLITS_CAP = 32   # attn_gqa_splits never asks for more (measured: profiles/gqa_attn_summary.md)
+
+
+def attn_gqa_covers(n_heads: int, n_kv_heads: int) -> bool:
+    """whether the grouped kernels have something to share and a tile to hold it: 2 <= n_heads / n_kv_heads <= 16 (pure host arithmetic)"""
+    n_heads, n_kv_heads = int(n_heads), int(n_kv_heads)
+    return n_kv_heads >= 1 and n_heads >= 1 and n_heads % n_kv_heads == 0 and 2 <= n_heads // n_kv_heads <= ATTN_GQA_MAX_G
+
+
+def attn_gqa_splits(kv_len: int, batch: int, n_kv_heads: int) -> int:
+    """how many workgroups share a KV group's keys in the grouped kernels when up to kv_len of them are visible.  The grouped grid has G times fewer workgroups
+    than the per-head one, so attn_splits is not its rule: the smallest S with batch * n_kv_heads * S >= 256 (a workgroup per CU), capped by kv_len // 256 (every
+    wave of a share gets a block of 32 keys), by ATTN_GQA_SPLITS_CAP = 32 and by ATTN_MAX_SPLITS, never below 1.  The cap of 32 is the sweep's correction: at 64
+    shares the per-share fixed cost and the merging launch cost more than the idle CUs they fill (28 / 4 heads, B = 1, 16384 positions: 41.9 us dense at 64 shares
+    against 29.4 at 32).  With it the rule's time is within 11 % of the best split count measured at every point of profiles/gqa_attn_summary.md, which holds the
+    table.  A function of (kv_len, batch, n_kv_heads) alone, so a captured graph keeps its launch shape per bucket as with attn_splits."""
+    groups = max(1, int(batch) * int(n_kv_heads))
+    want = -(-256 // groups)
+    return max(1, min(want, int(kv_len) // 256, ATTN_GQA_SPLITS_CAP, ATTN_MAX_SPLITS))
+
+
+def attn_decode_gqa_batched(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_batched's arguments through the grouped kernel (hqq_hip_attn_decode_gqa_batched): grid (n_kv, splits, B), the query heads of a KV group as one
+    MFMA tile.  n_heads / n_kv_heads up to 16.  Splits and workspace as attn_decode_batched (attn_gqa_splits / attn_workspace_batched)."""
+    _dev(q, k_cache, v_cache, pos, out)
+    B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "attn_decode_gqa_batched")
+    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_attn_decode_gqa_batched(_p(q), _p(k_cache), _p(v_cache), _p(pos), B, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
+                                                      int(splits), ws_ptr, ws_bytes, _stream())
+    _C.check(rc, "hqq_hip_attn_decode_gqa_batched")
+    return out
+
+
+def attn_decode_gqa(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_gqa_batched for one sequence: q [n_heads, hd], k_cache / v_cache [n_kv, cache_len, hd], pos int64[1], out [n_heads * hd]"""
+    return attn_decode_gqa_batched(q, _cache1(k_cache), _cache1(v_cache), _seq1(pos), out, scaling, splits=splits, workspace=workspace)
+
+
+def attn_decode_gqa_kvq_batched(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: float, head_dim: int, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_kvq_batched's arguments through the grouped kernel (hqq_hip_attn_decode_gqa_kvq_batched): a packed row is rebuilt once per KV group; the output
+    has the bits of attn_decode_gqa_batched on kv_dequantize's tensors with the same splits.  Nothing at or beyond pos[b] + 1 is read."""
+    _dev(q, pos, out)
+    B = _batch_of(pos, "attn_decode_gqa_kvq_batched")
+    hd = int(head_dim)
+    Bc, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, hd, "attn_decode_gqa_kvq_batched")
+    if Bc != B or q.numel() % (B * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or q.dtype != dt or out.dtype != dt:
+        raise ValueError("hqq_amd: attn_decode_gqa_kvq_batched takes dense q / out [B, n_heads * head_dim] of the buffers' dtype, B the positions' count and the buffers' batch")
+    n_heads = q.numel() // (B * hd)
+    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_attn_decode_gqa_kvq_batched(nbits, _p(q), *(_p(t) for t in bufs), _p(pos), B, _p(out), n_heads, n_kv, hd, gs, L, float(scaling), _dt(dt),
+                                                          int(splits), ws_ptr, ws_bytes, _stream())
+    _C.check(rc, "hqq_hip_attn_decode_gqa_kvq_batched")
+    return out
+
+
+def attn_decode_gqa_kvq(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: float, head_dim: int, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
+    """attn_decode_gqa_kvq_batched for one sequence: buffers [n_kv, cache_len, ...] (or [1, n_kv, cache_len, ...]), pos int64[1]"""
+    return attn_decode_gqa_kvq_batched(q, tuple(t.view(1, *t.shape[-3:]) for t in bufs), _seq1(pos), out, scaling, head_dim, splits=splits, workspace=workspace)
+
+
 def argmax_advance_batched(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, pos: Tensor | None = None) -> None:
     """The back of a greedy decode step for B sequences in one launch, one workgroup per row (hqq_hip_argmax_advance_batched): next_tok[b] = logits[b].argmax() (the first
     index of the largest value; torch.argmax's tie and NaN rule), tok[b] = the same, pos[b] += 1 (each skipped when None).  logits [B, vocab] dense; int64 tensors of

@@ -54,6 +54,12 @@ def eos_lengths(rows, eos_token_id, n: int) -> list:
     return out
 
 
+def check_gqa_attention(gqa_attention) -> None:
+    """the decoders' gqa_attention keyword: "heads" or "group" (ValueError otherwise)"""
+    if isinstance(gqa_attention, bool) or gqa_attention not in ("heads", "group"):
+        raise ValueError("gqa_attention: 'heads' or 'group'")
+
+
 def check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attention="rows") -> None:
     """the speculative-decoding keywords of GraphedGreedyDecoder and HFGenerator: speculate None or "ngram", draft_rows an integer in 2 .. ops.SPEC_MAX_ROWS,
     ngram_max an integer in 0 .. ops.SPEC_MAX_NGRAM, no sampling with speculation (acceptance is the greedy rule), verify_attention "rows" or "tile" and "tile"
@@ -149,18 +155,26 @@ class GraphedGreedyDecoder:
     everything else decodes as before.  `spec_stats` holds the last call's {"steps", "tokens"}; generate_batch is untouched.
     verify_attention: the verify step's attention kernel.  "rows" (default) — ops.attn_decode_shared, the code path as before.  "tile" (opt-in, with speculate) —
     ops.attn_decode_tiled, which reads each key once for all rows and holds its own contract (a derived band of float64 attention, not the one-row kernel's
-    bits).  Where speculation is not served the keyword has no effect; assigning `decoder.verify_attention` rebuilds the kept state at the next generate()."""
+    bits).  Where speculation is not served the keyword has no effect; assigning `decoder.verify_attention` rebuilds the kept state at the next generate().
+    gqa_attention: the decode-attention kernel's grid with attention="hip".  "heads" (default) — one workgroup per query head, the code path as before.  "group"
+    (opt-in) — one workgroup per KV-head group (ops.attn_decode_gqa_batched / ops.attn_decode_gqa_kvq_batched: each key read, and a packed key rebuilt, once for
+    the query heads that share it; the tile kernel's contract, not the one-row kernel's bits).  It is passed to the plain and the batched fused steps where
+    llama_fused.supports_gqa_attention(model) holds and attention == "hip" (`gqa_grouped` says whether); otherwise, and for the speculative verify step always,
+    the keyword has no effect.  Assigning `decoder.gqa_attention` rebuilds the kept state at the next generate()."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
                  qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
-                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, verify_attention: str = "rows", lora_bank=None):
+                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, verify_attention: str = "rows", lora_bank=None,
+                 gqa_attention: str = "heads"):
         from transformers import StaticCache
         from . import llama_fused
         from .kv_cache import check_kv_group_size, kv_cache_bits
         opted = opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
         check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attention)
         self._verify_attention = verify_attention
+        check_gqa_attention(gqa_attention)
+        self._gqa_attention = gqa_attention
         self.kv_bits = kv_cache_bits(kv_cache)   # (None: the dense StaticCache)
         check_kv_group_size(kv_cache, kv_group_size)
         self.kv_cache, self.kv_group_size = kv_cache, kv_group_size
@@ -202,6 +216,21 @@ class GraphedGreedyDecoder:
         check_speculation(self.speculate, self.draft_rows, self.ngram_max, self.do_sample, value)
         self._verify_attention = value   # (part of _fingerprint: the kept verify step and its graphs are rebuilt at the next generate())
 
+    @property
+    def gqa_attention(self) -> str:
+        """the decode-attention kernel's grid: "heads" or "group" ("group" has an effect only where `gqa_grouped` is True)"""
+        return self._gqa_attention
+
+    @gqa_attention.setter
+    def gqa_attention(self, value) -> None:
+        check_gqa_attention(value)
+        self._gqa_attention = value   # (part of _fingerprint: the kept steps and their graphs are rebuilt at the next generate())
+
+    @property
+    def gqa_grouped(self) -> bool:
+        """whether the plain and the batched fused steps are built with gqa_attention="group": asked for, the kernel attention, and a model with KV groups to serve"""
+        return bool(self._gqa_attention == "group" and self.attention == "hip" and self.variant is not None and self._fused_mod.supports_gqa_attention(self.model))
+
     # `variant` as flags (what bench.py, the tools and the tests read): `fused` is plain Llama's, the others are the opt-in variants, one true at most
     fused = property(lambda self: self.variant is not None and not any(self.variant.flags().values()))
     fused_axis0 = property(lambda self: self.variant is not None and self.variant.axis0 and not self.variant.lora)   # (an adapted axis-0 model is fused_lora's)
@@ -222,6 +251,8 @@ class GraphedGreedyDecoder:
         kw = {} if self.kv_bits is None else {"kv_cache": self.kv_cache}
         if self.lora_bank is not None and self.fused_lora:   # (the other variants serve no adapters: with them the bank works through activate alone)
             kw["lora_bank"] = self.lora_bank
+        if self.gqa_grouped:   # (absent otherwise: the steps' call is the one it was)
+            kw["gqa_attention"] = "group"
         return kw
 
     @property
@@ -295,7 +326,8 @@ class GraphedGreedyDecoder:
         bound to (set_backend rebinds it class-wide).  A re-quantised / re-loaded / re-patched model gives another tuple (round-5 advisor: the kept step and
         graphs silently decoded with stale copies).  In-place edits through .data bypass the version counters: call reset() after those."""
         from ..core.quantize import HQQLinear
-        fp = [getattr(HQQLinear, "backend", None), self._verify_attention]   # (the verify step's attention kernel is baked into the kept step and its graphs)
+        # (the verify step's attention kernel and the decode attention's grid are baked into the kept steps and their graphs)
+        fp = [getattr(HQQLinear, "backend", None), self._verify_attention, self._gqa_attention]
         bank = self.lora_bank
         if bank is not None:   # the bank's tensors in the place of the wrappers' adapter tensors below (activate rewrites those; set / activate keep the bank's)
             fp.append(bank.pointers())
@@ -682,14 +714,15 @@ class HFGenerator:
     Differences a caller can see: EOS is looked for every 16 tokens on the host instead of after every token (no per-token synchronisation; the text returned is cut at
     the EOS all the same); "output_tokens" holds every generated token before the EOS (the reference's slice drops the last one it generated, generation_hf.py:493);
     a prompt that leaves less than max_new_tokens of cache generates what fits.
-    speculate / draft_rows / ngram_max / verify_attention and attention are GraphedGreedyDecoder's keywords (defaults: no speculation, HF's attention function); speculation is served
+    speculate / draft_rows / ngram_max / verify_attention / gqa_attention and attention are GraphedGreedyDecoder's keywords (defaults: no speculation, HF's attention function); speculation is served
     with attention="hip" only, and everything else decodes as before (`decoder.speculating` says which).
     lora_bank, and the adapter / adapters keywords of generate / generate_batch, are GraphedGreedyDecoder's: passed through."""
 
     def __init__(self, model, tokenizer, max_new_tokens: int = 1000, cache_size: int | None = None, do_sample: bool = False, temperature: float = 0.6, top_k: int = 5,
                  compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
                  qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
-                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, attention: str = "sdpa", verify_attention: str = "rows", lora_bank=None):
+                 speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, attention: str = "sdpa", verify_attention: str = "rows", lora_bank=None,
+                 gqa_attention: str = "heads"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
@@ -697,6 +730,7 @@ class HFGenerator:
         kv_cache_bits(kv_cache)
         check_kv_group_size(kv_cache, kv_group_size)
         check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attention)
+        check_gqa_attention(gqa_attention)
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -710,7 +744,8 @@ class HFGenerator:
         self.compile_options = compile_options
         self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
                                             qkv_bias=qkv_bias, lora=lora, moe=moe, kv_cache=kv_cache, kv_group_size=kv_group_size, speculate=speculate,
-                                            draft_rows=draft_rows, ngram_max=ngram_max, attention=attention, verify_attention=verify_attention, lora_bank=lora_bank)
+                                            draft_rows=draft_rows, ngram_max=ngram_max, attention=attention, verify_attention=verify_attention, lora_bank=lora_bank,
+                                            gqa_attention=gqa_attention)
         self.init()
 
     @staticmethod

@@ -52,6 +52,11 @@ FusedLlamaStep(batch=R, verify=True) (opt-in; speculative decoding, GraphedGreed
 positions of ONE sequence on a batch-1 cache: ops.rope_cache_shared and ops.attn_decode_shared take the place of the rotary-and-cache launch and the attention.
 verify_attention="tile" (opt-in) puts ops.attn_decode_tiled — each key read once for all rows, a contract of its own — in ops.attn_decode_shared's place.
 Plain llama with attention="hip" on the dense cache only (supports_speculation); every other combination is refused.
+
+FusedLlamaStep(attention="hip", gqa_attention="group") (opt-in) attends with one workgroup per KV-HEAD GROUP (csrc/attn_gqa.hip): the family's rotary-and-cache
+launch, then ops.attn_decode_gqa_batched (dense cache), or ops.rope_kvq_cache_batched, then ops.attn_decode_gqa_kvq_batched (quantised cache).  Every variant
+and batch that attention="hip" serves, on models with 2 .. 16 query heads per KV head (supports_gqa_attention); not the verify step.  The same launches per block
+as "heads", except in the Llama family on the dense cache: one more (9 kernels / 6 folded against 8 / 5), because "heads" attends inside its rotary launch there.
 """
 from __future__ import annotations
 
@@ -502,6 +507,15 @@ def supports_speculation(model, rows: int) -> bool:
     return head_dim(model.config) in (64, 128, 256)
 
 
+def supports_gqa_attention(model) -> bool:
+    """whether FusedLlamaStep(..., attention="hip", gqa_attention="group") has a KV group to serve on this model: 2 .. 16 query heads per KV head
+    (ops.attn_gqa_covers) of a head_dim the decode-attention kernels cover"""
+    cfg = model.config
+    n_heads = cfg.num_attention_heads
+    n_kv = getattr(cfg, "num_key_value_heads", None) or n_heads
+    return ops.attn_gqa_covers(n_heads, n_kv) and head_dim(cfg) in (64, 128, 256)
+
+
 def _rec(L):
     """a layer as ops.gemv_block and the re-layout functions take it"""
     return (L.W_q, L.scale, L.zero, L.out_features)
@@ -546,7 +560,7 @@ class FusedLlamaStep:
 
     def __init__(self, model, cache, max_cache_len: int, attention: str = "sdpa", glue: str = "auto", axis0: bool = False, batch: int = 1,
                  qk_norm: bool = False, qkv_bias: bool = False, lora: bool = False, moe: bool = False, kv_cache: str | None = None, verify: bool = False,
-                 verify_attention: str = "rows", lora_bank=None):
+                 verify_attention: str = "rows", lora_bank=None, gqa_attention: str = "heads"):
         """attention: "sdpa" — HF's own attention function on the cache tensors (the step then emits the tokens `model(...)` would);
         "hip" — csrc/block.hip's decode-attention kernel (one query per head, fp32 softmax): within rounding of SDPA, not bit-identical,
         3-4 us instead of 12-15 per block.
@@ -586,7 +600,16 @@ class FusedLlamaStep:
         adapter, the base model; the initial value) or an index into the bank.  The caller writes it with slots.copy_(...) between steps; a captured step follows
         it, as it follows bank.set(...).  The wrappers' own lora_A / lora_B / scaling are not read.  Row b's logits are the bits of the one-adapter step on the model
         with adapter slots[b] in its wrappers.  A bank without lora=True, with verify=True, whose layers are not exactly the model's decoder wrappers, or that
-        ops.lora_routed_covers refuses for a group at `batch` rows, is a ValueError."""
+        ops.lora_routed_covers refuses for a group at `batch` rows, is a ValueError.
+        gqa_attention (with attention="hip"): "heads" (default) — one workgroup per QUERY head (csrc/block.hip, csrc/kv_cache.hip), the code path as it was.  "group"
+        (opt-in) — one workgroup per KV-HEAD GROUP (csrc/attn_gqa.hip): the family's rotary-and-cache launch, then ops.attn_decode_gqa_batched on the rotated qr
+        (dense cache), or ops.rope_kvq_cache_batched, then ops.attn_decode_gqa_kvq_batched (quantised cache); each key is read, and a packed key rebuilt, once for
+        the n_heads / n_kv_heads query heads that share it.  Its contract is the tile kernel's: deterministic, within a derived band of float64 attention, NOT
+        bit-identical to "heads".  Launches per block against "heads": the same for the Qwen families, Mixtral and every quantised-cache step; ONE MORE for the
+        Llama family on the dense cache, where "heads" rotates, caches and attends in the one rope_attn_decode_batched launch (with the separate glue kernels 9
+        against 8, folded 6 against 5; a split launch adds its merging launch to either).  The split count comes from ops.attn_gqa_splits.  Served for every variant and batch that attention="hip" serves; refused
+        (ValueError) with attention="sdpa", with verify=True (the verify step keeps verify_attention) and where ops.attn_gqa_covers is false (n_heads / n_kv_heads
+        outside 2 .. 16).  Any other value is a ValueError."""
         from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
         from transformers.models.llama.modeling_llama import eager_attention_forward
         self.variant = variant = StepVariant.from_flags(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)
@@ -602,6 +625,7 @@ class FusedLlamaStep:
         self.H, self.L = cfg.hidden_size, max_cache_len
         self.attn_fn = ALL_ATTENTION_FUNCTIONS.get_interface(cfg._attn_implementation, eager_attention_forward)
         self.attention, self.verify, self.verify_attention = attention, bool(verify), verify_attention
+        self.gqa_attention = gqa_attention
         self._rope_cache, self._rope_extra = _ROTARY[FAMILIES[variant.family].qk_norm, FAMILIES[variant.family].qkv_bias]
         self.lora_bank = lora_bank
         if lora_bank is not None and (not lora or verify):
@@ -631,6 +655,16 @@ class FusedLlamaStep:
             raise ValueError("verify_attention: 'rows' or 'tile'")
         if self.verify_attention == "tile" and not self.verify:
             raise ValueError("hqq_amd: verify_attention='tile' is the verify step's attention: it needs verify=True")
+        if self.gqa_attention not in ("heads", "group"):
+            raise ValueError("gqa_attention: 'heads' or 'group'")
+        if self.gqa_attention == "group":
+            if attention != "hip":
+                raise ValueError("hqq_amd: gqa_attention='group' is a kernel attention: it needs attention='hip'")
+            if self.verify:
+                raise ValueError("hqq_amd: gqa_attention='group' serves the decode step; the verify step keeps verify_attention ('rows' / 'tile')")
+            if not ops.attn_gqa_covers(self.n_heads, self.n_kv):
+                raise ValueError(f"hqq_amd: gqa_attention='group' needs 2 .. {ops.ATTN_GQA_MAX_G} query heads per KV head (ops.attn_gqa_covers): this model has "
+                                 f"{self.n_heads} / {self.n_kv}")
         if self.verify and (variant != StepVariant() or attention != "hip" or kv_cache is not None or not supports_speculation(model, B)):
             raise ValueError(f"hqq_amd: verify=True serves the plain Llama / Mistral step with attention='hip' on a dense cache, for 2 .. {ops.SPEC_MAX_ROWS} rows of a "
                              "model llama_fused.supports_speculation accepts")
@@ -704,8 +738,10 @@ class FusedLlamaStep:
                             q / k (which exist because of this rule: "qkv_rope"), writing the rotated q into qr and k / v into the caches                 _qkv_folded_rope
                          2  folded otherwise: gemv_block with BLOCK_NORM into q, k, v                                                                     _qkv_folded
                          3  else: add_rmsnorm(h, delta, n1), the grouped q|k|v launch (axis 0 or 1), the qkv adapters                                    _qkv_kernels
-          rotary, cache  1  a quantised cache: rope_kvq_cache_batched, attn_decode_kvq_batched                                                            _attend_kvq
-          and attention  2  the verify step: rope_cache_shared, then _verify_attn (attn_decode_shared or attn_decode_tiled)                               _attend_verify
+          rotary, cache  0  gqa_attention="group" (the kernel attention only; no verify step) — a quantised cache: rope_kvq_cache_batched,
+          and attention     attn_decode_gqa_kvq_batched; the dense cache: the family's rotary-and-cache launch (_ROTARY), attn_decode_gqa_batched     _attend_kvq_gqa / _attend_rotary_gqa
+                         1  a quantised cache: rope_kvq_cache_batched, attn_decode_kvq_batched                                                            _attend_kvq
+                         2  the verify step: rope_cache_shared, then _verify_attn (attn_decode_shared or attn_decode_tiled)                               _attend_verify
                          3  the kernel attention in the llama family (its axis-0 and lora variants too): rope_attn_decode_batched, one launch             _attend_rope_attn
                          4  else the family's rotary-and-cache launch (_ROTARY) — unless q|k|v rule 1 has rotated and cached already —, then
                             attn_decode_batched ("hip") or self.attn_fn on the first kv_len positions ("sdpa")                     _attend_rotary_hip / _attend_rotary_sdpa / _attend_sdpa
@@ -718,7 +754,9 @@ class FusedLlamaStep:
         The grouped and single-layer launches themselves are the axis-0 or the axis-1 pair."""
         S, hip, llama = FusedLlamaStep, self.attention == "hip", self.variant.family == "llama"
         qkv = S._qkv_kernels if not self.folded else S._qkv_folded_rope if not hip and llama and self.hd % 2 == 0 else S._qkv_folded
-        if self.kv_bits is not None:
+        if self.gqa_attention == "group":   # (_check: attention="hip", no verify step)
+            attend = S._attend_kvq_gqa if self.kv_bits is not None else S._attend_rotary_gqa
+        elif self.kv_bits is not None:
             attend = S._attend_kvq
         elif self.verify:
             attend = S._attend_verify
@@ -863,7 +901,8 @@ class FusedLlamaStep:
             if self._mask_rows is not None:
                 torch.where(self.ar.view(1, -1) <= pos.view(-1, 1), self.zero, self.ninf, out=self._mask_rows)   # the causal mask of one query per row at its `pos`
         kvl = self.L if kv_len is None else min(int(kv_len), self.L)
-        splits = ops.attn_splits(kvl) if self._mask_rows is None else 1   # (kernel attention: kv_len only picks how many workgroups share a head)
+        # (kernel attention: kv_len only picks how many workgroups share a head — or, grouped, a KV group — 's keys)
+        splits = 1 if self._mask_rows is not None else ops.attn_gqa_splits(kvl, B, self.n_kv) if self.gqa_attention == "group" else ops.attn_splits(kvl)
         if splits > 1 and splits not in self.attn_ws:
             self.attn_ws[splits] = ops.attn_workspace_batched(self.device, B, self.n_heads, self.hd, splits)
         return SimpleNamespace(cos=cos, sin=sin, pos=pos, kvl=kvl, mask=self.mask[..., :kvl], splits=splits, delta=None)
@@ -886,6 +925,10 @@ class FusedLlamaStep:
         ops.rope_kvq_cache_batched(b["q"], b["k"], b["v"], c.cos, c.sin, c.pos, b["kvq"], b["qr"])
         return ops.attn_decode_kvq_batched(b["qr"], b["kvq"], c.pos, self.att, b["attn"].scaling, self.hd, splits=c.splits, workspace=self.attn_ws.get(c.splits))
 
+    def _attend_kvq_gqa(self, b, c) -> Tensor:   # the same two launches, the attention per KV-head group
+        ops.rope_kvq_cache_batched(b["q"], b["k"], b["v"], c.cos, c.sin, c.pos, b["kvq"], b["qr"])
+        return ops.attn_decode_gqa_kvq_batched(b["qr"], b["kvq"], c.pos, self.att, b["attn"].scaling, self.hd, splits=c.splits, workspace=self.attn_ws.get(c.splits))
+
     def _attend_verify(self, b, c) -> Tensor:   # the rows are positions of one sequence: all of their keys / values into its cache first, then row i over keys [0, pos[i]]
         ops.rope_cache_shared(b["q"], b["k"], b["v"], c.cos, c.sin, c.pos, b["kc"], b["vc"], b["qr"])
         return self._verify_attn(b["qr"], b["kc"], b["vc"], c.pos, self.att, b["attn"].scaling, splits=c.splits, workspace=self.attn_ws.get(c.splits))
@@ -900,6 +943,10 @@ class FusedLlamaStep:
     def _attend_rotary_hip(self, b, c) -> Tensor:
         self._rotary(b, c)
         return ops.attn_decode_batched(b["qr"], b["kc"], b["vc"], c.pos, self.att, b["attn"].scaling, splits=c.splits, workspace=self.attn_ws.get(c.splits))
+
+    def _attend_rotary_gqa(self, b, c) -> Tensor:   # every family, the llama family too: the grouped kernel has no rotary-fused form
+        self._rotary(b, c)
+        return ops.attn_decode_gqa_batched(b["qr"], b["kc"], b["vc"], c.pos, self.att, b["attn"].scaling, splits=c.splits, workspace=self.attn_ws.get(c.splits))
 
     def _attend_rotary_sdpa(self, b, c) -> Tensor:
         self._rotary(b, c)
@@ -987,6 +1034,6 @@ class FusedLlamaBatchStep(FusedLlamaStep):
     wherever the tables exist)"""
 
     def __init__(self, model, cache, max_cache_len: int, batch: int, attention: str = "sdpa", axis0: bool = False, qk_norm: bool = False, qkv_bias: bool = False,
-                 lora: bool = False, moe: bool = False, kv_cache: str | None = None, lora_bank=None):
+                 lora: bool = False, moe: bool = False, kv_cache: str | None = None, lora_bank=None, gqa_attention: str = "heads"):
         super().__init__(model, cache, max_cache_len, attention=attention, axis0=axis0, batch=batch, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe,
-                         kv_cache=kv_cache, lora_bank=lora_bank)
+                         kv_cache=kv_cache, lora_bank=lora_bank, gqa_attention=gqa_attention)

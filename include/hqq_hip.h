@@ -684,6 +684,33 @@ int hqq_hip_attn_decode_kvq_batched(int nbits, const void* q, const void* kq, co
                                     int64_t group_size, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * hqq_hip_attn_decode_gqa_batched / hqq_hip_attn_decode_gqa_kvq_batched (csrc/attn_gqa.hip): the arguments, layouts, limits and workspace of
+ * hqq_hip_attn_decode_batched / hqq_hip_attn_decode_kvq_batched — `batch` sequences, q / out [batch, n_heads * hd], dense caches [batch, n_kv_heads, cache_len, hd]
+ * or the six buffers of the quantised cache, pos_dev int64[batch]; sequence b attends over keys [0, pos_dev[b]], a position outside [0, cache_len) as if at
+ * cache_len - 1; fp16 / bf16, hd 64 / 128 / 256, cache_len <= 30000, splits <= 64 with hqq_hip_attn_decode_workspace_bytes(batch * n_heads, hd, splits) bytes —
+ * with ANOTHER kernel and ANOTHER contract (opt-in: FusedLlamaStep(gqa_attention = "group")).  The grid is (n_kv_heads, splits, batch): one workgroup serves the
+ * G = n_heads / n_kv_heads query heads of a KV group as the rows of one 16-row MFMA query tile (hqq_hip_attn_decode_tiled's tile with the heads of a group in
+ * the place of the rows of a verify step; csrc/attn_tile_core.h is the one text both run), so every key and value row is read from memory — and on the quantised
+ * cache rebuilt — ONCE per group instead of once per query head.  Share sp of a split call covers keys [sp chunk, min((sp + 1) chunk, n)), n = pos + 1,
+ * chunk = ceil(n / splits); its records have the one-row kernels' layout and are merged by their merging launch.
+ * Added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * CONTRACT.  hqq_hip_attn_decode_tiled's: deterministic (no atomics, fixed orders); a head's output depends on its own query, its sequence's position and cache
+ *   and `splits`, on NO other head's or sequence's query; within tests/_tile_cases.py's band of float64 attention, NOT bit-identical to hqq_hip_attn_decode_batched.
+ *   On one sequence it IS bit-identical to hqq_hip_attn_decode_tiled on the transposed problem (rows = G, n_heads = n_kv_heads, every position equal, the same
+ *   splits), and the quantised entry to the dense one on hqq_hip_kv_dequantize's tensors.  Nothing at or beyond pos_dev[b] + 1 of a sequence's cache is read,
+ *   in levels or in meta.  The 16 - G padding rows of a tile read no query memory and write nothing.  No allocation.
+ *   G > 16: HQQ_ERR_UNSUPPORTED (the message names G), then the quantised cache's coverage rule (hqq_hip_kv_covers: HQQ_ERR_UNSUPPORTED), then the checks of
+ *   hqq_hip_attn_decode_batched with their codes; nothing is launched after an error.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_attn_decode_gqa_batched(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos_dev, int64_t batch, void* out, int64_t n_heads,
+                                    int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int hqq_hip_attn_decode_gqa_kvq_batched(int nbits, const void* q, const void* kq, const void* k_scale, const void* k_zero, const void* vq, const void* v_scale,
+                                        const void* v_zero, const int64_t* pos_dev, int64_t batch, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
+                                        int64_t group_size, int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace, size_t workspace_bytes,
+                                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
