@@ -118,6 +118,10 @@ SYMBOLS = {
     "hqq_hip_attn_decode_gqa_batched": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp, _sz, _vp]),
     "hqq_hip_attn_decode_gqa_kvq_batched": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _i64, _vp,
                                                    _sz, _vp]),
+    # a prompt's causal attention on the static cache, 16 positions of a query head per workgroup (csrc/attn_prefill.hip; added at ABI 9 without a bump: nothing
+    # that existed changed)
+    "hqq_hip_attn_prefill": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _vp]),
+    "hqq_hip_attn_prefill_kvq": (_i32, [_i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _i32, _vp]),
     "hqq_hip_quantize_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "hqq_hip_quantize": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

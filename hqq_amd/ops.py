@@ -1820,6 +1820,75 @@ def attn_decode_gqa_kvq(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: floa
     return attn_decode_gqa_kvq_batched(q, tuple(t.view(1, *t.shape[-3:]) for t in bufs), _seq1(pos), out, scaling, head_dim, splits=splits, workspace=workspace)
 
 
+# ---- a prompt's causal attention on the static cache (csrc/attn_prefill.hip): the T rows of ONE sequence at positions pos0 .. pos0 + T - 1, row t over keys
+#      [0, pos0 + t] of a cache that already holds the rows' own keys and values.  Grid (n_heads, ceil(T / 16)): 16 consecutive positions of a query head are one
+#      MFMA query tile of attn_decode_tiled's body, one share, no workspace.  The contract, pinned by tests/test_prefill_attn_gpu.py:
+#        (a) rows 16 j .. of head h have the bits of attn_decode_tiled on those queries with pos = pos0 + 16 j + i and splits = 1
+#        (b) every row lies within tests/_tile_cases.py's band of float64 attention
+#        (c) attn_prefill_kvq has the bits of attn_prefill on kv_dequantize's tensors
+#        (d) nothing at or beyond pos0 + T is read, in levels, meta or dense rows: it may hold NaN
+#        (e) row i depends on no query of a row > i and on no FINITE key / value at a position > pos0 + i (a masked V row inside the tile's range is still
+#            multiplied, by an exact 0)
+#        (f) the same bits call to call, and whatever q's strides
+#        (g) NOT the bits of SDPA: the probabilities are rounded to the tensors' dtype before the product with V, and the keys are blocked
+#      Tiles are per query head (the heads of a KV group re-read its rows), 16 rows, one sequence per call ------------------------------------------------------
+def _prefill_q(who: str, q: Tensor, pos0, L: int, hd: int, dt, out):
+    """q [T, n_heads, hd] with a dense last dimension (any strides of the other two that are multiples of 8 elements) against a cache of L positions of hd values
+    of dtype dt: (T, n_heads, pos0, out), out allocated [T, n_heads, hd] where None"""
+    if q.dim() != 3 or q.shape[0] < 1 or q.shape[1] < 1 or q.shape[2] != hd or q.stride(2) != 1 or q.stride(0) % 8 or q.stride(1) % 8:
+        raise ValueError(f"hqq_amd: {who} takes q [T, n_heads, head_dim] with T >= 1, the caches' head_dim, a dense last dimension and row / head strides that are "
+                         "multiples of 8 elements")
+    if dt not in (torch.float16, torch.bfloat16) or q.dtype != dt:
+        raise ValueError(f"hqq_amd: {who} takes fp16 / bf16 tensors of one dtype (q {q.dtype}, the cache {dt})")
+    T, n_heads = int(q.shape[0]), int(q.shape[1])
+    if isinstance(pos0, bool) or not isinstance(pos0, int) or pos0 < 0 or pos0 + T > L:
+        raise ValueError(f"hqq_amd: {who}: rows at positions pos0 .. pos0 + T - 1 (pos0 = {pos0!r}, a host integer >= 0; T = {T}) do not fit a cache of {L}")
+    if out is None:
+        out = torch.empty(T, n_heads, hd, dtype=dt, device=q.device)
+    elif out.dtype != dt or out.numel() != T * n_heads * hd or not out.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes out as a dense [T, n_heads, head_dim] tensor of q's dtype")
+    return T, n_heads, pos0, out
+
+
+def attn_prefill(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos0: int, out: Tensor | None = None, scaling: float | None = None) -> Tensor:
+    """Causal attention of a prompt's T rows on ONE sequence's dense static cache (hqq_hip_attn_prefill, csrc/attn_prefill.hip).  q [T, n_heads, hd]: any view
+    with a dense last dimension — HF's [1, H, T, hd] query goes in as query[0].transpose(0, 1), through its strides, without a copy; k_cache / v_cache
+    [n_kv, L, hd] or [1, n_kv, L, hd], already holding the rows' keys and values at positions pos0 .. pos0 + T - 1; pos0 a host integer.  Row t attends over keys
+    [0, pos0 + t].  Returns out [T, n_heads, hd] (dense; allocated when None), the layout o_proj takes.  scaling: hd ** -0.5 when None.
+    fp16 / bf16, hd 64 / 128 / 256, n_heads a multiple of n_kv, L <= 30000.  A prompt that does not fit the cache is a ValueError (no clamping).
+    Contract (a) - (g) above: per 16-row tile the bits of attn_decode_tiled (splits = 1), within tests/_tile_cases.py's band of float64 attention, nothing at or
+    beyond pos0 + T read, exactly causal, deterministic and independent of q's strides — and NOT the bits of SDPA."""
+    _dev(q, k_cache, v_cache, out)
+    n_kv, L, hd = _shared_cache("attn_prefill", k_cache, v_cache)
+    if v_cache.dtype != k_cache.dtype:
+        raise ValueError("hqq_amd: attn_prefill takes caches of one dtype")
+    T, n_heads, pos0, out = _prefill_q("attn_prefill", q, pos0, L, hd, k_cache.dtype, out)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_attn_prefill(_p(q), q.stride(0), q.stride(1), _p(k_cache), _p(v_cache), pos0, T, _p(out), n_heads, n_kv, hd, L,
+                                           float(hd ** -0.5 if scaling is None else scaling), _dt(q.dtype), _stream())
+    _C.check(rc, "hqq_hip_attn_prefill")
+    return out.view(T, n_heads, hd)
+
+
+def attn_prefill_kvq(q: Tensor, bufs, pos0: int, head_dim: int, out: Tensor | None = None, scaling: float | None = None) -> Tensor:
+    """attn_prefill on ONE sequence's quantised cache (hqq_hip_attn_prefill_kvq): the six buffers [n_kv, L, ...] (or [1, n_kv, L, ...]), which already hold the
+    rows' quantised keys and values; every attended row is rebuilt to the compute dtype as it is loaded and the rest is attn_prefill's arithmetic in its order —
+    the output has the bits of attn_prefill on kv_dequantize's tensors (contract (c)), and no full-length dequantised tensor exists.  Nothing at or beyond
+    pos0 + T is read, in levels or in meta.  Covered where ops.kv_covers holds (NotImplementedError otherwise)."""
+    _dev(q, out)
+    if len(bufs) != 6 or not all(isinstance(t, Tensor) and t.dim() in (3, 4) and (t.dim() == 3 or t.shape[0] == 1) for t in bufs):
+        raise ValueError("hqq_amd: attn_prefill_kvq takes ONE sequence's six cache buffers (kq, k_scale, k_zero, vq, v_scale, v_zero) [n_kv_heads, cache_len, .] (or [1, ...])")
+    bufs = tuple(t.view(1, *t.shape[-3:]) for t in bufs)
+    hd = int(head_dim)
+    _, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, hd, "attn_prefill_kvq")
+    T, n_heads, pos0, out = _prefill_q("attn_prefill_kvq", q, pos0, L, hd, dt, out)
+    with torch.cuda.device(q.device):
+        rc = _C.lib().hqq_hip_attn_prefill_kvq(nbits, _p(q), q.stride(0), q.stride(1), *(_p(t) for t in bufs), pos0, T, _p(out), n_heads, n_kv, hd, gs, L,
+                                               float(hd ** -0.5 if scaling is None else scaling), _dt(dt), _stream())
+    _C.check(rc, "hqq_hip_attn_prefill_kvq")
+    return out.view(T, n_heads, hd)
+
+
 def argmax_advance_batched(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, pos: Tensor | None = None) -> None:
     """The back of a greedy decode step for B sequences in one launch, one workgroup per row (hqq_hip_argmax_advance_batched): next_tok[b] = logits[b].argmax() (the first
     index of the largest value; torch.argmax's tie and NaN rule), tok[b] = the same, pos[b] += 1 (each skipped when None).  logits [B, vocab] dense; int64 tensors of

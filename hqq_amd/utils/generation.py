@@ -60,6 +60,12 @@ def check_gqa_attention(gqa_attention) -> None:
         raise ValueError("gqa_attention: 'heads' or 'group'")
 
 
+def check_prefill_attention(prefill_attention) -> None:
+    """the decoders' prefill_attention keyword: "model" or "hip" (ValueError otherwise)"""
+    if isinstance(prefill_attention, bool) or prefill_attention not in ("model", "hip"):
+        raise ValueError("prefill_attention: 'model' or 'hip'")
+
+
 def check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attention="rows") -> None:
     """the speculative-decoding keywords of GraphedGreedyDecoder and HFGenerator: speculate None or "ngram", draft_rows an integer in 2 .. ops.SPEC_MAX_ROWS,
     ngram_max an integer in 0 .. ops.SPEC_MAX_NGRAM, no sampling with speculation (acceptance is the greedy rule), verify_attention "rows" or "tile" and "tile"
@@ -160,13 +166,20 @@ class GraphedGreedyDecoder:
     (opt-in) — one workgroup per KV-head group (ops.attn_decode_gqa_batched / ops.attn_decode_gqa_kvq_batched: each key read, and a packed key rebuilt, once for
     the query heads that share it; the tile kernel's contract, not the one-row kernel's bits).  It is passed to the plain and the batched fused steps where
     llama_fused.supports_gqa_attention(model) holds and attention == "hip" (`gqa_grouped` says whether); otherwise, and for the speculative verify step always,
-    the keyword has no effect.  Assigning `decoder.gqa_attention` rebuilds the kept state at the next generate()."""
+    the keyword has no effect.  Assigning `decoder.gqa_attention` rebuilds the kept state at the next generate().
+    prefill_attention: what the prefill's attention runs through.  "model" (default) — the model's own forward as before: HF's attention function on the whole static
+    cache (max_cache_len positions under a [T, max_cache_len] mask; on a quantised cache a full-length dequantised copy per layer).  "hip" (opt-in) — every prefill
+    this decoder runs (generate(), the speculative generate(), each prompt of generate_batch, behind bank.activate as well) is still the model's own forward, but its
+    attention modules call ops.attn_prefill (ops.attn_prefill_kvq on a quantised cache, whose layers then dequantise nothing): only keys [0, t] are read for row t
+    (utils/prefill_attn.py switches config._attn_implementation for the duration of that forward).  Its contract is the tile kernel's — within a derived band of
+    float64 attention, NOT the bits of SDPA.  Served where llama_fused.supports_prefill_attention holds for the model and the cache (`prefill_hip` says whether);
+    otherwise the prefill runs as before.  Independent of `attention`, which names the decode steps' attention."""
 
     def __init__(self, model, max_cache_len: int = 512, fused: bool = True, attention: str = "sdpa", bucket_cache: bool = True, glue: str = "auto",
                  do_sample: bool = False, temperature: float = 0.6, top_k: int | None = 5, axis0: str = "model", qk_norm: str = "model",
                  qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
                  speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, verify_attention: str = "rows", lora_bank=None,
-                 gqa_attention: str = "heads"):
+                 gqa_attention: str = "heads", prefill_attention: str = "model"):
         from transformers import StaticCache
         from . import llama_fused
         from .kv_cache import check_kv_group_size, kv_cache_bits
@@ -175,6 +188,8 @@ class GraphedGreedyDecoder:
         self._verify_attention = verify_attention
         check_gqa_attention(gqa_attention)
         self._gqa_attention = gqa_attention
+        check_prefill_attention(prefill_attention)
+        self.prefill_attention = prefill_attention
         self.kv_bits = kv_cache_bits(kv_cache)   # (None: the dense StaticCache)
         check_kv_group_size(kv_cache, kv_group_size)
         self.kv_cache, self.kv_group_size = kv_cache, kv_group_size
@@ -205,6 +220,8 @@ class GraphedGreedyDecoder:
                                 and llama_fused.supports_speculation(model, self.draft_rows))
         self._spec = None      # the state holder of the speculative route (its own cache, verify step, history, device scalars and graphs)
         self.spec_stats = {"steps": 0, "tokens": 0}
+        # whether the prefills attend through ops.attn_prefill: asked for, and a model and cache the kernel covers (otherwise they run as before, without a message)
+        self.prefill_hip = bool(prefill_attention == "hip" and llama_fused.supports_prefill_attention(model, max_cache_len, self.kv_bits, kv_group_size))
 
     @property
     def verify_attention(self) -> str:
@@ -245,6 +262,16 @@ class GraphedGreedyDecoder:
             return self._StaticCache(config=self.model.config, max_cache_len=self.max_cache_len)
         from .kv_cache import QuantizedStaticCache
         return QuantizedStaticCache(self.model.config, self.max_cache_len, self.kv_bits, self.kv_group_size)
+
+    def _prefill(self, ids: Tensor, cache):
+        """the prompt ids [1, T] through the model's own forward into `cache` (reset by the caller: the rows stand at positions 0 .. T - 1); with `prefill_hip` its
+        attention modules attend through ops.attn_prefill for the duration of this call"""
+        T = ids.shape[1]
+        if not self.prefill_hip:
+            return self.model(ids, past_key_values=cache, cache_position=torch.arange(T, device=self.device), use_cache=True)
+        from .prefill_attn import hip_prefill
+        with hip_prefill(self.model, cache, 0):
+            return self.model(ids, past_key_values=cache, cache_position=torch.arange(T, device=self.device), use_cache=True)
 
     def _step_keywords(self) -> dict:
         """what the fused steps are told about the cache (nothing with the dense one: their call is the one it was)"""
@@ -384,7 +411,7 @@ class GraphedGreedyDecoder:
             self.cache.reset()
         else:
             self.cache = self._new_cache()
-        out = self.model(ids, past_key_values=self.cache, cache_position=torch.arange(T, device=self.device), use_cache=True)   # prefill
+        out = self._prefill(ids, self.cache)
         first = self._pick(out.logits[:, -1])
         if kept:
             st = self._state   # (its tensors are the ones the captured graphs read and write)
@@ -478,7 +505,7 @@ class GraphedGreedyDecoder:
         R, T = self.draft_rows, ids.shape[1]
         cache = st["cache"]
         cache.reset()
-        out = self.model(ids, past_key_values=cache, cache_position=torch.arange(T, device=self.device), use_cache=True)   # prefill
+        out = self._prefill(ids, cache)
         first = self._pick(out.logits[:, -1])
         last = T + max_new_tokens - 1   # the index of the last token to emit; the first one is hist[T]
         eos = -1 if eos_token_id is None else int(eos_token_id)
@@ -637,7 +664,7 @@ class GraphedGreedyDecoder:
             scratch.reset()
             if slots:
                 self.lora_bank.activate(self.model, slots[b])
-            out = self.model(x, past_key_values=scratch, cache_position=torch.arange(lengths[b], device=self.device), use_cache=True)
+            out = self._prefill(x, scratch)
             firsts.append(self._pick(out.logits[:, -1]))
             for dst, src in zip(bc.layers, scratch.layers):
                 if self.kv_bits is not None:   # the six buffers of a quantised layer: rows are independent, so a copied row is the row a B-row prefill would have stored
@@ -714,7 +741,7 @@ class HFGenerator:
     Differences a caller can see: EOS is looked for every 16 tokens on the host instead of after every token (no per-token synchronisation; the text returned is cut at
     the EOS all the same); "output_tokens" holds every generated token before the EOS (the reference's slice drops the last one it generated, generation_hf.py:493);
     a prompt that leaves less than max_new_tokens of cache generates what fits.
-    speculate / draft_rows / ngram_max / verify_attention / gqa_attention and attention are GraphedGreedyDecoder's keywords (defaults: no speculation, HF's attention function); speculation is served
+    speculate / draft_rows / ngram_max / verify_attention / gqa_attention / prefill_attention and attention are GraphedGreedyDecoder's keywords (defaults: no speculation, HF's attention function); speculation is served
     with attention="hip" only, and everything else decodes as before (`decoder.speculating` says which).
     lora_bank, and the adapter / adapters keywords of generate / generate_batch, are GraphedGreedyDecoder's: passed through."""
 
@@ -722,7 +749,7 @@ class HFGenerator:
                  compile: str | None = None, compile_options: dict | None = None, patch_accelerate: bool = True, axis0: str = "model", qk_norm: str = "model",
                  qkv_bias: str = "model", lora: str = "model", moe: str = "model", kv_cache: str | None = None, kv_group_size: int | None = None,
                  speculate: str | None = None, draft_rows: int = 8, ngram_max: int = 3, attention: str = "sdpa", verify_attention: str = "rows", lora_bank=None,
-                 gqa_attention: str = "heads"):
+                 gqa_attention: str = "heads", prefill_attention: str = "model"):
         if compile not in (None, "partial", "full"):
             raise ValueError("compile: None, 'partial' or 'full'")
         opt_ins(axis0=axis0, qk_norm=qk_norm, qkv_bias=qkv_bias, lora=lora, moe=moe)   # (GraphedGreedyDecoder's keywords, checked before anything is built)
@@ -731,6 +758,7 @@ class HFGenerator:
         check_kv_group_size(kv_cache, kv_group_size)
         check_speculation(speculate, draft_rows, ngram_max, do_sample, verify_attention)
         check_gqa_attention(gqa_attention)
+        check_prefill_attention(prefill_attention)
         self.model, self.tokenizer = model, tokenizer
         self.device = next(p.device for p in model.parameters() if p.device.type == "cuda")
         self.do_sample = bool(do_sample)
@@ -745,7 +773,7 @@ class HFGenerator:
         self.decoder = GraphedGreedyDecoder(model, max_cache_len=self.cache_size, do_sample=self.do_sample, temperature=temperature, top_k=top_k, axis0=axis0, qk_norm=qk_norm,
                                             qkv_bias=qkv_bias, lora=lora, moe=moe, kv_cache=kv_cache, kv_group_size=kv_group_size, speculate=speculate,
                                             draft_rows=draft_rows, ngram_max=ngram_max, attention=attention, verify_attention=verify_attention, lora_bank=lora_bank,
-                                            gqa_attention=gqa_attention)
+                                            gqa_attention=gqa_attention, prefill_attention=prefill_attention)
         self.init()
 
     @staticmethod

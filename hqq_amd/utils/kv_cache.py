@@ -9,6 +9,8 @@ QuantizedStaticCache is the COMPOSED route: a transformers Cache of static layer
 no host synchronisation, so the model's own forward stays graph-capturable with it) whose update() writes the incoming rows with ops.kv_quantize and returns the
 full-length dequantised tensors of ops.kv_dequantize.  One rule throughout: every attended key and value is the stored, dequantised one, the prompt's included.
 It holds only the six quantised buffers per layer; the dense tensors are per-layer transients.  It serves any model the dense StaticCache serves.
+Under GraphedGreedyDecoder(prefill_attention="hip") a prefill sets the layers' packed_prefill flag for its duration: update() then quantises as always and
+dequantises nothing, and the attention reads the six buffers itself (ops.attn_prefill_kvq) — the rule above holds, without the full-length tensors.
 The FUSED route (llama_fused.FusedLlamaStep on such a cache) reads the same buffers with ops.rope_kvq_cache_batched and ops.attn_decode_kvq_batched.
 """
 from __future__ import annotations
@@ -47,6 +49,7 @@ class QuantizedStaticLayer(StaticLayer):
         super().__init__(max_cache_len=max_cache_len)
         self.nbits, self.group_size = int(nbits), group_size
         self.bufs = None
+        self.packed_prefill = False   # set for the duration of a prefill_attention="hip" prefill (utils/prefill_attn.py): update() then dequantises nothing
 
     def lazy_initialization(self, key_states: torch.Tensor, value_states: torch.Tensor) -> None:
         self.dtype, self.device = key_states.dtype, key_states.device
@@ -64,11 +67,15 @@ class QuantizedStaticLayer(StaticLayer):
         self.is_initialized = True
 
     def update(self, key_states: torch.Tensor, value_states: torch.Tensor, *args, **kwargs):
-        """the incoming rows quantised into positions cumulative_length .. + T - 1 (read on the device), then the whole cache dequantised: what the layer attends"""
+        """the incoming rows quantised into positions cumulative_length .. + T - 1 (read on the device), then the whole cache dequantised: what the layer attends.
+        Under packed_prefill the rows are quantised the same way and handed back as they came: the prefill's attention function (prefill_attn.hip_prefill_attention)
+        does not look at them — it reads this layer's `bufs` through ops.attn_prefill_kvq, so what is attended is still the stored, dequantised row"""
         if not self.is_initialized:
             self.lazy_initialization(key_states, value_states)
         ops.kv_quantize(key_states, value_states, self.bufs, start=self.cumulative_length.view(1))
         self.cumulative_length.add_(key_states.shape[-2])
+        if self.packed_prefill:
+            return key_states, value_states
         return ops.kv_dequantize(self.bufs, self.k_head_dim)
 
     def reset(self) -> None:

@@ -516,6 +516,44 @@ def supports_gqa_attention(model) -> bool:
     return ops.attn_gqa_covers(n_heads, n_kv) and head_dim(cfg) in (64, 128, 256)
 
 
+def supports_prefill_attention(model, max_cache_len: int | None = None, kv_bits: int | None = None, kv_group_size: int | None = None) -> bool:
+    """the coverage rule of GraphedGreedyDecoder(prefill_attention="hip") (utils/prefill_attn.py; ops.attn_prefill / ops.attn_prefill_kvq attend ONE sequence's
+    prompt): full attention in every layer — the sliding-window signals _arch_ok reads for the model's family (FAMILIES; every one of them for a model type no
+    family names), and no window on an attention module —, no attention sinks, no soft-capping of the attention logits, keys and values of one head_dim of
+    64 / 128 / 256, fp16 / bf16, query heads a multiple of the KV heads.  The hook sits behind the projections, the norms and the rotary embedding, so nothing
+    else about the block is asked.  With max_cache_len also the cache the decoder would build: a dense StaticCache of up to ops.KV_MAX_LEN positions, or
+    (kv_bits 8 / 4, kv_group_size None: ops.kv_group_size's default) a QuantizedStaticCache that ops.kv_covers serves."""
+    try:
+        cfg = model.config
+        hd = head_dim(cfg)
+        n_heads = cfg.num_attention_heads
+        n_kv = getattr(cfg, "num_key_value_heads", None) or n_heads
+        if hd not in (64, 128, 256) or n_heads % n_kv or getattr(cfg, "attn_logit_softcapping", None):
+            return False
+        if any(getattr(cfg, name, None) not in (None, hd) for name in ("v_head_dim", "qk_head_dim")):
+            return False
+        family = next((f for f in FAMILIES.values() if getattr(cfg, "model_type", None) in f.model_types), None)
+        sliding = ("sliding_window", "use_sliding_window", "layer_types") if family is None else family.sliding
+        if any(getattr(cfg, sig, None) for sig in sliding if sig != "layer_types"):
+            return False
+        if "layer_types" in sliding and any(t != "full_attention" for t in (getattr(cfg, "layer_types", None) or ())):
+            return False
+        dt = model.model.norm.weight.dtype
+        if dt not in (torch.float16, torch.bfloat16):
+            return False
+        for blk in model.model.layers:
+            at = blk.self_attn
+            if hasattr(at, "sinks") or getattr(at, "sliding_window", None) or not isinstance(getattr(at, "layer_idx", None), int):
+                return False
+        if max_cache_len is None:
+            return True
+        if kv_bits is None:
+            return 1 <= int(max_cache_len) <= ops.KV_MAX_LEN
+        return ops.kv_covers(dt, kv_bits, hd, ops.kv_group_size(hd) if kv_group_size is None else kv_group_size, int(max_cache_len))
+    except (AttributeError, TypeError):
+        return False
+
+
 def _rec(L):
     """a layer as ops.gemv_block and the re-layout functions take it"""
     return (L.W_q, L.scale, L.zero, L.out_features)

@@ -711,6 +711,32 @@ int hqq_hip_attn_decode_gqa_kvq_batched(int nbits, const void* q, const void* kq
                                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * hqq_hip_attn_prefill / hqq_hip_attn_prefill_kvq (csrc/attn_prefill.hip): causal attention of the T rows of ONE sequence's prompt against its static cache —
+ * dense caches [n_kv_heads, cache_len, hd], or the six buffers [n_kv_heads, cache_len, .] of the quantised cache — that reads only the causal part of it
+ * (opt-in: GraphedGreedyDecoder(prefill_attention = "hip")).  Query row t of head h is at q + t q_row_stride + h q_head_stride (strides in ELEMENTS, hd dense;
+ * both multiples of 8) and stands at position pos0 + t: it attends over keys [0, pos0 + t].  The keys and values of the T rows are already in the cache when the
+ * call runs.  out is dense [T, n_heads, hd].  pos0 and T are host integers (a prefill is not graph-captured).  fp16 / bf16, hd 64 / 128 / 256,
+ * n_heads a multiple of n_kv_heads, cache_len <= 30000; the packed entry is additionally bounded by hqq_hip_kv_covers.
+ * The grid is (n_heads, ceil(T / 16)): workgroup (h, j) serves rows 16 j .. min(16 j + 15, T - 1) of head h as the rows of hqq_hip_attn_decode_tiled's 16-row MFMA
+ * query tile (csrc/attn_tile_core.h is the one text), each with its own causal limit, over keys [0, n_max), n_max = pos0 + min(16 j + 16, T), in ONE share: no
+ * split, no workspace, no merging launch.  Tiles are per query head: the heads of a KV group re-read the same K and V rows.
+ * The two symbols were added without raising HQQ_HIP_ABI_VERSION: nothing that existed at version 9 changed its signature, constants or bits.
+ * CONTRACT.  (a) rows 16 j .. of head h are bit-identical to hqq_hip_attn_decode_tiled on those queries with pos = pos0 + 16 j + i and splits = 1; (b) every row
+ *   lies within tests/_tile_cases.py's band of float64 attention (c_acc(n_max, 1)); (c) the packed entry is bit-identical to the dense one on
+ *   hqq_hip_kv_dequantize's tensors; (d) nothing at or beyond pos0 + T is read, in levels, meta or dense rows (it may hold NaN); (e) row i depends on no query of
+ *   a row > i and on no FINITE key / value at a position > pos0 + i (a masked V row inside the tile's range is multiplied by an exact 0); (f) deterministic, and
+ *   the bits do not depend on q's strides; (g) it does NOT produce the bits of a softmax-then-matmul in the tensors' dtype (SDPA): the probabilities are rounded to
+ *   the tensors' dtype before the product with V, and the keys are blocked.  Padding rows of the last tile read no query memory and write nothing.
+ *   There is no position clamping: T < 1, pos0 < 0 or pos0 + T > cache_len is HQQ_ERR_SHAPE; a stride that is negative or no multiple of 8: HQQ_ERR_ALIGN; then
+ *   (packed entry) the quantised cache's coverage rule, then hqq_hip_attn_decode_batched's checks with their codes; nothing is launched after an error.
+ * ------------------------------------------------------------------------------------------- */
+int hqq_hip_attn_prefill(const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* k_cache, const void* v_cache, int64_t pos0, int64_t T, void* out,
+                         int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t cache_len, float scaling, int dtype, void* stream);
+int hqq_hip_attn_prefill_kvq(int nbits, const void* q, int64_t q_row_stride, int64_t q_head_stride, const void* kq, const void* k_scale, const void* k_zero,
+                             const void* vq, const void* v_scale, const void* v_zero, int64_t pos0, int64_t T, void* out, int64_t n_heads, int64_t n_kv_heads,
+                             int64_t head_dim, int64_t group_size, int64_t cache_len, float scaling, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Quantizer.quantize + optimize_weights_proximal_legacy + BitPack.pack_* in one call
  * (quantize.py:75-180, optimize.py:96-108, 201-255), axis=1, channel_wise=True.
  *   W          [N*K] of w_dtype (F32/F16/BF16); promoted to float32 (`tensor.float()`, quantize.py:102)
