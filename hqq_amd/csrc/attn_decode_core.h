@@ -217,15 +217,21 @@ static inline int attn_raise_lds(LdsRaised& raised, const void* kern, int lds, i
   return lds > 48 * 1024 ? raise_lds_limit(raised, kern, lds_max, who) : 0;
 }
 
-// a checked call's launches: launch(HDc, BFc) -> 0 or an error code starts the attention kernel of that instantiation; the shares of a split call (records of
-// head r n_heads + h, the offset of output row r, head h in a dense [rows, n_heads, HD] output) are then merged, and the launches checked
+// behind the attention kernel's launch (rc: what starting it gave): the shares of a split call (records of head r n_heads + h, the offset of output row r,
+// head h in a dense [rows, n_heads, HD] output) are merged, and the launches checked
+static inline int attn_finish(const AttnCall& c, int rc) {
+  if (rc) return rc;
+  if (c.S() > 1) launch_attn_combine(c.ws(), c.out, c.rows * c.n_heads, c.S(), c.HD(), c.bf(), as_stream(c.stream));
+  return check_launch(c.who);
+}
+
+// a checked call's launches: launch(HDc, BFc) -> 0 or an error code starts the attention kernel of that instantiation, then attn_finish.  (A call on the
+// quantised cache dispatches on the width too: kv_dispatch in kv_load.h, then attn_finish)
 template <class Launch>
 static inline int attn_launch(const AttnCall& c, Launch&& launch) {
   int rc = 0;
   attn_dispatch(c.head_dim, c.bf(), [&](auto HDc, auto BFc) { rc = launch(HDc, BFc); });
-  if (rc) return rc;
-  if (c.S() > 1) launch_attn_combine(c.ws(), c.out, c.rows * c.n_heads, c.S(), c.HD(), c.bf(), as_stream(c.stream));
-  return check_launch(c.who);
+  return attn_finish(c, rc);
 }
 
 }  // namespace hqq

@@ -10,10 +10,10 @@
 //            kernels' workspace layout, so that attn_combine_kernel (block.hip) finishes a split call as it finishes theirs.  Padding rows (u >= G) hold a zero
 //            fragment, read no query memory and write nothing
 //   position all rows share pos[b], clamped as the one-row kernels clamp it (outside [0, L): the last slot); chunk = ceil((pos[b] + 1) / S), empty shares allowed
-//   loaders  dense: plain 16-byte loads of the sequence's cache rows.  Quantised: kv_load8 (kv_load.h) on the six buffers — everything behind a loader is the one
-//            body, so the quantised entry has the bits of the dense one on kv_dequantize's tensors with the same splits
-//   host     attn_check / attn_launch (attn_decode_core.h) behind the entries' own checks: 1 <= G <= 16, then kv_check for the packed entry
-// Nothing at or beyond pos[b] + 1 of a sequence's cache is read (the body never asks a loader for a row >= k1), in levels or in meta.  No atomics, no allocation.
+//   source   attn_gqa_kernel<HD, BF, Src> on DenseKV (attn_tile_core.h) or PackedKV (kv_load.h): everything behind the source is the one body, so the quantised
+//            entry has the bits of the dense one on kv_dequantize's tensors with the same splits
+//   host     attn_check / attn_launch / tile_launch behind the entries' own checks: 1 <= G <= 16, then kv_check for the packed entry
+// Nothing at or beyond pos[b] + 1 of a sequence's cache is read (the body never asks the source for a row >= k1), in levels or in meta.  No atomics, no allocation.
 // Compiled with attn_tile.hip's flags.
 #include "block_math.h"
 #include "attn_decode_core.h"
@@ -48,43 +48,15 @@ __device__ __forceinline__ int group_pos(const int64_t* __restrict__ pos, int L)
   return (p_raw >= 0 && p_raw < L) ? static_cast<int>(p_raw) : L - 1;
 }
 
-template <int HD, bool BF>
-__global__ __launch_bounds__(TILE_WAVES * 64) void attn_gqa_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
-                                                                   const int64_t* __restrict__ pos, uint16_t* __restrict__ out, int n_heads, int n_kv, int L,
-                                                                   float scaling, int S, float* __restrict__ ws) {
+template <int HD, bool BF, class Src>
+__global__ __launch_bounds__(TILE_WAVES * 64) void attn_gqa_kernel(const uint16_t* __restrict__ q, const Src src, const int64_t* __restrict__ pos,
+                                                                   uint16_t* __restrict__ out, int n_heads, int n_kv, int L, float scaling, int S,
+                                                                   float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const GroupTile<HD> tile = group_tile<HD>(q, out, ws, n_heads, n_kv, S);
   const int p = group_pos(pos, L);
-  const int64_t r0 = (static_cast<int64_t>(blockIdx.z) * n_kv + blockIdx.x) * L;
-  const uint16_t* K = kc + r0 * HD;
-  const uint16_t* V = vc + r0 * HD;
-  auto krow = [&](int ch, int j) -> u32x4 { return *reinterpret_cast<const u32x4*>(K + static_cast<int64_t>(j) * HD + 8 * ch); };
-  auto vrow = [&](int ch, int j) -> u32x4 { return *reinterpret_cast<const u32x4*>(V + static_cast<int64_t>(j) * HD + 8 * ch); };
-  attn_tile_body<HD, BF>(smem, tile, p + 1, (static_cast<int>(threadIdx.x) & 15) < tile.rows ? p : -1, blockIdx.y, S, scaling, krow, vrow);
-}
-
-template <int HD, int NBITS, bool BF>
-__global__ __launch_bounds__(TILE_WAVES * 64) void attn_gqa_kvq_kernel(const uint16_t* __restrict__ q, const uint8_t* __restrict__ kq, const uint16_t* __restrict__ ks,
-                                                                       const uint16_t* __restrict__ kz, const uint8_t* __restrict__ vq, const uint16_t* __restrict__ vs,
-                                                                       const uint16_t* __restrict__ vz, const int64_t* __restrict__ pos, uint16_t* __restrict__ out,
-                                                                       int n_heads, int n_kv, int L, int gs_shift, float scaling, int S, float* __restrict__ ws) {
-  constexpr int RB = HD * NBITS / 8;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const GroupTile<HD> tile = group_tile<HD>(q, out, ws, n_heads, n_kv, S);
-  const int p = group_pos(pos, L);
-  const int NG = HD >> gs_shift;   // (scale, zero) pairs per row
-  const int64_t r0 = (static_cast<int64_t>(blockIdx.z) * n_kv + blockIdx.x) * L;
-  kq += r0 * RB; vq += r0 * RB;
-  ks += r0 * NG; kz += r0 * NG; vs += r0 * NG; vz += r0 * NG;
-  auto krow = [&](int ch, int j) -> u32x4 {
-    const int64_t r = j;
-    return kv_load8<HD, NBITS, BF>(kq + r * RB, ks + r * NG, kz + r * NG, ch, gs_shift);
-  };
-  auto vrow = [&](int ch, int j) -> u32x4 {
-    const int64_t r = j;
-    return kv_load8<HD, NBITS, BF>(vq + r * RB, vs + r * NG, vz + r * NG, ch, gs_shift);
-  };
-  attn_tile_body<HD, BF>(smem, tile, p + 1, (static_cast<int>(threadIdx.x) & 15) < tile.rows ? p : -1, blockIdx.y, S, scaling, krow, vrow);
+  const auto kv = src.at((static_cast<int64_t>(blockIdx.z) * n_kv + blockIdx.x) * L);   // the sequence's rows of this KV head
+  attn_tile_body<HD, BF>(smem, tile, p + 1, (static_cast<int>(threadIdx.x) & 15) < tile.rows ? p : -1, blockIdx.y, S, scaling, kv);
 }
 
 // the entries' own check, before the shared front: the group is one MFMA tile
@@ -95,8 +67,13 @@ static inline int gqa_check(const char* who, int64_t n_heads, int64_t n_kv_heads
   return 0;
 }
 
-// the grid of a grouped launch: (n_kv_heads, splits, sequences)
-static inline dim3 gqa_grid(const AttnCall& c) { return dim3(static_cast<unsigned>(c.n_kv_heads), static_cast<unsigned>(c.splits), static_cast<unsigned>(c.rows)); }
+// a grouped launch on source `src`: the grid is (n_kv_heads, splits, sequences)
+template <int HD, bool BF, class Src>
+static inline int gqa_launch(const AttnCall& c, const void* q, const Src& src, const int64_t* pos_dev, float scaling) {
+  const dim3 grid(static_cast<unsigned>(c.n_kv_heads), static_cast<unsigned>(c.splits), static_cast<unsigned>(c.rows));
+  return tile_launch<&attn_gqa_kernel<HD, BF, Src>, HD>(c, grid, static_cast<const uint16_t*>(q), src, pos_dev, static_cast<uint16_t*>(c.out), static_cast<int>(c.n_heads),
+                                                        static_cast<int>(c.n_kv_heads), static_cast<int>(c.cache_len), scaling, c.S(), c.ws());
+}
 
 extern "C" {
 
@@ -109,14 +86,8 @@ int hqq_hip_attn_decode_gqa_batched(const void* q, const void* k_cache, const vo
   const AttnCall c{who, batch, n_heads, n_kv_heads, head_dim, cache_len, dtype, splits, workspace, workspace_bytes, out, stream};
   if (const int rc = attn_check(c, {q, k_cache, v_cache, pos_dev, out}, {q, k_cache, v_cache, out})) return rc;
   return attn_launch(c, [&](auto HDc, auto BFc) {
-    constexpr auto kern = &attn_gqa_kernel<decltype(HDc)::value, decltype(BFc)::value>;
-    constexpr int lds = tile_lds_bytes<decltype(HDc)::value>();
-    static LdsRaised raised;   // (one per instantiation)
-    if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, lds, who)) return rc;
-    hipLaunchKernelGGL(kern, gqa_grid(c), dim3(TILE_WAVES * 64), lds, as_stream(stream), static_cast<const uint16_t*>(q), static_cast<const uint16_t*>(k_cache),
-                       static_cast<const uint16_t*>(v_cache), pos_dev, static_cast<uint16_t*>(out), static_cast<int>(n_heads), static_cast<int>(n_kv_heads),
-                       static_cast<int>(cache_len), scaling, c.S(), c.ws());
-    return 0;
+    constexpr int HD = decltype(HDc)::value;
+    return gqa_launch<HD, decltype(BFc)::value>(c, q, DenseKV<HD>{static_cast<const uint16_t*>(k_cache), static_cast<const uint16_t*>(v_cache)}, pos_dev, scaling);
   });
 }
 
@@ -130,21 +101,13 @@ int hqq_hip_attn_decode_gqa_kvq_batched(int nbits, const void* q, const void* kq
   if (const int rc = kv_check(who, nbits, head_dim, group_size, cache_len, dtype)) return rc;   // (the cache's coverage rule answers with its own code)
   const AttnCall c{who, batch, n_heads, n_kv_heads, head_dim, cache_len, dtype, splits, workspace, workspace_bytes, out, stream};
   if (const int rc = attn_check(c, {q, kq, k_scale, k_zero, vq, v_scale, v_zero, pos_dev, out}, {q, kq, vq, out})) return rc;
-  const int gs_shift = group_size == 64 ? 6 : 5;
-  return attn_launch(c, [&](auto HDc, auto BFc) {
-    auto go = [&](auto NBc) {
-      constexpr auto kern = &attn_gqa_kvq_kernel<decltype(HDc)::value, decltype(NBc)::value, decltype(BFc)::value>;
-      constexpr int lds = tile_lds_bytes<decltype(HDc)::value>();
-      static LdsRaised raised;   // (one per instantiation)
-      if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, lds, who)) return rc;
-      hipLaunchKernelGGL(kern, gqa_grid(c), dim3(TILE_WAVES * 64), lds, as_stream(stream), static_cast<const uint16_t*>(q), static_cast<const uint8_t*>(kq),
-                         static_cast<const uint16_t*>(k_scale), static_cast<const uint16_t*>(k_zero), static_cast<const uint8_t*>(vq),
-                         static_cast<const uint16_t*>(v_scale), static_cast<const uint16_t*>(v_zero), pos_dev, static_cast<uint16_t*>(out), static_cast<int>(n_heads),
-                         static_cast<int>(n_kv_heads), static_cast<int>(cache_len), gs_shift, scaling, c.S(), c.ws());
-      return 0;
-    };
-    return nbits == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{});
+  int rc = 0;
+  kv_dispatch(head_dim, nbits, c.bf(), [&](auto HDc, auto NBc, auto BFc) {
+    constexpr int HD = decltype(HDc)::value;
+    constexpr bool BF = decltype(BFc)::value;
+    rc = gqa_launch<HD, BF>(c, q, PackedKV<HD, decltype(NBc)::value, BF>::of(kq, k_scale, k_zero, vq, v_scale, v_zero, group_size), pos_dev, scaling);
   });
+  return attn_finish(c, rc);
 }
 
 }  // extern "C"

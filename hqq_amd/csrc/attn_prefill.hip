@@ -12,12 +12,12 @@
 //            (profiles/prefill_attn_summary.md): level with SDPA on the whole cache at 128 / 512 tokens, but NOT enough for long prompts — at 8192 tokens 2.97 ms per
 //            block against 1.47 on the dense cache, 5.2 - 6.3 against 1.5 on the quantised one: 16-row tiles re-read K and V T / 16 times
 //   order    the tiles with the most keys take the lowest block indices, so the long ones start first (a supposition about the tail, not a measured result)
-//   loaders  dense: plain 16-byte loads of the cache rows, as attn_tile.hip's.  Quantised: kv_load8 (kv_load.h) on the six buffers, as attn_gqa.hip's — everything
-//            behind a loader is the one body, so the quantised entry has the bits of the dense one on kv_dequantize's tensors
-//   host     attn_check / attn_launch (attn_decode_core.h) behind the entries' own checks: T >= 1, pos0 >= 0, pos0 + T <= cache_len (a prompt that does not fit is
-//            an error: there is no "attend at the last slot" rule here), strides that keep every query row 16-byte aligned; then kv_check for the packed entry
+//   source   attn_prefill_kernel<HD, BF, Src> on DenseKV (attn_tile_core.h) or PackedKV (kv_load.h): everything behind the source is the one body, so the
+//            quantised entry has the bits of the dense one on kv_dequantize's tensors
+//   host     attn_check / attn_launch / tile_launch behind the entries' own checks: T >= 1, pos0 >= 0, pos0 + T <= cache_len (a prompt that does not fit is an
+//            error: there is no "attend at the last slot" rule here), strides that keep every query row 16-byte aligned; then kv_check for the packed entry
 // Rows 16 j .. of head h have the bits of hqq_hip_attn_decode_tiled on those queries with pos = pos0 + 16 j + i and splits = 1: the same body, n_max and deal of
-// blocks to waves.  Nothing at or beyond pos0 + T is read (the body never asks a loader for a row >= n_max), in levels, meta or dense rows.  No atomics, no allocation.
+// blocks to waves.  Nothing at or beyond pos0 + T is read (the body never asks the source for a row >= n_max), in levels, meta or dense rows.  No atomics, no allocation.
 // NOT built here: sharing between the query heads of a KV group (tiles are per query head, so the G heads of a group re-read the same K and V rows; a tile of
 // G heads x 16 / G positions is the follow-up), query tiles of more than 16 rows for very long prompts, and several sequences per launch.
 // Compiled with attn_tile.hip's flags.
@@ -53,43 +53,15 @@ __device__ __forceinline__ PrefillTile<HD> prefill_tile(const uint16_t* q, int64
   return PrefillTile<HD>{rows, q + t0 * qrs + h * qhs, out + (static_cast<int64_t>(t0) * n_heads + h) * HD, qrs, static_cast<int64_t>(n_heads) * HD};
 }
 
-template <int HD, bool BF>
-__global__ __launch_bounds__(TILE_WAVES * 64) void attn_prefill_kernel(const uint16_t* __restrict__ q, int64_t qrs, int64_t qhs, const uint16_t* __restrict__ kc,
-                                                                       const uint16_t* __restrict__ vc, int pos0, int T, uint16_t* __restrict__ out, int n_heads,
-                                                                       int n_kv, int L, float scaling) {
+template <int HD, bool BF, class Src>
+__global__ __launch_bounds__(TILE_WAVES * 64) void attn_prefill_kernel(const uint16_t* __restrict__ q, int64_t qrs, int64_t qhs, const Src src, int pos0, int T,
+                                                                       uint16_t* __restrict__ out, int n_heads, int n_kv, int L, float scaling) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   int n_max, pr;
   const PrefillTile<HD> tile = prefill_tile<HD>(q, qrs, qhs, out, pos0, T, n_heads, n_max, pr);
   const int kvh = blockIdx.x / (n_heads / n_kv);
-  const uint16_t* K = kc + static_cast<int64_t>(kvh) * L * HD;
-  const uint16_t* V = vc + static_cast<int64_t>(kvh) * L * HD;
-  auto krow = [&](int ch, int j) -> u32x4 { return *reinterpret_cast<const u32x4*>(K + static_cast<int64_t>(j) * HD + 8 * ch); };
-  auto vrow = [&](int ch, int j) -> u32x4 { return *reinterpret_cast<const u32x4*>(V + static_cast<int64_t>(j) * HD + 8 * ch); };
-  attn_tile_body<HD, BF>(smem, tile, n_max, pr, 0, 1, scaling, krow, vrow);
-}
-
-template <int HD, int NBITS, bool BF>
-__global__ __launch_bounds__(TILE_WAVES * 64) void attn_prefill_kvq_kernel(const uint16_t* __restrict__ q, int64_t qrs, int64_t qhs, const uint8_t* __restrict__ kq,
-                                                                           const uint16_t* __restrict__ ks, const uint16_t* __restrict__ kz, const uint8_t* __restrict__ vq,
-                                                                           const uint16_t* __restrict__ vs, const uint16_t* __restrict__ vz, int pos0, int T,
-                                                                           uint16_t* __restrict__ out, int n_heads, int n_kv, int L, int gs_shift, float scaling) {
-  constexpr int RB = HD * NBITS / 8;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  int n_max, pr;
-  const PrefillTile<HD> tile = prefill_tile<HD>(q, qrs, qhs, out, pos0, T, n_heads, n_max, pr);
-  const int NG = HD >> gs_shift;   // (scale, zero) pairs per row
-  const int64_t r0 = static_cast<int64_t>(blockIdx.x / (n_heads / n_kv)) * L;
-  kq += r0 * RB; vq += r0 * RB;
-  ks += r0 * NG; kz += r0 * NG; vs += r0 * NG; vz += r0 * NG;
-  auto krow = [&](int ch, int j) -> u32x4 {
-    const int64_t r = j;
-    return kv_load8<HD, NBITS, BF>(kq + r * RB, ks + r * NG, kz + r * NG, ch, gs_shift);
-  };
-  auto vrow = [&](int ch, int j) -> u32x4 {
-    const int64_t r = j;
-    return kv_load8<HD, NBITS, BF>(vq + r * RB, vs + r * NG, vz + r * NG, ch, gs_shift);
-  };
-  attn_tile_body<HD, BF>(smem, tile, n_max, pr, 0, 1, scaling, krow, vrow);
+  const auto kv = src.at(static_cast<int64_t>(kvh) * L);
+  attn_tile_body<HD, BF>(smem, tile, n_max, pr, 0, 1, scaling, kv);
 }
 
 // the entries' own checks, before the shared front: the prompt fits the cache and every query row is 16-byte aligned
@@ -106,8 +78,14 @@ static inline int prefill_check(const char* who, int64_t pos0, int64_t T, int64_
   return 0;
 }
 
-// the grid of a prompt: (n_heads, tiles of 16 rows)
-static inline dim3 prefill_grid(const AttnCall& c) { return dim3(static_cast<unsigned>(c.n_heads), static_cast<unsigned>((c.rows + TILE_ROWS - 1) / TILE_ROWS)); }
+// a prompt's launch on source `src`: the grid is (n_heads, tiles of 16 rows); c.rows: the prompt's
+template <int HD, bool BF, class Src>
+static inline int prefill_launch(const AttnCall& c, const void* q, int64_t q_row_stride, int64_t q_head_stride, const Src& src, int64_t pos0, float scaling) {
+  const dim3 grid(static_cast<unsigned>(c.n_heads), static_cast<unsigned>((c.rows + TILE_ROWS - 1) / TILE_ROWS));
+  return tile_launch<&attn_prefill_kernel<HD, BF, Src>, HD>(c, grid, static_cast<const uint16_t*>(q), q_row_stride, q_head_stride, src, static_cast<int>(pos0),
+                                                            static_cast<int>(c.rows), static_cast<uint16_t*>(c.out), static_cast<int>(c.n_heads),
+                                                            static_cast<int>(c.n_kv_heads), static_cast<int>(c.cache_len), scaling);
+}
 
 extern "C" {
 
@@ -119,14 +97,9 @@ int hqq_hip_attn_prefill(const void* q, int64_t q_row_stride, int64_t q_head_str
   const AttnCall c{who, T, n_heads, n_kv_heads, head_dim, cache_len, dtype, 1, nullptr, 0, out, stream};   // (rows: the prompt's; one share)
   if (const int rc = attn_check(c, {q, k_cache, v_cache, out}, {q, k_cache, v_cache, out})) return rc;
   return attn_launch(c, [&](auto HDc, auto BFc) {
-    constexpr auto kern = &attn_prefill_kernel<decltype(HDc)::value, decltype(BFc)::value>;
-    constexpr int lds = tile_lds_bytes<decltype(HDc)::value>();
-    static LdsRaised raised;   // (one per instantiation)
-    if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, lds, who)) return rc;
-    hipLaunchKernelGGL(kern, prefill_grid(c), dim3(TILE_WAVES * 64), lds, as_stream(stream), static_cast<const uint16_t*>(q), q_row_stride, q_head_stride,
-                       static_cast<const uint16_t*>(k_cache), static_cast<const uint16_t*>(v_cache), static_cast<int>(pos0), static_cast<int>(T),
-                       static_cast<uint16_t*>(out), static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(cache_len), scaling);
-    return 0;
+    constexpr int HD = decltype(HDc)::value;
+    return prefill_launch<HD, decltype(BFc)::value>(c, q, q_row_stride, q_head_stride, DenseKV<HD>{static_cast<const uint16_t*>(k_cache), static_cast<const uint16_t*>(v_cache)},
+                                                    pos0, scaling);
   });
 }
 
@@ -139,21 +112,14 @@ int hqq_hip_attn_prefill_kvq(int nbits, const void* q, int64_t q_row_stride, int
   if (const int rc = kv_check(who, nbits, head_dim, group_size, cache_len, dtype)) return rc;   // (the cache's coverage rule answers with its own code)
   const AttnCall c{who, T, n_heads, n_kv_heads, head_dim, cache_len, dtype, 1, nullptr, 0, out, stream};
   if (const int rc = attn_check(c, {q, kq, k_scale, k_zero, vq, v_scale, v_zero, out}, {q, kq, vq, out})) return rc;
-  const int gs_shift = group_size == 64 ? 6 : 5;
-  return attn_launch(c, [&](auto HDc, auto BFc) {
-    auto go = [&](auto NBc) {
-      constexpr auto kern = &attn_prefill_kvq_kernel<decltype(HDc)::value, decltype(NBc)::value, decltype(BFc)::value>;
-      constexpr int lds = tile_lds_bytes<decltype(HDc)::value>();
-      static LdsRaised raised;   // (one per instantiation)
-      if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, lds, who)) return rc;
-      hipLaunchKernelGGL(kern, prefill_grid(c), dim3(TILE_WAVES * 64), lds, as_stream(stream), static_cast<const uint16_t*>(q), q_row_stride, q_head_stride,
-                         static_cast<const uint8_t*>(kq), static_cast<const uint16_t*>(k_scale), static_cast<const uint16_t*>(k_zero), static_cast<const uint8_t*>(vq),
-                         static_cast<const uint16_t*>(v_scale), static_cast<const uint16_t*>(v_zero), static_cast<int>(pos0), static_cast<int>(T),
-                         static_cast<uint16_t*>(out), static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(cache_len), gs_shift, scaling);
-      return 0;
-    };
-    return nbits == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{});
+  int rc = 0;
+  kv_dispatch(head_dim, nbits, c.bf(), [&](auto HDc, auto NBc, auto BFc) {
+    constexpr int HD = decltype(HDc)::value;
+    constexpr bool BF = decltype(BFc)::value;
+    rc = prefill_launch<HD, BF>(c, q, q_row_stride, q_head_stride, PackedKV<HD, decltype(NBc)::value, BF>::of(kq, k_scale, k_zero, vq, v_scale, v_zero, group_size), pos0,
+                                scaling);
   });
+  return attn_finish(c, rc);
 }
 
 }  // extern "C"

@@ -18,10 +18,9 @@
 //            and the cache beyond n_max may hold anything) and read transposed with ds_read_b64_tr_b16.  O stays in fp32 VGPRs, HD / 16 tiles
 //   end      the waves' (m, l, O) are merged through LDS in wave order (no atomics); S == 1: out[i] = T(O / l) for i < rows; S > 1: the share's record goes
 //            to ((i n_heads + h) S + sp) of the one-row kernels' workspace layout and attn_combine_kernel (block.hip) finishes over rows * n_heads heads
-//   body     the algorithm is stated in attn_tile_core.h (attn_tile_body), which the grouped-query kernels of attn_gqa.hip run too; this file keeps the tile of a
-//            verify step: the rows' queries, positions and outputs, and the dense loaders
-//   host     the entry point goes through the host front of every decode-attention call (attn_decode_core.h: the
-//            argument checks, the (head_dim, dtype) dispatch, the combine launch) and keeps only the row limit and its LDS size
+//   body     the algorithm is stated in attn_tile_core.h (attn_tile_body) over a tile and a K / V row source; attn_gqa.hip and attn_prefill.hip place other
+//            tiles on it.  This file keeps the tile of a verify step: the rows' queries, positions and outputs
+//   host     attn_check / attn_launch (attn_decode_core.h) and tile_launch (attn_tile_core.h) behind the entry's own check, the row limit
 //
 // Loads: a key row >= k1 is never read (K rows are clamped to k1 - 1 and masked, V rows are not loaded), so nothing at or beyond n_max <= L is touched.
 // Padding rows (i >= rows) read no query memory — their fragment is zero, their position -1: every key masked — and write nothing.
@@ -45,11 +44,11 @@ struct RowTile {
   __device__ __forceinline__ float* rec(int i) const { return wh + i * wstride; }
 };
 
-// the tile body (attn_tile_core.h) on the dense cache of ONE sequence, the rows' own positions
-template <int HD, bool BF>
-__global__ __launch_bounds__(TILE_WAVES * 64) void attn_tile_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
-                                                                    const int64_t* __restrict__ pos, int rows, uint16_t* __restrict__ out, int n_heads, int n_kv, int L,
-                                                                    float scaling, int S, float* __restrict__ ws) {
+// the tile body (attn_tile_core.h) on the cache of ONE sequence (served: Src = DenseKV<HD>), the rows' own positions
+template <int HD, bool BF, class Src>
+__global__ __launch_bounds__(TILE_WAVES * 64) void attn_tile_kernel(const uint16_t* __restrict__ q, const Src src, const int64_t* __restrict__ pos, int rows,
+                                                                    uint16_t* __restrict__ out, int n_heads, int n_kv, int L, float scaling, int S,
+                                                                    float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int h = blockIdx.x, sp = blockIdx.y, kvh = h / (n_heads / n_kv);
   const int row = threadIdx.x & 15;
@@ -61,13 +60,10 @@ __global__ __launch_bounds__(TILE_WAVES * 64) void attn_tile_kernel(const uint16
     n_max = p + 1 > n_max ? p + 1 : n_max;
     pr = i == row ? p : pr;
   }
-  const uint16_t* K = kc + static_cast<int64_t>(kvh) * L * HD;
-  const uint16_t* V = vc + static_cast<int64_t>(kvh) * L * HD;
+  const auto kv = src.at(static_cast<int64_t>(kvh) * L);
   const RowTile<HD> tile{rows, q + static_cast<int64_t>(h) * HD, out + static_cast<int64_t>(h) * HD,
                          S > 1 ? ws + (static_cast<int64_t>(h) * S + sp) * (HD + 2) : nullptr, static_cast<int64_t>(n_heads) * HD, static_cast<int64_t>(n_heads) * S * (HD + 2)};
-  auto krow = [&](int ch, int j) -> u32x4 { return *reinterpret_cast<const u32x4*>(K + static_cast<int64_t>(j) * HD + 8 * ch); };
-  auto vrow = [&](int ch, int j) -> u32x4 { return *reinterpret_cast<const u32x4*>(V + static_cast<int64_t>(j) * HD + 8 * ch); };
-  attn_tile_body<HD, BF>(smem, tile, n_max, pr, sp, S, scaling, krow, vrow);
+  attn_tile_body<HD, BF>(smem, tile, n_max, pr, sp, S, scaling, kv);
 }
 
 extern "C" {
@@ -82,14 +78,12 @@ int hqq_hip_attn_decode_tiled(const void* q, const void* k_cache, const void* v_
   const AttnCall c{who, rows, n_heads, n_kv_heads, head_dim, cache_len, dtype, splits, workspace, workspace_bytes, out, stream};
   if (const int rc = attn_check(c, {q, k_cache, v_cache, pos_dev, out}, {q, k_cache, v_cache, out})) return rc;
   return attn_launch(c, [&](auto HDc, auto BFc) {
-    constexpr auto kern = &attn_tile_kernel<decltype(HDc)::value, decltype(BFc)::value>;
-    constexpr int lds = tile_lds_bytes<decltype(HDc)::value>();
-    static LdsRaised raised;   // (one per instantiation)
-    if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, lds, who)) return rc;
-    hipLaunchKernelGGL(kern, c.grid(1), dim3(TILE_WAVES * 64), lds, as_stream(stream), static_cast<const uint16_t*>(q), static_cast<const uint16_t*>(k_cache),
-                       static_cast<const uint16_t*>(v_cache), pos_dev, static_cast<int>(rows), static_cast<uint16_t*>(out), static_cast<int>(n_heads),
-                       static_cast<int>(n_kv_heads), static_cast<int>(cache_len), scaling, c.S(), c.ws());
-    return 0;
+    constexpr int HD = decltype(HDc)::value;
+    using Src = DenseKV<HD>;
+    return tile_launch<&attn_tile_kernel<HD, decltype(BFc)::value, Src>, HD>(c, c.grid(1), static_cast<const uint16_t*>(q),
+                                                                               Src{static_cast<const uint16_t*>(k_cache), static_cast<const uint16_t*>(v_cache)}, pos_dev,
+                                                                               static_cast<int>(rows), static_cast<uint16_t*>(out), static_cast<int>(n_heads),
+                                                                               static_cast<int>(n_kv_heads), static_cast<int>(cache_len), scaling, c.S(), c.ws());
   });
 }
 

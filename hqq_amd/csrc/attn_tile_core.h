@@ -1,14 +1,14 @@
-// attn_tile_core.h — the MFMA query-tile decode attention, stated once: attn_tile_kernel (attn_tile.hip: the tile is the R rows of a verify step) and the
-// grouped-query kernels (attn_gqa.hip: the tile is the G query heads of a KV group) hand attn_tile_body what differs between them and run this one text.
+// attn_tile_core.h — the MFMA query-tile attention, stated once: a kernel is a PLACEMENT (attn_tile.hip, attn_gqa.hip, attn_prefill.hip) times a row SOURCE
+// (DenseKV here, PackedKV in kv_load.h), and each hands attn_tile_body what differs.
 //   tile    where tile row t's query, output and split record live (a struct with rows, q(t), out(t), rec(t)); the positions arrive as n_max (1 + the largest
 //           clamped position of the tile) and pr (the clamped position of THIS lane's row, -1 for a padding row: every key masked)
-//   loaders krow(ch, j) / vrow(ch, j) -> u32x4: a lane's 8 dims (chunk ch of the row's HD / 8) of key / value row j as T, the signature of attn_decode_core.h.
-//           The K operand of lane (row, g) is chunks 4 c + g of its key, a V block is loaded as chunk x % (HD / 8) of row x / (HD / 8): both are that shape
-// The algorithm (blocks of 32 keys dealt round-robin to the waves, S^T = K . Q^T, mask before the maximum, the running (m, l, O), P rounded to T for V^T . P^T,
-// V through the wave's own LDS image with rows >= k1 replaced by zero, the in-order merge) is described at the head of attn_tile.hip.
-// Translation units that use the body are compiled with -ffp-contract=off (expf under the flags its error was measured with).
+//   source  a POD kernel argument; at(r0) gives the rows of one (sequence, KV head) from row r0 of the cache, with k(ch, j) / v(ch, j) -> u32x4: a lane's 8 dims
+//           (chunk ch of HD / 8) of key / value row j as T.  Lane (row, g) takes chunks 4 c + g of its key; a V block is chunk x % (HD / 8) of row x / (HD / 8)
+// The algorithm is described at the head of attn_tile.hip.  Translation units that use the body are compiled with -ffp-contract=off (expf under the flags its
+// error was measured with).
 #pragma once
 #include "block_math.h"
+#include "attn_decode_core.h"
 
 namespace hqq {
 
@@ -24,9 +24,28 @@ constexpr int tile_vstride() { return HD * 2 + 32; }
 template <int HD>
 constexpr int tile_lds_bytes() { return TILE_WAVES * TILE_KEYS * tile_vstride<HD>() + TILE_WAVES * TILE_ROWS * 2 * 4; }
 
-// ---- the attention of one workgroup (TILE_WAVES * 64 threads) over share sp of keys [0, n_max) for the rows of `tile`; smem: tile_lds_bytes<HD>() ----
-template <int HD, bool BF, class Tile, class KRow, class VRow>
-__device__ __forceinline__ void attn_tile_body(uint8_t* smem, const Tile& tile, int n_max, int pr, int sp, int S, float scaling, KRow krow, VRow vrow) {
+// ---- the dense cache as a row source: plain 16-byte loads of rows of HD values ----
+template <int HD>
+struct DenseKV {
+  const uint16_t* kc;
+  const uint16_t* vc;
+  struct Rows {
+    const uint16_t* K;
+    const uint16_t* V;
+    __device__ __forceinline__ u32x4 k(int ch, int j) const { return *reinterpret_cast<const u32x4*>(K + static_cast<int64_t>(j) * HD + 8 * ch); }
+    __device__ __forceinline__ u32x4 v(int ch, int j) const { return *reinterpret_cast<const u32x4*>(V + static_cast<int64_t>(j) * HD + 8 * ch); }
+  };
+  __device__ __forceinline__ Rows at(int64_t r0) const { return Rows{kc + r0 * HD, vc + r0 * HD}; }
+};
+
+// ---- the attention of one workgroup (TILE_WAVES * 64 threads) over share sp of keys [0, n_max) for the rows of `tile`, keys and values from `kv` (a source's rows);
+//      smem: tile_lds_bytes<HD>() ----
+template <int HD, bool BF, class Tile, class Rows>
+__device__ __forceinline__ void attn_tile_body(uint8_t* smem, const Tile& tile, int n_max, int pr, int sp, int S, float scaling, const Rows& kv) {
+  // (the two loaders as closures, not kv.k / kv.v called in place: in place, the compiler hoists one address computation elsewhere and the dense grouped kernels
+  //  lose the instruction-for-instruction identity that profiles/attn_tile_family_parity.md records)
+  auto krow = [&](int ch, int j) -> u32x4 { return kv.k(ch, j); };
+  auto vrow = [&](int ch, int j) -> u32x4 { return kv.v(ch, j); };
   using E = El<BF>;
   constexpr int NC = HD / 32, NT = HD / 16, VS = tile_vstride<HD>(), IMG = TILE_KEYS * VS;
   static_assert(IMG >= TILE_ROWS * HD * 4, "a wave's V image also parks its output tile [16][HD] fp32 for the merge");
@@ -154,6 +173,17 @@ __device__ __forceinline__ void attn_tile_body(uint8_t* smem, const Tile& tile, 
       if (d == 0) { rec[0] = mm; rec[1] = den; }
     }
   }
+}
+
+// ---- the launch of one instantiation of the family: Kern's LDS limit raised once per device (tile_lds_bytes<HD>() passes 48 KiB at head_dim 128 and 256), then the
+//      workgroups of TILE_WAVES waves.  0 or the error code with c.who's message ----
+template <auto Kern, int HD, class... Args>
+static inline int tile_launch(const AttnCall& c, dim3 grid, Args... args) {
+  constexpr int lds = tile_lds_bytes<HD>();
+  static LdsRaised raised;   // (one per instantiation)
+  if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(Kern), lds, lds, c.who)) return rc;
+  hipLaunchKernelGGL(Kern, grid, dim3(TILE_WAVES * 64), lds, as_stream(c.stream), args...);
+  return 0;
 }
 
 }  // namespace hqq

@@ -228,12 +228,6 @@ static inline bool kv_batch_ok(int64_t batch, const char* who) {
   return false;
 }
 
-// f(HD, NBITS, BF) as integral constants
-template <class F>
-static void kv_dispatch(int64_t hd, int nbits, bool bf, F&& f) {
-  attn_dispatch(hd, bf, [&](auto HDc, auto BFc) { if (nbits == 8) f(HDc, std::integral_constant<int, 8>{}, BFc); else f(HDc, std::integral_constant<int, 4>{}, BFc); });
-}
-
 static int attn_kvq_run(const char* who, int nbits, const void* q, const void* kq, const void* k_scale, const void* k_zero, const void* vq, const void* v_scale,
                         const void* v_zero, const int64_t* pos_dev, int64_t batch, void* out, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t group_size,
                         int64_t cache_len, float scaling, int dtype, int64_t splits, void* workspace, size_t workspace_bytes, void* stream) {
@@ -243,18 +237,16 @@ static int attn_kvq_run(const char* who, int nbits, const void* q, const void* k
   if (const int rc = attn_check(c, {q, kq, k_scale, k_zero, vq, v_scale, v_zero, pos_dev, out}, {q, kq, vq, out})) return rc;
   const int lds = attn_lds_launch(c.HD(), cache_len, c.S());   // (the dense kernel's layout and size)
   const int gs_shift = group_size == 64 ? 6 : 5;
-  return attn_launch(c, [&](auto HDc, auto BFc) {
-    auto go = [&](auto NBc) {
-      constexpr auto kern = &attn_decode_kvq_kernel<decltype(HDc)::value, decltype(NBc)::value, decltype(BFc)::value>;
-      static LdsRaised raised;   // (one per instantiation)
-      if (const int rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, ATTN_LDS_MAX, who)) return rc;
-      hipLaunchKernelGGL(kern, c.grid(batch), dim3(512), lds, as_stream(stream), static_cast<cu16>(q), static_cast<cu8>(kq), static_cast<cu16>(k_scale),
-                         static_cast<cu16>(k_zero), static_cast<cu8>(vq), static_cast<cu16>(v_scale), static_cast<cu16>(v_zero), pos_dev, static_cast<u16>(out),
-                         static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(cache_len), gs_shift, scaling, c.S(), c.ws());
-      return 0;
-    };
-    return nbits == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{});
+  int rc = 0;
+  kv_dispatch(head_dim, nbits, c.bf(), [&](auto HDc, auto NBc, auto BFc) {
+    constexpr auto kern = &attn_decode_kvq_kernel<decltype(HDc)::value, decltype(NBc)::value, decltype(BFc)::value>;
+    static LdsRaised raised;   // (one per instantiation)
+    if ((rc = attn_raise_lds(raised, reinterpret_cast<const void*>(kern), lds, ATTN_LDS_MAX, who))) return;
+    hipLaunchKernelGGL(kern, c.grid(batch), dim3(512), lds, as_stream(stream), static_cast<cu16>(q), static_cast<cu8>(kq), static_cast<cu16>(k_scale),
+                       static_cast<cu16>(k_zero), static_cast<cu8>(vq), static_cast<cu16>(v_scale), static_cast<cu16>(v_zero), pos_dev, static_cast<u16>(out),
+                       static_cast<int>(n_heads), static_cast<int>(n_kv_heads), static_cast<int>(cache_len), gs_shift, scaling, c.S(), c.ws());
   });
+  return attn_finish(c, rc);
 }
 
 extern "C" {

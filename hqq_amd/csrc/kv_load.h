@@ -1,9 +1,10 @@
-// kv_load.h — what every reader of the quantised KV cache shares (the format is described at the head of kv_cache.hip): the rebuild of a lane's 8 dims of a stored
-// row to T, and the cache's one coverage rule.  kv_cache.hip (the one-row attention, the write and expansion kernels) and attn_gqa.hip (the grouped-query
-// attention) include it.  Translation units that use kv_load8 are compiled with -ffp-contract=off: CD<T>::dequant's two roundings stay separate.
+// kv_load.h — what every reader of the quantised KV cache shares (format: the head of kv_cache.hip): the rebuild of a lane's 8 dims of a stored row to T, the cache
+// as a row source of the tile attention (attn_tile_core.h), its one coverage rule and its dispatch.  Translation units that use kv_load8 are compiled with
+// -ffp-contract=off: CD<T>::dequant's two roundings stay separate.
 #pragma once
 #include "hqq_common.h"
 #include "block_math.h"
+#include "attn_decode_core.h"
 
 namespace hqq {
 
@@ -64,6 +65,47 @@ __device__ __forceinline__ u32x4 kv_load8(const uint8_t* __restrict__ qrow, cons
   return out;
 }
 
+// ---- the six buffers as a row source of the tile family (attn_tile_core.h states what a source is): row j of a (sequence, KV head) rebuilt to T as it is loaded.
+//      The row index is widened signed, the code these kernels always had (kv_cache.hip's widen_t was tuned for the one-row kernels) ----
+template <int HD, int NBITS, bool BF>
+struct PackedKV {
+  const uint8_t* kq;
+  const uint16_t* ks;
+  const uint16_t* kz;
+  const uint8_t* vq;
+  const uint16_t* vs;
+  const uint16_t* vz;
+  int gs_shift;
+  static constexpr int RB = HD * NBITS / 8;   // bytes of levels per row
+  struct Rows {
+    const uint8_t* kq;
+    const uint16_t* ks;
+    const uint16_t* kz;
+    const uint8_t* vq;
+    const uint16_t* vs;
+    const uint16_t* vz;
+    int NG, gs_shift;   // NG: (scale, zero) pairs per row
+    __device__ __forceinline__ u32x4 k(int ch, int j) const {
+      const int64_t r = j;
+      return kv_load8<HD, NBITS, BF>(kq + r * RB, ks + r * NG, kz + r * NG, ch, gs_shift);
+    }
+    __device__ __forceinline__ u32x4 v(int ch, int j) const {
+      const int64_t r = j;
+      return kv_load8<HD, NBITS, BF>(vq + r * RB, vs + r * NG, vz + r * NG, ch, gs_shift);
+    }
+  };
+  __device__ __forceinline__ Rows at(int64_t r0) const {
+    const int NG = HD >> gs_shift;
+    return Rows{kq + r0 * RB, ks + r0 * NG, kz + r0 * NG, vq + r0 * RB, vs + r0 * NG, vz + r0 * NG, NG, gs_shift};
+  }
+  // an entry point's six buffers and group size (32 / 64: kv_check) as the source
+  static PackedKV of(const void* kq, const void* ks, const void* kz, const void* vq, const void* vs, const void* vz, int64_t group_size) {
+    using u8 = const uint8_t*;
+    using u16 = const uint16_t*;
+    return PackedKV{static_cast<u8>(kq), static_cast<u16>(ks), static_cast<u16>(kz), static_cast<u8>(vq), static_cast<u16>(vs), static_cast<u16>(vz), group_size == 64 ? 6 : 5};
+  }
+};
+
 // the one coverage rule of the quantised cache (hqq_hip_kv_covers); 0 where covered, else the error code with `who`'s message
 static inline int kv_check(const char* who, int nbits, int64_t head_dim, int64_t group_size, int64_t cache_len, int dtype) {
   if (dtype != HQQ_F16 && dtype != HQQ_BF16) { set_error("%s: not covered: fp16 / bf16 only (dtype %d)", who, dtype); return HQQ_ERR_UNSUPPORTED; }
@@ -75,6 +117,12 @@ static inline int kv_check(const char* who, int nbits, int64_t head_dim, int64_t
   }
   if (cache_len < 1 || cache_len > 30000) { set_error("%s: not covered: cache_len %lld outside [1, 30000]", who, (long long)cache_len); return HQQ_ERR_UNSUPPORTED; }
   return 0;
+}
+
+// f(HD, NBITS, BF) as integral constants, for a covered head_dim and width
+template <class F>
+static inline void kv_dispatch(int64_t hd, int nbits, bool bf, F&& f) {
+  attn_dispatch(hd, bf, [&](auto HDc, auto BFc) { if (nbits == 8) f(HDc, std::integral_constant<int, 8>{}, BFc); else f(HDc, std::integral_constant<int, 4>{}, BFc); });
 }
 
 }  // namespace hqq

@@ -1357,17 +1357,29 @@ def token_prologue(tok: Tensor, pos: Tensor, embed: Tensor, h: Tensor, cos_tab=N
     token_prologue_batched(tok, _seq1(pos), embed, h, cos_tab, sin_tab, cos, sin, mask)
 
 
+def _batched_cache(who: str, k_cache: Tensor, v_cache: Tensor, B: int):
+    """the dense caches [B, n_kv, L, hd] of B sequences: (n_kv, L, hd)"""
+    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise ValueError(f"hqq_amd: {who} takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
+    return tuple(int(x) for x in k_cache.shape[1:])
+
+
+def _qkv_extents(who: str, n: int, n_kv: int, hd: int, q: Tensor, k: Tensor, v: Tensor, q_out: Tensor, cos: Tensor, sin: Tensor, dt=None, R: str = "B", tail: str = "") -> int:
+    """the extents every rotary-and-cache front (`who`) asks of its row tensors, n rows (R in the message, which `tail` ends) against caches of n_kv heads of hd
+    values: dense q / q_out [n, n_heads * hd], k / v [n, n_kv * hd] and cos / sin [n, hd], all of dtype dt where one is given.  Returns n_heads."""
+    ts = (q, k, v, q_out, cos, sin)
+    if hd < 1 or cos.numel() != n * hd or sin.numel() != n * hd or any(t.numel() % (n * hd) or not t.is_contiguous() for t in ts) or \
+            k.numel() != n * n_kv * hd or v.numel() != k.numel() or q_out.numel() != q.numel() or (dt is not None and any(t.dtype != dt for t in ts)):
+        raise ValueError(f"hqq_amd: {who} takes dense q / q_out [{R}, n_heads * hd], k / v [{R}, n_kv_heads * hd] and cos / sin [{R}, hd]{tail}")
+    return q.numel() // (n * hd)
+
+
 def _rope_cache_args(who: str, q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor):
     """what rope_cache_batched, qknorm_rope_cache_batched and bias_rope_cache_batched (`who`) all ask of their tensors: dense caches of the positions' batch and
     q / k / v / q_out / cos / sin of matching extents.  Returns (B, head_dim, n_heads, n_kv_heads, cache_len), what the launches are given."""
     B = _batch_of(pos, who)
-    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
-        raise ValueError(f"hqq_amd: {who} takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
-    _, n_kv, L, hd = k_cache.shape
-    if cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
-            k.numel() != B * n_kv * hd or v.numel() != k.numel() or q_out.numel() != q.numel():
-        raise ValueError(f"hqq_amd: {who} takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd]")
-    return B, hd, q.numel() // (B * hd), n_kv, L
+    n_kv, L, hd = _batched_cache(who, k_cache, v_cache, B)
+    return B, hd, _qkv_extents(who, B, n_kv, hd, q, k, v, q_out, cos, sin), n_kv, L
 
 
 def rope_cache_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor, pos: Tensor, k_cache: Tensor, v_cache: Tensor, q_out: Tensor) -> Tensor:
@@ -1434,14 +1446,43 @@ def bias_rope_cache(q: Tensor, k: Tensor, v: Tensor, q_bias: Tensor, k_bias: Ten
     return bias_rope_cache_batched(q, k, v, q_bias, k_bias, v_bias, cos, sin, _seq1(pos), _cache1(k_cache), _cache1(v_cache), q_out)
 
 
-def _attn_batched_args(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, who: str):
+def _dense(cache) -> tuple:
+    """the tensors of a dense pair (k_cache, v_cache), () for (bufs, head_dim): _kv_bufs looks at the six buffers itself"""
+    return tuple(cache) if isinstance(cache[1], Tensor) else ()
+
+
+def _attn_cache(who: str, cache, B):
+    """the cache an attention front (`who`) is given, checked.  cache: the dense pair (k_cache, v_cache), or (bufs, head_dim) for the six buffers of a quantised
+    cache (below); B: the sequences of the positions' batch, or None for ONE sequence's cache ([n_kv, L, .] or [1, n_kv, L, .]).  Returns (n_kv, L, hd, dtype,
+    head, ptrs, gs): what the library is given in front of q (the width, for the buffers), the cache's pointers, and (the group size,) or ()."""
+    if isinstance(cache[1], Tensor):
+        k_cache, v_cache = cache
+        n_kv, L, hd = _shared_cache(who, k_cache, v_cache) if B is None else _batched_cache(who, k_cache, v_cache, B)
+        if v_cache.dtype != k_cache.dtype:
+            raise ValueError(f"hqq_amd: {who} takes caches of one dtype (k_cache {k_cache.dtype}, v_cache {v_cache.dtype})")
+        return n_kv, L, hd, k_cache.dtype, (), (_p(k_cache), _p(v_cache)), ()
+    bufs, hd = cache
+    if B is None:
+        if len(bufs) != 6 or not all(isinstance(t, Tensor) and t.dim() in (3, 4) and (t.dim() == 3 or t.shape[0] == 1) for t in bufs):
+            raise ValueError(f"hqq_amd: {who} takes ONE sequence's six cache buffers (kq, k_scale, k_zero, vq, v_scale, v_zero) [n_kv_heads, cache_len, .] (or [1, ...])")
+        bufs = tuple(t.view(1, *t.shape[-3:]) for t in bufs)
+    Bc, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, int(hd), who)
+    if B is not None and Bc != B:
+        raise ValueError(f"hqq_amd: {who} takes buffers of the positions' batch ({Bc} sequences against {B} positions)")
+    return n_kv, L, int(hd), dt, (nbits,), tuple(_p(t) for t in bufs), (gs,)
+
+
+def _attn_args(who: str, q: Tensor, cache, pos: Tensor, out: Tensor, rows: bool = False):
+    """what every decode-attention front (`who`) asks of (q, cache, pos, out): tensors on the device, dense int64 positions, the cache of _attn_cache — of the
+    positions' batch, or with rows=True ONE sequence's, the positions being R rows of it —, and dense q / out [B, n_heads * hd] of the cache's dtype.
+    Returns (B, n_heads) and _attn_cache's tuple."""
+    _dev(q, pos, out, *_dense(cache))
     B = _batch_of(pos, who)
-    if k_cache.dim() != 4 or k_cache.shape[0] != B or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or not v_cache.is_contiguous():
-        raise ValueError(f"hqq_amd: {who} takes dense [B, n_kv_heads, cache_len, head_dim] caches, B the positions' count")
-    _, n_kv, L, hd = k_cache.shape
-    if q.numel() % (B * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous():
-        raise ValueError(f"hqq_amd: {who} takes dense q / out [B, n_heads * head_dim]")
-    return B, q.numel() // (B * hd), n_kv, L, hd
+    c = _attn_cache(who, cache, None if rows else B)
+    hd, dt = c[2], c[3]
+    if hd < 1 or q.numel() % (B * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or q.dtype != dt or out.dtype != dt:
+        raise ValueError(f"hqq_amd: {who} takes dense q / out [{'R' if rows else 'B'}, n_heads * head_dim] of the cache's dtype")
+    return B, q.numel() // (B * hd), c
 
 
 def attn_splits(kv_len: int) -> int:
@@ -1468,20 +1509,24 @@ def _split_workspace(workspace, splits: int, device, rows: int, n_heads: int, he
     return _p(workspace), 0 if workspace is None else workspace.numel(), workspace
 
 
+def _attn_front(symbol: str, who: str, q: Tensor, cache, pos: Tensor, out: Tensor, scaling: float, splits: int, workspace, rows: bool = False) -> Tensor:
+    """the one front of the decode-attention calls on (q, cache, pos, out) — public function `who`, library entry point `symbol`; cache and rows as in
+    _attn_args: the checks, the record buffer of a split launch, the call"""
+    B, n_heads, (n_kv, L, hd, dt, head, ptrs, gs) = _attn_args(who, q, cache, pos, out, rows)
+    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
+    with torch.cuda.device(q.device):
+        rc = getattr(_C.lib(), symbol)(*head, _p(q), *ptrs, _p(pos), B, _p(out), n_heads, n_kv, hd, *gs, L, float(scaling), _dt(dt), int(splits), ws_ptr, ws_bytes, _stream())
+    _C.check(rc, symbol)
+    return out
+
+
 def attn_decode_batched(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
     """one query per head and sequence against the static KV caches, B sequences in one launch (fp16 / bf16; within rounding of SDPA, not bit-identical):
     q / out [B, n_heads * hd] (any dense view of those values), caches [B, n_kv, cache_len, hd], pos int64 [B] on the device; sequence b attends over its own first
     pos[b] + 1 keys.  splits > 1: the keys of a head shared out over that many workgroups + a merging launch (long caches; attn_splits / attn_workspace_batched).
     splits is one for the whole launch (pick it from the largest position): a sequence with fewer visible keys than splits
     leaves the surplus shares empty, and the merging launch ignores them"""
-    _dev(q, k_cache, v_cache, pos, out)
-    B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "attn_decode_batched")
-    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_decode_batched(_p(q), _p(k_cache), _p(v_cache), _p(pos), B, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
-                                                  int(splits), ws_ptr, ws_bytes, _stream())
-    _C.check(rc, "hqq_hip_attn_decode_batched")
-    return out
+    return _attn_front("hqq_hip_attn_decode_batched", "attn_decode_batched", q, (k_cache, v_cache), pos, out, scaling, splits, workspace)
 
 
 def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
@@ -1494,8 +1539,8 @@ def rope_attn_decode_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: 
     """rope_cache_batched + attn_decode_batched in one launch: raw q [B, n_heads * hd], k / v [B, n_kv * hd], cos / sin [B, hd]; rotary applied in the kernel, each
     sequence's new key / value used from on-chip memory and written to its own cache row at pos[b] for the following steps (the caches end up bit-identical to
     rope_cache_batched's); splits as in attn_decode_batched"""
-    _dev(q, k, v, cos, sin, pos, k_cache, v_cache, out)
-    B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "rope_attn_decode_batched")
+    _dev(k, v, cos, sin)
+    B, n_heads, (n_kv, L, hd, *_) = _attn_args("rope_attn_decode_batched", q, (k_cache, v_cache), pos, out)
     if cos.numel() != B * hd or sin.numel() != B * hd or k.numel() != B * n_kv * hd or v.numel() != k.numel() or \
             not all(t.is_contiguous() for t in (k, v, cos, sin)):
         raise ValueError("hqq_amd: rope_attn_decode_batched takes dense k / v [B, n_kv_heads * head_dim] and cos / sin [B, head_dim]")
@@ -1522,8 +1567,8 @@ SPEC_MAX_NGRAM = 4
 def _shared_cache(who: str, k_cache: Tensor, v_cache: Tensor):
     """one sequence's caches [n_kv, L, hd] or [1, n_kv, L, hd] (a batch-1 StaticCache's tensors): (n_kv, L, hd)"""
     if k_cache.dim() not in (3, 4) or (k_cache.dim() == 4 and k_cache.shape[0] != 1) or v_cache.shape != k_cache.shape or not k_cache.is_contiguous() or \
-            not v_cache.is_contiguous():
-        raise ValueError(f"hqq_amd: {who} takes ONE sequence's dense caches [n_kv_heads, cache_len, head_dim] (or [1, ...])")
+            not v_cache.is_contiguous() or v_cache.dtype != k_cache.dtype:
+        raise ValueError(f"hqq_amd: {who} takes ONE sequence's dense caches [n_kv_heads, cache_len, head_dim] (or [1, ...]) of one dtype")
     return tuple(int(x) for x in k_cache.shape[-3:])
 
 
@@ -1534,38 +1579,18 @@ def rope_cache_shared(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor,
     _dev(q, k, v, cos, sin, pos, k_cache, v_cache, q_out)
     R = _batch_of(pos, "rope_cache_shared")
     n_kv, L, hd = _shared_cache("rope_cache_shared", k_cache, v_cache)
-    if cos.numel() != R * hd or sin.numel() != R * hd or any(t.numel() % (R * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
-            k.numel() != R * n_kv * hd or v.numel() != k.numel() or q_out.numel() != q.numel() or \
-            any(t.dtype != q.dtype for t in (k, v, cos, sin, k_cache, v_cache, q_out)):
-        raise ValueError("hqq_amd: rope_cache_shared takes dense q / q_out [R, n_heads * hd], k / v [R, n_kv_heads * hd] and cos / sin [R, hd] of the caches' dtype")
+    n_heads = _qkv_extents("rope_cache_shared", R, n_kv, hd, q, k, v, q_out, cos, sin, dt=k_cache.dtype, R="R", tail=" of the caches' dtype")
     with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_rope_cache_shared(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), R, _p(q_out), _p(k_cache), _p(v_cache), q.numel() // (R * hd), n_kv, hd, L,
-                                                _dt(q.dtype), _stream())
+        rc = _C.lib().hqq_hip_rope_cache_shared(_p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), R, _p(q_out), _p(k_cache), _p(v_cache), n_heads, n_kv, hd, L, _dt(q.dtype), _stream())
     _C.check(rc, "hqq_hip_rope_cache_shared")
     return q_out
-
-
-def _attn_decode_rows(symbol: str, who: str, q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int, workspace) -> Tensor:
-    """the R rows of ONE sequence against its caches through entry point `symbol` (attn_decode_shared / attn_decode_tiled: the same arguments)"""
-    _dev(q, k_cache, v_cache, pos, out)
-    R = _batch_of(pos, who)
-    n_kv, L, hd = _shared_cache(who, k_cache, v_cache)
-    if q.numel() % (R * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or any(t.dtype != q.dtype for t in (k_cache, v_cache, out)):
-        raise ValueError(f"hqq_amd: {who} takes dense q / out [R, n_heads * head_dim] of the caches' dtype")
-    n_heads = q.numel() // (R * hd)
-    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, R, n_heads, hd)
-    with torch.cuda.device(q.device):
-        rc = getattr(_C.lib(), symbol)(_p(q), _p(k_cache), _p(v_cache), _p(pos), R, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype), int(splits), ws_ptr, ws_bytes,
-                                       _stream())
-    _C.check(rc, symbol)
-    return out
 
 
 def attn_decode_shared(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
     """attn_decode_batched for R queries of ONE sequence against that sequence's caches [n_kv, L, hd] (or [1, n_kv, L, hd]) (hqq_hip_attn_decode_shared): q / out
     [R, n_heads * hd], pos int64 [R]; row i attends over keys [0, pos[i]] and is bit-identical to attn_decode with row i's query and position and the same
     splits.  Splits and workspace as attn_decode_batched at R rows (attn_workspace_batched(device, R, ...))."""
-    return _attn_decode_rows("hqq_hip_attn_decode_shared", "attn_decode_shared", q, k_cache, v_cache, pos, out, scaling, splits, workspace)
+    return _attn_front("hqq_hip_attn_decode_shared", "attn_decode_shared", q, (k_cache, v_cache), pos, out, scaling, splits, workspace, rows=True)
 
 
 def attn_decode_tiled(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
@@ -1573,7 +1598,7 @@ def attn_decode_tiled(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, 
     one workgroup per (head, split), the rows as one MFMA tile, flash-decoding over blocks of 32 keys.  Its own contract: deterministic, row i independent of the
     other rows' queries, within a derived band of float64 attention (tests/_tile_cases.py) — NOT bit-identical to attn_decode.  Splits and workspace as
     attn_decode_shared (attn_workspace_batched(device, R, ...))."""
-    return _attn_decode_rows("hqq_hip_attn_decode_tiled", "attn_decode_tiled", q, k_cache, v_cache, pos, out, scaling, splits, workspace)
+    return _attn_front("hqq_hip_attn_decode_tiled", "attn_decode_tiled", q, (k_cache, v_cache), pos, out, scaling, splits, workspace, rows=True)
 
 
 def _i64_dev(who: str, **tensors) -> None:
@@ -1717,13 +1742,12 @@ def rope_kvq_cache_batched(q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Te
     B = _batch_of(pos, "rope_kvq_cache_batched")
     hd = cos.numel() // B
     Bc, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, hd, "rope_kvq_cache_batched")
-    if Bc != B or cos.numel() != B * hd or sin.numel() != B * hd or any(t.numel() % (B * hd) or not t.is_contiguous() for t in (q, k, v, q_out, cos, sin)) or \
-            k.numel() != B * n_kv * hd or v.numel() != k.numel() or q_out.numel() != q.numel() or any(t.dtype != dt for t in (q, k, v, cos, sin, q_out)):
-        raise ValueError("hqq_amd: rope_kvq_cache_batched takes dense q / q_out [B, n_heads * hd], k / v [B, n_kv_heads * hd] and cos / sin [B, hd] of the buffers' dtype, "
-                         "B the positions' count and the buffers' batch")
+    if Bc != B:
+        raise ValueError(f"hqq_amd: rope_kvq_cache_batched takes buffers of the positions' batch ({Bc} sequences against {B} positions)")
+    n_heads = _qkv_extents("rope_kvq_cache_batched", B, n_kv, hd, q, k, v, q_out, cos, sin, dt=dt, tail=" of the buffers' dtype")
     with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_rope_kvq_cache_batched(nbits, _p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), B, _p(q_out), *(_p(t) for t in bufs), q.numel() // (B * hd),
-                                                     n_kv, hd, gs, L, _dt(dt), _stream())
+        rc = _C.lib().hqq_hip_rope_kvq_cache_batched(nbits, _p(q), _p(k), _p(v), _p(cos), _p(sin), _p(pos), B, _p(q_out), *(_p(t) for t in bufs), n_heads, n_kv, hd, gs, L,
+                                                     _dt(dt), _stream())
     _C.check(rc, "hqq_hip_rope_kvq_cache_batched")
     return q_out
 
@@ -1732,19 +1756,7 @@ def attn_decode_kvq_batched(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: 
     """attn_decode_batched on a quantised cache: q / out [B, n_heads * hd], the six buffers, pos int64 [B] on the device; every row is rebuilt to the compute dtype
     as it is loaded and the rest is attn_decode_batched's arithmetic in its order — the output has the bits of attn_decode_batched on kv_dequantize's tensors with
     the same splits.  Nothing at or beyond pos[b] + 1 is read.  splits / workspace as in attn_decode_batched (attn_workspace_batched)."""
-    _dev(q, pos, out)
-    B = _batch_of(pos, "attn_decode_kvq_batched")
-    hd = int(head_dim)
-    Bc, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, hd, "attn_decode_kvq_batched")
-    if Bc != B or q.numel() % (B * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or q.dtype != dt or out.dtype != dt:
-        raise ValueError("hqq_amd: attn_decode_kvq_batched takes dense q / out [B, n_heads * head_dim] of the buffers' dtype, B the positions' count and the buffers' batch")
-    n_heads = q.numel() // (B * hd)
-    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_decode_kvq_batched(nbits, _p(q), *(_p(t) for t in bufs), _p(pos), B, _p(out), n_heads, n_kv, hd, gs, L, float(scaling), _dt(dt),
-                                                      int(splits), ws_ptr, ws_bytes, _stream())
-    _C.check(rc, "hqq_hip_attn_decode_kvq_batched")
-    return out
+    return _attn_front("hqq_hip_attn_decode_kvq_batched", "attn_decode_kvq_batched", q, (bufs, head_dim), pos, out, scaling, splits, workspace)
 
 
 def attn_decode_kvq(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: float, head_dim: int, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
@@ -1782,14 +1794,7 @@ def attn_gqa_splits(kv_len: int, batch: int, n_kv_heads: int) -> int:
 def attn_decode_gqa_batched(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
     """attn_decode_batched's arguments through the grouped kernel (hqq_hip_attn_decode_gqa_batched): grid (n_kv, splits, B), the query heads of a KV group as one
     MFMA tile.  n_heads / n_kv_heads up to 16.  Splits and workspace as attn_decode_batched (attn_gqa_splits / attn_workspace_batched)."""
-    _dev(q, k_cache, v_cache, pos, out)
-    B, n_heads, n_kv, L, hd = _attn_batched_args(q, k_cache, v_cache, pos, out, "attn_decode_gqa_batched")
-    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_decode_gqa_batched(_p(q), _p(k_cache), _p(v_cache), _p(pos), B, _p(out), n_heads, n_kv, hd, L, float(scaling), _dt(q.dtype),
-                                                      int(splits), ws_ptr, ws_bytes, _stream())
-    _C.check(rc, "hqq_hip_attn_decode_gqa_batched")
-    return out
+    return _attn_front("hqq_hip_attn_decode_gqa_batched", "attn_decode_gqa_batched", q, (k_cache, v_cache), pos, out, scaling, splits, workspace)
 
 
 def attn_decode_gqa(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, out: Tensor, scaling: float, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
@@ -1800,19 +1805,7 @@ def attn_decode_gqa(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, ou
 def attn_decode_gqa_kvq_batched(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: float, head_dim: int, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
     """attn_decode_kvq_batched's arguments through the grouped kernel (hqq_hip_attn_decode_gqa_kvq_batched): a packed row is rebuilt once per KV group; the output
     has the bits of attn_decode_gqa_batched on kv_dequantize's tensors with the same splits.  Nothing at or beyond pos[b] + 1 is read."""
-    _dev(q, pos, out)
-    B = _batch_of(pos, "attn_decode_gqa_kvq_batched")
-    hd = int(head_dim)
-    Bc, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, hd, "attn_decode_gqa_kvq_batched")
-    if Bc != B or q.numel() % (B * hd) or out.numel() != q.numel() or not q.is_contiguous() or not out.is_contiguous() or q.dtype != dt or out.dtype != dt:
-        raise ValueError("hqq_amd: attn_decode_gqa_kvq_batched takes dense q / out [B, n_heads * head_dim] of the buffers' dtype, B the positions' count and the buffers' batch")
-    n_heads = q.numel() // (B * hd)
-    ws_ptr, ws_bytes, _ws = _split_workspace(workspace, splits, q.device, B, n_heads, hd)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_decode_gqa_kvq_batched(nbits, _p(q), *(_p(t) for t in bufs), _p(pos), B, _p(out), n_heads, n_kv, hd, gs, L, float(scaling), _dt(dt),
-                                                          int(splits), ws_ptr, ws_bytes, _stream())
-    _C.check(rc, "hqq_hip_attn_decode_gqa_kvq_batched")
-    return out
+    return _attn_front("hqq_hip_attn_decode_gqa_kvq_batched", "attn_decode_gqa_kvq_batched", q, (bufs, head_dim), pos, out, scaling, splits, workspace)
 
 
 def attn_decode_gqa_kvq(q: Tensor, bufs, pos: Tensor, out: Tensor, scaling: float, head_dim: int, splits: int = 1, workspace: Tensor | None = None) -> Tensor:
@@ -1850,6 +1843,18 @@ def _prefill_q(who: str, q: Tensor, pos0, L: int, hd: int, dt, out):
     return T, n_heads, pos0, out
 
 
+def _prefill_front(symbol: str, who: str, q: Tensor, cache, pos0, out, scaling) -> Tensor:
+    """the one front of the prompt calls — public function `who`, library entry point `symbol`, ONE sequence's cache as in _attn_cache"""
+    _dev(q, out, *_dense(cache))
+    n_kv, L, hd, dt, head, ptrs, gs = _attn_cache(who, cache, None)
+    T, n_heads, pos0, out = _prefill_q(who, q, pos0, L, hd, dt, out)
+    with torch.cuda.device(q.device):
+        rc = getattr(_C.lib(), symbol)(*head, _p(q), q.stride(0), q.stride(1), *ptrs, pos0, T, _p(out), n_heads, n_kv, hd, *gs, L,
+                                       float(hd ** -0.5 if scaling is None else scaling), _dt(dt), _stream())
+    _C.check(rc, symbol)
+    return out.view(T, n_heads, hd)
+
+
 def attn_prefill(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos0: int, out: Tensor | None = None, scaling: float | None = None) -> Tensor:
     """Causal attention of a prompt's T rows on ONE sequence's dense static cache (hqq_hip_attn_prefill, csrc/attn_prefill.hip).  q [T, n_heads, hd]: any view
     with a dense last dimension — HF's [1, H, T, hd] query goes in as query[0].transpose(0, 1), through its strides, without a copy; k_cache / v_cache
@@ -1858,16 +1863,7 @@ def attn_prefill(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos0: int, out: Te
     fp16 / bf16, hd 64 / 128 / 256, n_heads a multiple of n_kv, L <= 30000.  A prompt that does not fit the cache is a ValueError (no clamping).
     Contract (a) - (g) above: per 16-row tile the bits of attn_decode_tiled (splits = 1), within tests/_tile_cases.py's band of float64 attention, nothing at or
     beyond pos0 + T read, exactly causal, deterministic and independent of q's strides — and NOT the bits of SDPA."""
-    _dev(q, k_cache, v_cache, out)
-    n_kv, L, hd = _shared_cache("attn_prefill", k_cache, v_cache)
-    if v_cache.dtype != k_cache.dtype:
-        raise ValueError("hqq_amd: attn_prefill takes caches of one dtype")
-    T, n_heads, pos0, out = _prefill_q("attn_prefill", q, pos0, L, hd, k_cache.dtype, out)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_prefill(_p(q), q.stride(0), q.stride(1), _p(k_cache), _p(v_cache), pos0, T, _p(out), n_heads, n_kv, hd, L,
-                                           float(hd ** -0.5 if scaling is None else scaling), _dt(q.dtype), _stream())
-    _C.check(rc, "hqq_hip_attn_prefill")
-    return out.view(T, n_heads, hd)
+    return _prefill_front("hqq_hip_attn_prefill", "attn_prefill", q, (k_cache, v_cache), pos0, out, scaling)
 
 
 def attn_prefill_kvq(q: Tensor, bufs, pos0: int, head_dim: int, out: Tensor | None = None, scaling: float | None = None) -> Tensor:
@@ -1875,18 +1871,7 @@ def attn_prefill_kvq(q: Tensor, bufs, pos0: int, head_dim: int, out: Tensor | No
     rows' quantised keys and values; every attended row is rebuilt to the compute dtype as it is loaded and the rest is attn_prefill's arithmetic in its order —
     the output has the bits of attn_prefill on kv_dequantize's tensors (contract (c)), and no full-length dequantised tensor exists.  Nothing at or beyond
     pos0 + T is read, in levels or in meta.  Covered where ops.kv_covers holds (NotImplementedError otherwise)."""
-    _dev(q, out)
-    if len(bufs) != 6 or not all(isinstance(t, Tensor) and t.dim() in (3, 4) and (t.dim() == 3 or t.shape[0] == 1) for t in bufs):
-        raise ValueError("hqq_amd: attn_prefill_kvq takes ONE sequence's six cache buffers (kq, k_scale, k_zero, vq, v_scale, v_zero) [n_kv_heads, cache_len, .] (or [1, ...])")
-    bufs = tuple(t.view(1, *t.shape[-3:]) for t in bufs)
-    hd = int(head_dim)
-    _, n_kv, L, nbits, gs, dt = _kv_bufs(bufs, hd, "attn_prefill_kvq")
-    T, n_heads, pos0, out = _prefill_q("attn_prefill_kvq", q, pos0, L, hd, dt, out)
-    with torch.cuda.device(q.device):
-        rc = _C.lib().hqq_hip_attn_prefill_kvq(nbits, _p(q), q.stride(0), q.stride(1), *(_p(t) for t in bufs), pos0, T, _p(out), n_heads, n_kv, hd, gs, L,
-                                               float(hd ** -0.5 if scaling is None else scaling), _dt(dt), _stream())
-    _C.check(rc, "hqq_hip_attn_prefill_kvq")
-    return out.view(T, n_heads, hd)
+    return _prefill_front("hqq_hip_attn_prefill_kvq", "attn_prefill_kvq", q, (bufs, head_dim), pos0, out, scaling)
 
 
 def argmax_advance_batched(logits: Tensor, next_tok: Tensor, tok: Tensor | None = None, pos: Tensor | None = None) -> None:

@@ -292,3 +292,27 @@ def test_positions_outside_the_cache(L, dt, hd, S, rope, batched):
         assert torch.equal(A.bits(got), A.bits(want)), f"pos {group}: {int((A.bits(got) != A.bits(want)).sum())} outputs differ from those at pos = L - 1"
         assert torch.equal(kbuf, kbefore) and torch.equal(vbuf, vbefore), f"pos {group}: a cache (or a guard band around it) was written"
         assert _guards_intact(obuf, og) and _guards_intact(kbuf, kg) and _guards_intact(vbuf, vg), f"pos {group}: a guard band was written"
+
+
+def test_dense_batched_fronts_refuse_a_cache_of_another_dtype():
+    """An fp16 q against a bf16 cache, then against an fp16 k_cache with only v_cache in bf16: each dense batched front raises ValueError before anything is
+    launched (the kernel would read the cache's 16-bit words as q's type), and out stays untouched."""
+    from hqq_amd import ops
+
+    hd, heads, cache_len = 64, 2, 8
+    g = torch.Generator().manual_seed(0)
+    q, k, v = (torch.randn(1, heads * hd, generator=g).half().cuda() for _ in range(3))
+    kc, vc = (torch.randn(1, heads, cache_len, hd, generator=g).bfloat16().cuda() for _ in range(2))
+    cos, sin = torch.ones(1, hd, dtype=torch.float16, device="cuda"), torch.zeros(1, hd, dtype=torch.float16, device="cuda")
+    pos = torch.tensor([3], dtype=torch.int64, device="cuda")
+    out = torch.full((1, heads * hd), 7.0, dtype=torch.float16, device="cuda")
+    before = out.clone()
+    for k_cache, v_cache in ((kc, vc), (kc.half(), vc)):
+        with pytest.raises(ValueError):
+            ops.attn_decode_batched(q, k_cache, v_cache, pos, out, hd ** -0.5)
+        with pytest.raises(ValueError):
+            ops.attn_decode_gqa_batched(q, k_cache, v_cache, pos, out, hd ** -0.5)
+        with pytest.raises(ValueError):
+            ops.rope_attn_decode_batched(q, k, v, cos, sin, pos, k_cache, v_cache, out, hd ** -0.5)
+    torch.cuda.synchronize()
+    assert torch.equal(out, before), "out was written by a refused call"
